@@ -78,6 +78,36 @@ def mfma_roofline(kind, macs_per_term, k1_ms):
             "unit": "TFLOP/s", "frac": round(ach / peak, 4), "note": "executed " + what}
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this much in all (a seeded sample of the outputs beyond it)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: write what the timed path computed in its last step as `path`/<name>.npy (float32).
+    `arrays`: (name, tensor or array, axis) with 2-D arrays.  When they hold more than `budget` bytes, every array keeps the
+    same fraction of its indices along `axis`, a fixed seeded sample in ascending order, and `<name>_index.npy` (float64)
+    says which ones were kept."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = [(name, a.detach().float().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, np.float32), axis)
+              for name, a, axis in arrays]
+    total = sum(a.nbytes for _, a, _ in arrays)
+    # bytes per kept index: the slice itself and its float64 entry in the index file (plus a page for the .npy headers)
+    per_index = sum(a.shape[axis] * (a.nbytes // max(a.shape[axis], 1) + 8) for _, a, axis in arrays)
+    keep = 1.0 if total <= budget else (budget - 4096 * 2 * len(arrays)) / per_index
+    written = []
+    for name, a, axis in arrays:
+        if keep < 1.0:
+            n = a.shape[axis]
+            idx = np.sort(np.random.default_rng(20240101).choice(n, max(1, int(n * keep)), replace=False))
+            a = np.take(a, idx, axis=axis)
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            written.append(name + "_index.npy")
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written.append(name + ".npy")
+    print(f"bench.py: wrote {', '.join(written)} to {path}" + ("" if keep >= 1.0 else f" (a seeded sample: {keep:.3f} of each)"),
+          file=sys.stderr, flush=True)
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -122,6 +152,8 @@ def producer_bench(args):
         step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("direct", direct, 0), ("diffuse", diffuse, 0)])
     # parity of what was timed (a sample of it) and the CPU baseline: the oracle's PolarExtent, one thread
     import _oracle
     k = min(n, 2000)
@@ -209,7 +241,9 @@ def refbench(args):
     t, v = points(m, total)
     g = capi.GainInterp(ctx, m, n_out)
     g.set_points(t, v)
-    x = torch.rand((m, total), device=dev, dtype=torch.float32) * 2.0 - 1.0
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(6)
+    x = torch.rand((m, total), generator=gen, device=dev, dtype=torch.float32) * 2.0 - 1.0
     out = torch.zeros((n_out, total), device=dev, dtype=torch.float32)
     steps, warm = max(args.steps, 1), max(args.warmup, 2)
     for _ in range(warm):
@@ -220,6 +254,8 @@ def refbench(args):
         g.process_device(0, total, x.data_ptr(), total, out.data_ptr(), total)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("outputs", out, 1)])
     # parity of the stream call on a window, and the CPU path's rate on the same window
     w = 8 * n
     xs = x[:, :w].cpu().numpy()
@@ -351,7 +387,14 @@ def main():
                     help="instead of the render path, time the Objects gain producer (libearhip group I: point source "
                          "+ polar extent panners) on this many (object, metadata block) positions with random extents, "
                          "device pointers; prints its own JSON line with a CPU baseline (the oracle on a sample)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (the loudspeaker outputs; "
+                         "refbench: the interpolator's outputs; --producer: the direct and diffuse gains) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (beyond that a fixed seeded sample of the samples, or of the positions, "
+                         "and DIR/<name>_index.npy naming them)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.producer:
         return producer_bench(args)
     if args.config == "refbench":
@@ -385,6 +428,11 @@ def main():
         if rank == 0:
             print(f"bench.py: {world} ranks on {torch.cuda.device_count()} GPU(s): ranks share devices, exchange over gloo "
                   "(a functional check of the multi-rank path, not a measurement)", file=sys.stderr, flush=True)
+    if args.dump_outputs and world > 1 and not (backend == "nccl" and (args.shard == "objects" or
+                                                                       (args.shard == "time" and args.scaling == "strong"))):
+        # (elsewhere no buffer holds the whole of the last step's output once the step is over)
+        raise SystemExit("bench.py: --dump-outputs on several ranks needs the nccl backend and --shard objects, "
+                         "or --shard time with strong scaling")
     dev_index = local_rank % max(torch.cuda.device_count(), 1) if backend != "nccl" else local_rank
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
@@ -673,6 +721,16 @@ def main():
     time_every = max(1, min(args.kernel_timing_every, args.steps))
     timed_steps = len(range(0, args.steps, time_every))
     dt, pre_steps = wl.timed(args.steps, args.warmup, args.precondition_ms, timing_every=time_every)
+    if args.dump_outputs:
+        # the last timed step's output before the untimed passes below reuse its buffers: one rank's whole output, the bus
+        # gathered on the root, or (time-sharded) every rank's own blocks of the stream behind its lead block
+        if world == 1:
+            dump_outputs(args.dump_outputs, [("outputs", wl.outs[wl.last_slot][:N], 1)])
+        elif wl.time_sharded:
+            dump_outputs(args.dump_outputs, [(f"outputs_rank{rank}", wl.outs[wl.last_slot][:N, wl.lead * B:], 1)],
+                         DUMP_BYTES // world)
+        elif rank == gather_root:
+            dump_outputs(args.dump_outputs, [("outputs", torch.cat(wl.full[(args.steps - 1) % 2], dim=1)[:N], 1)])
     timing = wl.r.get_timing()
     plan = wl.r.last_plan()
     gain_kernel = plan["kernel"]

@@ -245,3 +245,19 @@ def test_default_line_carries_the_other_workloads():
         assert e["parity"]["pass"] and e["parity"]["same_plan_as_timed"] and e["parity"]["max_channel_rel_rms_vs_cpu"] <= 1e-6, (name, e)
     assert "k_gain_mix_hg" in sec["C4 moving"]["roofline"]["kernel"] and "k_gain_mix_p2" in sec["C4 adm"]["roofline"]["kernel"]
     assert "k_gain_mix_h2" in sec["C4 bursty"]["roofline"]["kernel"]
+
+
+def test_dump_outputs_writes_the_last_timed_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: the loudspeaker outputs of the last timed step as DIR/outputs.npy (float32, [channels][samples]); the
+    same arguments give the same inputs, so a second run writes the same outputs; --steps is the number of timed steps"""
+    import numpy as np
+    common = ["--blocks", "64", "--steps", "5", "--warmup", "1", "--cpu-blocks", "0", "--brief"]
+    got = []
+    for run in ("a", "b"):
+        line = run_bench(common + ["--dump-outputs", str(tmp_path / run)])
+        assert line["steps"] == 5 and line["parity"]["pass"]
+        out = np.load(tmp_path / run / "outputs.npy")
+        assert out.dtype == np.float32 and out.shape == (line["config"]["channels"], 64 * line["config"]["block"])
+        assert np.isfinite(out).all() and np.abs(out).max() > 0
+        got.append(out)
+    assert np.linalg.norm(got[0] - got[1]) <= 1e-6 * np.linalg.norm(got[1])

@@ -1,6 +1,7 @@
 """Evidence hygiene: what bench.py attaches to `roofline.traffic` must be traceable.  Every entry of
 profiles/traffic.json names a file that is tracked by git and holds, for the kernel the entry names, the counters the
 entry's bytes were computed from — with the values the entry quotes."""
+import fnmatch
 import json
 import os
 import re
@@ -11,9 +12,41 @@ NEEDED = ("TCC_EA0_RDREQ_128B_sum", "TCC_EA0_RDREQ_64B_sum", "TCC_EA0_RDREQ_32B_
           "TCC_EA0_WRREQ_sum")
 
 
+def _ignored(rel, patterns):
+    """whether .gitignore's patterns cover `rel` (or a directory above it): the subset of gitignore syntax the file uses
+    (comments, `dir/`, basename globs, root-anchored paths with a slash)"""
+    parts = rel.split("/")
+    for i in range(len(parts)):
+        is_dir = i < len(parts) - 1
+        for pat in patterns:
+            if pat.endswith("/") and not is_dir:
+                continue
+            p = pat.rstrip("/")
+            if "/" in p:
+                if fnmatch.fnmatchcase("/".join(parts[:i + 1]), p.lstrip("/")):
+                    return True
+            elif fnmatch.fnmatchcase(parts[i], p):
+                return True
+    return False
+
+
 def tracked_files():
-    out = subprocess.run(["git", "ls-files"], cwd=ROOT, stdout=subprocess.PIPE, text=True, check=True).stdout
-    return set(out.split())
+    """git's index when the tree is a git checkout; otherwise (an exported tree) every file present that .gitignore
+    does not cover: what a checkout of the commit holds besides build products"""
+    res = subprocess.run(["git", "ls-files"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+    if res.returncode == 0 and os.path.isdir(os.path.join(ROOT, ".git")):
+        return set(res.stdout.split())
+    patterns = [ln.strip() for ln in open(os.path.join(ROOT, ".gitignore"))
+                if ln.strip() and not ln.startswith(("#", "!"))]
+    found = set()
+    for d, dirs, files in os.walk(ROOT):
+        rel_d = os.path.relpath(d, ROOT)
+        dirs[:] = [x for x in dirs if x != ".git" and not _ignored(os.path.normpath(os.path.join(rel_d, x)) + "/x", patterns)]
+        for f in files:
+            rel = os.path.normpath(os.path.join(rel_d, f))
+            if not _ignored(rel, patterns):
+                found.add(rel)
+    return found
 
 
 def counters_of(path, kernel):
