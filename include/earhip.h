@@ -381,6 +381,74 @@ int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int 
                                        const char *normalization, float *out);
 
 /* ------------------------------------------------------------------------
+ * (I, DirectSpeakers) Gain vectors for channel-based content — replaces
+ * ear::GainCalculatorDirectSpeakers (include/ear/gain_calculators.hpp:18-35,
+ * src/direct_speakers/gain_calculator_direct_speakers.cpp:58-320).  Per channel, in libear's order:
+ *   1. audioPackFormatID without speakerLabels: EARHIP_ADM_ERROR (:247-250); a Cartesian position:
+ *      EARHIP_NOT_IMPLEMENTED (:253);
+ *   2. LFE or not: lowPass <= 200 Hz without highPass, or a nominal label LFE1 / LFE2; the warnings
+ *      FREQ_NOT_LFE and FREQ_SPEAKERLABEL_LFE_MISMATCH (:111-137);
+ *   3. nominal label: the capture of ^urn:itu:bs:2051:[0-9]+:speaker:(.*)$ or the label itself, replaced
+ *      by a substitution whose key is the ORIGINAL label: LFE -> LFE1, LFEL -> LFE1, LFER -> LFE2, plus
+ *      the caller's, which do not override these (:80-83, :139-150);
+ *   4. the first label naming a layout channel of the same LFE type gets gain 1 (:280-291);
+ *   5. a screenEdgeLock is EARHIP_NOT_IMPLEMENTED from here on, as in libear (:293,
+ *      src/common/screen_edge_lock.hpp:15-17); else the one channel of the same LFE type whose NOMINAL
+ *      position lies within the position's bounds (tolerance 1e-5), or the nearest of several when it is
+ *      more than 1e-5 nearer than the next (distances to the REAL positions) gets gain 1 (:152-242);
+ *   6. else an LFE channel goes to LFE1 (silence without one), anything else through the layout's point
+ *      source panner (group I, real positions), LFE columns zero (:304-319).
+ * A BATCH of channels per call; every channel that reaches the panner goes to the device in one launch.
+ *
+ * NOT carried: libear's ITU-R BS.2127 mapping rules for the common-definitions packs
+ * (src/direct_speakers/mapping_rules.cpp).  A channel whose audioPackFormatID has the common-definitions
+ * form AP_0001xxxx (after the checks and warnings of 1-2) is EARHIP_NOT_IMPLEMENTED, the message naming
+ * the pack; libear would apply a downmix rule there.  Any other pack follows 3-6, as in libear.
+ *
+ * layout: an ITU-R BS.2051 name (group H); gains: [n][n_channels] float for the full layout, LFE
+ * channels included.  ctx may be NULL: no device panner, and a channel that reaches step 6 as a
+ * non-LFE channel is EARHIP_INVALID_ARGUMENT.  from / to: n_subst extra substitutions.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_direct_speakers earhip_direct_speakers;
+
+/* one channel's DirectSpeakersTypeMetadata (include/ear/metadata.hpp:11-71).  An absent optional
+ * has its has_* flag 0 (bounds default to the position's value). */
+typedef struct earhip_ds_metadata {
+  int n_labels;
+  const char *const *labels; /* speakerLabels, in AXML order */
+  int cartesian;             /* nonzero: a CartesianSpeakerPosition (refused) */
+  double azimuth, elevation, distance;
+  int has_azimuth_min, has_azimuth_max, has_elevation_min, has_elevation_max, has_distance_min,
+      has_distance_max;
+  double azimuth_min, azimuth_max, elevation_min, elevation_max, distance_min, distance_max;
+  int screen_edge_lock_horizontal, screen_edge_lock_vertical; /* nonzero: set (refused, step 5) */
+  int has_low_pass, has_high_pass;                            /* channelFrequency */
+  double low_pass, high_pass;
+  const char *audio_pack_format_id; /* NULL: none */
+} earhip_ds_metadata;
+
+int earhip_direct_speakers_create(earhip_ctx *ctx, const char *layout, int n_subst,
+                                  const char *const *from, const char *const *to,
+                                  earhip_direct_speakers **out);
+/* loudspeakers at real positions (as earhip_panner_create_positions; distance 1): the bounds match
+ * the nominal positions, the nearest candidate and the panner use the real ones */
+int earhip_direct_speakers_create_positions(earhip_ctx *ctx, const char *layout, int n_channels,
+                                            const double *azimuth, const double *elevation,
+                                            int n_subst, const char *const *from,
+                                            const char *const *to, earhip_direct_speakers **out);
+int earhip_direct_speakers_destroy(earhip_direct_speakers *ds);
+int earhip_direct_speakers_num_channels(const earhip_direct_speakers *ds, int *n_channels);
+/* warnings_out (may be NULL): [n][2] Warning::Code values (include/ear/warnings.hpp) in the order
+ * libear raises them, 0 where none.  On an error the rows up to and including the failing channel
+ * hold what was raised before it; the message names the channel when n > 1. */
+int earhip_direct_speakers_calculate(earhip_direct_speakers *ds, size_t n,
+                                     const earhip_ds_metadata *md, float *gains,
+                                     int *warnings_out);
+/* the underlying point source panner's earhip_panner_missed after the last calculate (0 when
+ * no channel reached it or there is no panner) */
+int earhip_direct_speakers_missed(earhip_direct_speakers *ds, unsigned *count);
+
+/* ------------------------------------------------------------------------
  * (F) Composed Objects render block — the chain libear documents but does not
  * implement (docs/dsp.rst:40-71, include/ear/gain_calculators.hpp:45-56):
  *   per object: interpolated direct and diffuse gain vectors (a

@@ -487,6 +487,106 @@ class Panner:
             self.h = C.c_void_p()
 
 
+class DSMetadata(C.Structure):
+    """earhip_ds_metadata: one DirectSpeakers channel's metadata"""
+    _fields_ = [("n_labels", C.c_int), ("labels", C.POINTER(C.c_char_p)), ("cartesian", C.c_int),
+                ("azimuth", C.c_double), ("elevation", C.c_double), ("distance", C.c_double)]
+    _fields_ += [("has_" + k, C.c_int) for k in ("azimuth_min", "azimuth_max", "elevation_min", "elevation_max",
+                                                 "distance_min", "distance_max")]
+    _fields_ += [(k, C.c_double) for k in ("azimuth_min", "azimuth_max", "elevation_min", "elevation_max",
+                                           "distance_min", "distance_max")]
+    _fields_ += [("screen_edge_lock_horizontal", C.c_int), ("screen_edge_lock_vertical", C.c_int),
+                 ("has_low_pass", C.c_int), ("has_high_pass", C.c_int), ("low_pass", C.c_double),
+                 ("high_pass", C.c_double), ("audio_pack_format_id", C.c_char_p)]
+
+
+BOUNDS = ("azimuth_min", "azimuth_max", "elevation_min", "elevation_max", "distance_min", "distance_max")
+
+# Warning::Code values (libear_amd/host/ear/warnings.hpp)
+FREQ_SPEAKERLABEL_LFE_MISMATCH, FREQ_NOT_LFE = 1, 2
+
+
+class DirectSpeakers:
+    """(I, DirectSpeakers) gain vectors for channel-based content (ear::GainCalculatorDirectSpeakers), batched.
+
+    A channel's metadata is a dict with the keys of libear's DirectSpeakersTypeMetadata, all optional:
+    speakerLabels (list of str), azimuth / elevation / distance (polar position, default 0, 0, 1), azimuthMin ...
+    distanceMax (bounds), cartesian, screenEdgeLock ({"horizontal": ..., "vertical": ...}), lowPass / highPass
+    (channelFrequency), audioPackFormatID."""
+
+    _KEYS = {"azimuthMin": "azimuth_min", "azimuthMax": "azimuth_max", "elevationMin": "elevation_min",
+             "elevationMax": "elevation_max", "distanceMin": "distance_min", "distanceMax": "distance_max"}
+
+    def __init__(self, ctx, layout, substitutions=None, positions=None):
+        """ctx: a Context, or None (no device panner: a non-LFE channel that needs it is an InvalidArgument);
+        substitutions: {label: nominal label} on top of libear's defaults; positions: (azimuths, elevations) of
+        every channel of the full layout (the loudspeakers' real positions), None: nominal"""
+        subst = list((substitutions or {}).items())
+        frm = (C.c_char_p * max(len(subst), 1))(*[k.encode() for k, _ in subst])
+        to = (C.c_char_p * max(len(subst), 1))(*[v.encode() for _, v in subst])
+        self.h = C.c_void_p()
+        h = ctx.h if ctx is not None else None
+        if positions is None:
+            check(load().earhip_direct_speakers_create(h, layout.encode(), len(subst), frm, to, C.byref(self.h)))
+        else:
+            f64 = C.POINTER(C.c_double)
+            az, el = (np.ascontiguousarray(v, np.float64) for v in positions)
+            assert az.size == el.size
+            check(load().earhip_direct_speakers_create_positions(h, layout.encode(), int(az.size), _ptr(az, f64),
+                                                                 _ptr(el, f64), len(subst), frm, to, C.byref(self.h)))
+        n = C.c_int(0)
+        check(load().earhip_direct_speakers_num_channels(self.h, C.byref(n)))
+        self.n_out = n.value
+
+    @classmethod
+    def _struct(cls, m, keep):
+        s = DSMetadata()
+        labels = [lab.encode() for lab in m.get("speakerLabels", ())]
+        arr = (C.c_char_p * max(len(labels), 1))(*labels)
+        keep.append(arr)
+        s.n_labels, s.labels = len(labels), C.cast(arr, C.POINTER(C.c_char_p))
+        s.cartesian = int(bool(m.get("cartesian", False)))
+        s.azimuth, s.elevation, s.distance = m.get("azimuth", 0.0), m.get("elevation", 0.0), m.get("distance", 1.0)
+        for k, f in cls._KEYS.items():
+            if m.get(k) is not None:
+                setattr(s, "has_" + f, 1)
+                setattr(s, f, m[k])
+        sel = m.get("screenEdgeLock") or {}
+        s.screen_edge_lock_horizontal = int(sel.get("horizontal") is not None)
+        s.screen_edge_lock_vertical = int(sel.get("vertical") is not None)
+        if m.get("lowPass") is not None:
+            s.has_low_pass, s.low_pass = 1, m["lowPass"]
+        if m.get("highPass") is not None:
+            s.has_high_pass, s.high_pass = 1, m["highPass"]
+        pack = m.get("audioPackFormatID")
+        s.audio_pack_format_id = None if pack is None else pack.encode()
+        return s
+
+    def calculate(self, metadata):
+        """list of metadata dicts [n] -> (gains float32 [n][n_out], warnings int32 [n][2]: Warning::Code values in
+        the order libear raises them, 0 where none)"""
+        n = len(metadata)
+        keep = []
+        md = (DSMetadata * max(n, 1))(*[self._struct(m, keep) for m in metadata])
+        gains = np.zeros((n, self.n_out), np.float32)
+        warnings = np.zeros((n, 2), np.int32)
+        self.last_warnings = warnings
+        check(load().earhip_direct_speakers_calculate(self.h, C.c_size_t(n), md, _ptr(gains),
+                                                      _ptr(warnings, C.POINTER(C.c_int))))
+        return gains, warnings
+
+    def missed(self):
+        """channels of the last calculate that no region of the point source panner took"""
+        n = C.c_uint(0)
+        check(load().earhip_direct_speakers_missed(self.h, C.byref(n)))
+        return n.value
+
+    def close(self):
+        if self.h:
+            load().earhip_direct_speakers_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Comm:
     """(J) RCCL communicator of the multi-GPU exchange: one per rank, made from rank 0's 128-byte id"""
 

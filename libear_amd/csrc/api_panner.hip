@@ -640,8 +640,8 @@ static void build_extent_table(earhip_panner &pn) {
 
 // with_extent = false: the point source panner alone (the HOA design only pans points: no extent grid to pan,
 // upload and wait for on every decode matrix)
-static int panner_create(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth,
-                         const double *elevation, earhip_panner **out, bool with_extent) {
+int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth,
+                          const double *elevation, earhip_panner **out, bool with_extent) {
   return guarded([&] {
     require(ctx != nullptr && out != nullptr, "NULL argument");
     const LayoutEntry &L = layout_entry(layout);

@@ -192,3 +192,10 @@ struct earhip_ctx {
   earhip::DevBuf<float> dev_in, dev_out, dev_pts;
   void use() const { EARHIP_HIP(hipSetDevice(device)); }
 };
+
+namespace earhip {
+// the point source panner of a layout (api_panner.hip): earhip_panner_create_positions, and with_extent = false
+// leaves out the extent panner's point grid (for callers that only pan points: the HOA design, DirectSpeakers)
+int panner_create(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth, const double *elevation,
+                  earhip_panner **out, bool with_extent);
+}  // namespace earhip

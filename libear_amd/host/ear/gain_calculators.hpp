@@ -1,7 +1,9 @@
 // ear/gain_calculators.hpp — GainCalculatorObjects with libear's interface
 // (include/ear/gain_calculators.hpp:45-56) over the device batch panner (earhip group I), plus the batched
-// call a renderer wants: all metadata blocks of all objects in one launch.
+// call a renderer wants: all metadata blocks of all objects in one launch; GainCalculatorHOA and
+// GainCalculatorDirectSpeakers over the same panner.
 #pragma once
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -102,6 +104,93 @@ namespace ear {
 
    private:
     earhip_panner *h_ = nullptr;
+    std::vector<int> keep_;
+    size_t n_full_ = 0;
+  };
+
+  /// libear: include/ear/gain_calculators.hpp:18-35 (earhip group I, DirectSpeakers).  One difference: the ITU-R
+  /// BS.2127 mapping rules of the common-definitions packs are not carried, and a channel of such a pack
+  /// (audioPackFormatID AP_0001xxxx) throws not_implemented.
+  class GainCalculatorDirectSpeakers {
+   public:
+    /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels; additionalSubstitutions:
+    /// speakerLabel -> nominal label, on top of (never instead of) LFE -> LFE1, LFEL -> LFE1, LFER -> LFE2
+    explicit GainCalculatorDirectSpeakers(const Layout &layout,
+                                          std::map<std::string, std::string> additionalSubstitutions = {},
+                                          hip::Context &ctx = hip::default_context()) {
+      std::vector<double> az, el;
+      keep_ = detail::match_layout(layout, az, el);
+      n_full_ = az.size();
+      std::vector<const char *> from, to;
+      for (auto &kv : additionalSubstitutions) from.push_back(kv.first.c_str()), to.push_back(kv.second.c_str());
+      hip::check(earhip_direct_speakers_create_positions(ctx.get(), layout.name().c_str(), (int)n_full_, az.data(),
+                                                         el.data(), (int)from.size(), from.data(), to.data(), &h_));
+    }
+    ~GainCalculatorDirectSpeakers() { earhip_direct_speakers_destroy(h_); }
+    GainCalculatorDirectSpeakers(const GainCalculatorDirectSpeakers &) = delete;
+    GainCalculatorDirectSpeakers &operator=(const GainCalculatorDirectSpeakers &) = delete;
+
+    /// one channel's metadata -> its gains, which must have the layout's channel count (after the ADM check, as
+    /// in libear: src/direct_speakers/gain_calculator_direct_speakers.cpp:247-251)
+    template <typename T>
+    void calculate(const DirectSpeakersTypeMetadata &metadata, std::vector<T> &gains,
+                   const WarningCB &warning_cb = default_warning_cb) {
+      const bool adm_error_first = metadata.audioPackFormatID && metadata.speakerLabels.empty();
+      if (gains.size() != keep_.size() && !adm_error_first) throw invalid_argument("incorrect size for output vector");
+      std::vector<std::vector<T>> g;
+      calculate(std::vector<DirectSpeakersTypeMetadata>(1, metadata), g, warning_cb);
+      gains = g[0];
+    }
+    /// a batch of channels; the ones that need the point source panner go to the device in one launch.  The
+    /// warnings of each channel reach warning_cb in order (on an error: those raised up to it, then the throw).
+    template <typename T>
+    void calculate(const std::vector<DirectSpeakersTypeMetadata> &metadata, std::vector<std::vector<T>> &gains,
+                   const WarningCB &warning_cb = default_warning_cb) {
+      const size_t n = metadata.size();
+      std::vector<earhip_ds_metadata> md(n);
+      std::vector<std::vector<const char *>> labels(n);
+      for (size_t i = 0; i < n; i++) {
+        const DirectSpeakersTypeMetadata &m = metadata[i];
+        earhip_ds_metadata &c = md[i];
+        c = earhip_ds_metadata();
+        for (auto &l : m.speakerLabels) labels[i].push_back(l.c_str());
+        c.n_labels = (int)labels[i].size();
+        c.labels = labels[i].data();
+        c.cartesian = m.position.isCartesian;
+        const PolarSpeakerPosition &p = m.position.polar;
+        c.azimuth = p.azimuth, c.elevation = p.elevation, c.distance = p.distance;
+        c.has_azimuth_min = (bool)p.azimuthMin, c.azimuth_min = p.azimuthMin.value_or(0.0);
+        c.has_azimuth_max = (bool)p.azimuthMax, c.azimuth_max = p.azimuthMax.value_or(0.0);
+        c.has_elevation_min = (bool)p.elevationMin, c.elevation_min = p.elevationMin.value_or(0.0);
+        c.has_elevation_max = (bool)p.elevationMax, c.elevation_max = p.elevationMax.value_or(0.0);
+        c.has_distance_min = (bool)p.distanceMin, c.distance_min = p.distanceMin.value_or(0.0);
+        c.has_distance_max = (bool)p.distanceMax, c.distance_max = p.distanceMax.value_or(0.0);
+        c.screen_edge_lock_horizontal = (bool)p.screenEdgeLock.horizontal;
+        c.screen_edge_lock_vertical = (bool)p.screenEdgeLock.vertical;
+        c.has_low_pass = (bool)m.channelFrequency.lowPass, c.low_pass = m.channelFrequency.lowPass.value_or(0.0);
+        c.has_high_pass = (bool)m.channelFrequency.highPass, c.high_pass = m.channelFrequency.highPass.value_or(0.0);
+        c.audio_pack_format_id = m.audioPackFormatID ? m.audioPackFormatID.get().c_str() : nullptr;
+      }
+      std::vector<float> g(n * n_full_);
+      std::vector<int> warnings(2 * n, 0);
+      const int status = earhip_direct_speakers_calculate(h_, n, md.data(), g.data(), warnings.data());
+      const std::string error = status == EARHIP_OK ? std::string() : std::string(earhip_last_error());
+      for (int w : warnings) {
+        // (libear's messages: src/direct_speakers/gain_calculator_direct_speakers.cpp:118-120, :132-134)
+        if (w == (int)Warning::Code::FREQ_NOT_LFE)
+          warning_cb({Warning::Code::FREQ_NOT_LFE, "frequency indication present but does not indicate an LFE channel"});
+        else if (w == (int)Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH)
+          warning_cb({Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH,
+                      "LFE indication from frequency element does not match speakerLabel"});
+      }
+      hip::check(status, error);
+      gains.assign(n, std::vector<T>(keep_.size()));
+      for (size_t i = 0; i < n; i++)
+        for (size_t c = 0; c < keep_.size(); c++) gains[i][c] = (T)g[i * n_full_ + keep_[c]];
+    }
+
+   private:
+    earhip_direct_speakers *h_ = nullptr;
     std::vector<int> keep_;
     size_t n_full_ = 0;
   };
