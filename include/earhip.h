@@ -142,6 +142,10 @@ int earhip_debug_hg_prof(earhip_ctx *ctx, unsigned long long *out128);
  * row-major [n_in][n_out] (libear's Matrix point is vector<vector<float>>
  * indexed [in][out], gain_interpolator.hpp:247).  Writes out[o][range_start ..
  * range_end) for every output o; in and out must not alias.
+ * apply_interp evaluates ONE ramp, extrapolated outside [start, end) and
+ * ramping between equal points as libear's does, with libear's exact float
+ * arithmetic whatever the strict setting; its samples must lie less than 2^30
+ * from `start` (EARHIP_INVALID_ARGUMENT otherwise — libear has no such limit).
  * ---------------------------------------------------------------------- */
 int earhip_interp_apply_interp(earhip_ctx *ctx, int n_in, int n_out,
                                const float *const *in, float *const *out,

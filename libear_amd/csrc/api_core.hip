@@ -452,8 +452,11 @@ struct GainStage {
   void run_device(int64_t t_call, int nsamples, const float *in_dev, size_t in_stride,
                   float *out_dev, size_t out_stride) {
     curves.commit(ctx);
-    // 1 -> N policies have no accumulation: always use libear's exact arithmetic
-    const bool strict = ctx->strict || n_in == 1;
+    // 1 -> N policies have no accumulation: always use libear's exact arithmetic.  The policy entry points
+    // (force_ramp: one ramp per input, extrapolated outside its two points) run it as well: only the VALU kernel's
+    // segment descriptors express such a curve (describe_segment's policy mode); the matrix-core kernels' list builders
+    // computed something else outside [start, end) for 32 inputs and more.
+    const bool strict = ctx->strict || n_in == 1 || force_ramp;
     MixLaunch ml = plan_mix(ctx, curves.plan(), n_in, nsamples, strict, 32,
                             curves.aligned_tile(t_call), curves.ramp_share(), curves.gain_scale(), curves.point_density_all(),
                             curves.pair_waste(256), curves.pair_waste(512), curves.hinge_exact_share(in_stride, (size_t)nsamples), false,
@@ -915,13 +918,15 @@ int earhip_interp_apply_interp(earhip_ctx *ctx, int n_in, int n_out, const float
     // a two-point curve per input channel, evaluated as ONE ramp (also outside
     // [start, end) and between equal points, like a direct call of apply_interp,
     // gain_interpolator.hpp:147-169)
+    // (apply_interp ramps between equal points too, (1 - p) s + p s: the "equals the previous point" bit stays clear)
     const int64_t t[2] = {start, end};
+    const uint8_t ramp_bits[2] = {0, 0};
     std::vector<float> &rows = st->rows;
     rows.resize(2 * (size_t)n_out);
     for (int m = 0; m < n_in; m++) {
       std::memcpy(rows.data(), start_point + (size_t)m * n_out, sizeof(float) * n_out);
       std::memcpy(rows.data() + n_out, end_point + (size_t)m * n_out, sizeof(float) * n_out);
-      st->curves.set_object(m, 2, t, rows.data());
+      st->curves.set_object(m, 2, t, rows.data(), ramp_bits);
     }
     st->curves.commit(ctx);
     st->run_host(block_start + range_start, in, out, range_start, range_end);

@@ -559,9 +559,12 @@ __device__ __forceinline__ void record_mode(const GainMixParams &P, bool device_
   if (P.record) *P.record = (P.mode_word ? *P.mode_word : 0u) | (device_form ? 0u : 1u) | kModeRecorded;
 }
 
-// accumulate one segment piece of one object into acc
-template <int NOUT, int SPL, bool STRICT>
-__device__ __forceinline__ void accumulate_piece(float (&acc)[NOUT][SPL], const float (&xs)[SPL],
+// accumulate one segment piece of one object into acc; on[i]: sample i of this lane lies in the piece (its xs[i] is
+// zeroed otherwise).  STRICT && PARTIAL (a piece that covers part of the tile) leaves the other lanes' acc untouched:
+// libear never evaluates a segment outside its range, where a NaN or infinite gain — or a finite ramp extrapolated past
+// FLT_MAX — would make 0 * g = NaN.
+template <int NOUT, int SPL, bool STRICT, bool PARTIAL>
+__device__ __forceinline__ void accumulate_piece(float (&acc)[NOUT][SPL], const float (&xs)[SPL], const bool (&on)[SPL],
                                                  const SegDesc d, const float *__restrict__ rows,
                                                  int rowlen, int lane, int col0, int bus_cols) {
   const bool ramp = d.info & kSegRamp;
@@ -583,7 +586,8 @@ __device__ __forceinline__ void accumulate_piece(float (&acc)[NOUT][SPL], const 
 #pragma unroll
       for (int i = 0; i < SPL; i++) {
         const float g = cflat ? e : q[i] * s + p[i] * e;  // un-contracted (-ffp-contract=off)
-        acc[j][i] = acc[j][i] + xs[i] * g;
+        const float v = acc[j][i] + xs[i] * g;
+        acc[j][i] = !PARTIAL || on[i] ? v : acc[j][i];
       }
     }
   } else {
@@ -669,24 +673,33 @@ __global__ void __launch_bounds__(512) k_gain_mix(GainMixParams P) {
     int64_t cur = tile_t0;
     for (;;) {
       float xm[SPL];
+      bool on[SPL];
 #pragma unroll
-      for (int i = 0; i < SPL; i++) xm[i] = x[i];
+      for (int i = 0; i < SPL; i++) xm[i] = x[i], on[i] = true;
       int64_t seg_end = tile_t1;
       if (d.info & kSegMulti) {
         seg_end = tile_t0 + seg_r1(d.info);
         const int r0 = (int)(cur - tile_t0), r1 = seg_r1(d.info);
 #pragma unroll
-        for (int i = 0; i < SPL; i++)
-          xm[i] = (lane * SPL + i >= r0 && lane * SPL + i < r1) ? x[i] : 0.0f;
+        for (int i = 0; i < SPL; i++) {
+          on[i] = lane * SPL + i >= r0 && lane * SPL + i < r1;
+          xm[i] = on[i] ? x[i] : 0.0f;
+        }
       } else if (cur != tile_t0) {
         const int r0 = (int)(cur - tile_t0);
 #pragma unroll
-        for (int i = 0; i < SPL; i++) xm[i] = lane * SPL + i >= r0 ? x[i] : 0.0f;
+        for (int i = 0; i < SPL; i++) {
+          on[i] = lane * SPL + i >= r0;
+          xm[i] = on[i] ? x[i] : 0.0f;
+        }
       }
-      if (seg_end > cur)  // duplicate times make empty segments (steps)
-        accumulate_piece<NOUT, SPL, STRICT>(acc, xm, d,
-                                            P.ps.gain + (size_t)d.row * P.ps.row + col0,
-                                            P.ps.row, lane, col0, P.ps.bus_cols);
+      if (seg_end > cur) {  // duplicate times make empty segments (steps)
+        const float *rows = P.ps.gain + (size_t)d.row * P.ps.row + col0;
+        if (STRICT && ((d.info & kSegMulti) || cur != tile_t0))  // (wave-uniform)
+          accumulate_piece<NOUT, SPL, STRICT, true>(acc, xm, on, d, rows, P.ps.row, lane, col0, P.ps.bus_cols);
+        else
+          accumulate_piece<NOUT, SPL, STRICT, false>(acc, xm, on, d, rows, P.ps.row, lane, col0, P.ps.bus_cols);
+      }
       if (!(d.info & kSegMulti)) break;
       cur = seg_end;
       const int base = P.ps.off[m], n = P.ps.cnt[m];

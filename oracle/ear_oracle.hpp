@@ -15,9 +15,12 @@
 //   * FFT: checked bit-for-bit against the reference's vendored kissfft.hh,
 //     compiled in place into oracle/_ref (oracle/Makefile target `ref`), and
 //     against committed fixtures generated from it (tests/golden/).
-//   * GainInterpolator: reference header cannot be compiled here without a
-//     stand-in for its CMake-generated export header, so it is pinned by the
-//     reference tests' closed-form expectations (tests/gain_interpolator_tests.cpp).
+//   * GainInterpolator: checked bit-for-bit against the reference's own
+//     gain_interpolator.hpp, compiled in place into oracle/_ref with a stand-in
+//     for its CMake-generated export header (oracle/ref_interp_capi.cpp), and
+//     against committed fixtures generated from it (tests/golden/
+//     gain_interp_ref.npz); also by the reference tests' closed-form
+//     expectations (tests/gain_interpolator_tests.cpp).
 //   * BlockConvolver: pinned by the reference tests' brute-force convolution
 //     oracle and all 15 scenarios (tests/block_convolver_tests.cpp), abs 1e-6.
 //   * DelayBuffer / VariableBlockSizeAdapter: exact-shift properties (==).
@@ -778,6 +781,8 @@ class ObjectsRenderer {
       for (size_t i = 0; i < B_; i++) out[c][i] = dc[c][i] + dl[c][i];
     t_ += (SampleIndex)B_;
   }
+  // the sample index of the next block's first sample (earhip_render_reset's clock)
+  void set_time(SampleIndex t) { t_ = t; }
 
  private:
   std::vector<std::unique_ptr<block_convolver::BlockConvolver>> conv_;

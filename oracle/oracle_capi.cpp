@@ -92,6 +92,69 @@ int oracle_gain_interp(int kind, int n_in, int n_out, int npoints,
   });
 }
 
+// LinearInterp{Single,Vector,Matrix}::apply_interp (interp = 1) or ::apply_constant
+// (interp = 0, point = sp): in [n_in][stride], out [n_out][stride]; points
+// [n_in][n_out].  The signature of ref_interp_policy (oracle/ref_interp_capi.cpp).
+int oracle_interp_policy(int kind, int interp, int n_in, int n_out, const float *in,
+                         float *out, size_t stride, int64_t r0, int64_t r1,
+                         int64_t block_start, int64_t start, int64_t end,
+                         const float *sp, const float *ep) {
+  return guarded([&] {
+    auto ip = planar_c(in, n_in, stride, 0);
+    auto op = planar(out, n_out, stride, 0);
+    if (kind == 0) {
+      if (interp)
+        LinearInterpSingle::apply_interp(ip.data(), op.data(), r0, r1, block_start, start, end, sp[0], ep[0]);
+      else
+        LinearInterpSingle::apply_constant(ip.data(), op.data(), r0, r1, sp[0]);
+    } else if (kind == 1) {
+      const std::vector<float> a(sp, sp + n_out), b(ep, ep + n_out);
+      if (interp)
+        LinearInterpVector::apply_interp(ip.data(), op.data(), r0, r1, block_start, start, end, a, b);
+      else
+        LinearInterpVector::apply_constant(ip.data(), op.data(), r0, r1, a);
+    } else {
+      LinearInterpMatrix::Point a(n_in), b(n_in);
+      for (int m = 0; m < n_in; m++) {
+        a[m].assign(sp + (size_t)m * n_out, sp + (size_t)(m + 1) * n_out);
+        b[m].assign(ep + (size_t)m * n_out, ep + (size_t)(m + 1) * n_out);
+      }
+      if (interp)
+        LinearInterpMatrix::apply_interp(ip.data(), op.data(), r0, r1, block_start, start, end, a, b);
+      else
+        LinearInterpMatrix::apply_constant(ip.data(), op.data(), r0, r1, a);
+    }
+  });
+}
+
+// A GainInterpolator<LinearInterpMatrix> that lives across calls; the
+// signatures of ref_gi_* (oracle/ref_interp_capi.cpp)
+void *oracle_gi_create() { return new GainInterpolator<LinearInterpMatrix>(); }
+void oracle_gi_destroy(void *h) { delete static_cast<GainInterpolator<LinearInterpMatrix> *>(h); }
+int oracle_gi_set_points(void *h, int n_in, int n_out, int npoints, const int64_t *times,
+                         const float *values) {
+  return guarded([&] {
+    auto &gi = *static_cast<GainInterpolator<LinearInterpMatrix> *>(h);
+    const size_t psz = (size_t)n_in * n_out;
+    gi.interp_points.clear();
+    for (int p = 0; p < npoints; p++) {
+      LinearInterpMatrix::Point mat(n_in);
+      for (int m = 0; m < n_in; m++)
+        mat[m].assign(values + p * psz + (size_t)m * n_out, values + p * psz + (size_t)(m + 1) * n_out);
+      gi.interp_points.emplace_back((SampleIndex)times[p], std::move(mat));
+    }
+  });
+}
+int oracle_gi_process(void *h, int n_in, int n_out, int64_t block_start, size_t nsamples,
+                      const float *in, size_t in_stride, float *out, size_t out_stride) {
+  return guarded([&] {
+    auto ip = planar_c(in, n_in, in_stride, 0);
+    auto op = planar(out, n_out, out_stride, 0);
+    static_cast<GainInterpolator<LinearInterpMatrix> *>(h)->process((SampleIndex)block_start, nsamples,
+                                                                   ip.data(), op.data());
+  });
+}
+
 // ---- FFT -------------------------------------------------------------------
 int oracle_cfft_f32(size_t n, int inverse, const float *in, float *out) {
   return guarded([&] {
@@ -231,6 +294,7 @@ ObjectsRenderer *oracle_render_create(size_t n_obj, size_t n_out, size_t block,
   return new ObjectsRenderer(n_obj, n_out, block, f, delay);
 }
 void oracle_render_destroy(ObjectsRenderer *r) { delete r; }
+void oracle_render_set_time(ObjectsRenderer *r, int64_t t) { r->set_time((SampleIndex)t); }
 // bus: 0 direct, 1 diffuse; gains: [npoints][n_out]
 int oracle_render_set_points(ObjectsRenderer *r, size_t obj, int bus, int npoints,
                              const int64_t *times, const float *gains,

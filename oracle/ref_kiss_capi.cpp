@@ -4,9 +4,10 @@
 // check the oracle's FFT restatement bit-for-bit and to generate the golden
 // vectors under tests/golden/ (see tests/golden/make_golden.py).
 //
-// The rest of the reference's hot path cannot be compiled in this image:
-// every libear header reaches ear/export.hpp -> generated/export.hpp (a CMake
-// product), and the .cpp files need Eigen and Boost, which are absent.
+// The reference's GainInterpolator is header-only and is compiled as well
+// (oracle/ref_interp_capi.cpp, with a generated stand-in for the CMake product
+// generated/export.hpp).  The rest of its hot path (BlockConvolver, DelayBuffer,
+// the VBS adapter, the decorrelator design) needs Eigen or Boost, which are absent.
 #include <complex>
 #include <cstddef>
 

@@ -49,6 +49,123 @@ def load_ref():
     return C.CDLL(path)
 
 
+def load_ref_interp():
+    """The reference's own gain_interpolator.hpp compiled in place (oracle/_ref/libref_interp.so, oracle/ref_interp_capi.cpp);
+    None when absent."""
+    path = os.path.join(ODIR, "_ref", "libref_interp.so")
+    if not os.path.exists(path):
+        if os.path.exists("/root/reference/include/ear/dsp/gain_interpolator.hpp"):
+            _build()
+    if not os.path.exists(path):
+        return None
+    lib = C.CDLL(path)
+    lib.ref_interp_last_error.restype = C.c_char_p
+    lib.ref_gi_create.restype = C.c_void_p
+    lib.ref_objects_create.restype = C.c_void_p
+    return lib
+
+
+def _pfx(lib_):
+    """the shim (ref_*) and the oracle (oracle_*) export the policy and live-interpolator entry points alike"""
+    return "ref" if lib_ is not _lib else "oracle"
+
+
+def _ref_chk(ref, rc):
+    if rc != 0:
+        err = ref.ref_interp_last_error() if _pfx(ref) == "ref" else ref.oracle_last_error()
+        raise OracleError(rc, err.decode())
+
+
+def ref_gain_interp(ref, kind, times, values, x, call_sizes, t0=0):
+    """libear's GainInterpolator<LinearInterp{Single,Vector,Matrix}>: the signature of gain_interp"""
+    values = _f32(values)
+    npts, n_in, n_out = values.shape
+    x = _f32(x).reshape(n_in, -1)
+    total = x.shape[1]
+    assert sum(call_sizes) == total
+    out = np.zeros((n_out, total), np.float32)
+    t = np.ascontiguousarray(times, dtype=np.int64)
+    cs = np.ascontiguousarray(call_sizes, dtype=np.uintp)
+    _ref_chk(ref, ref.ref_gain_interp(KIND[kind], n_in, n_out, npts, ptr(t, i64p), ptr(values), C.c_int64(t0),
+                                      ptr(cs, szp), len(cs), ptr(x), ptr(out)))
+    return out
+
+
+def ref_policy(ref, kind, x, out, range_start, range_end, block_start=0, start=0, end=1, sp=None, ep=None):
+    """libear's LinearInterp*::apply_interp (sp and ep given) or ::apply_constant (point sp, ep None), in place on
+    out [n_out][n] from x [n_in][n]; points [n_in][n_out].  ref: load_ref_interp(), or lib() for the oracle's own."""
+    x = _f32(x)
+    assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.shape[1] == x.shape[1]
+    sp = _f32(sp)
+    ep_ = _f32(ep if ep is not None else sp)
+    fn = getattr(ref, _pfx(ref) + "_interp_policy")
+    _ref_chk(ref, fn(KIND[kind], int(ep is not None), x.shape[0], out.shape[0], ptr(x), ptr(out),
+                                        C.c_size_t(x.shape[1]), C.c_int64(range_start), C.c_int64(range_end),
+                                        C.c_int64(block_start), C.c_int64(start), C.c_int64(end), ptr(sp), ptr(ep_)))
+    return out
+
+
+class RefGainInterp:
+    """libear's GainInterpolator<LinearInterpMatrix>, living across calls (its search cache included); ref:
+    load_ref_interp(), or lib() for the oracle's restatement"""
+
+    def __init__(self, ref, n_in, n_out):
+        self.ref, self.n_in, self.n_out = ref, n_in, n_out
+        p = _pfx(ref)
+        self._set, self._process, self._destroy = (getattr(ref, f"{p}_gi_{f}") for f in ("set_points", "process",
+                                                                                       "destroy"))
+        create = getattr(ref, p + "_gi_create")
+        create.restype = C.c_void_p
+        self.h = C.c_void_p(create())
+
+    def set_points(self, times, values):
+        t = np.ascontiguousarray(times, dtype=np.int64)
+        v = _f32(values)
+        assert v.size == len(t) * self.n_in * self.n_out
+        _ref_chk(self.ref, self._set(self.h, self.n_in, self.n_out, len(t), ptr(t, i64p), ptr(v)))
+
+    def process(self, block_start, x):
+        x = _f32(x).reshape(self.n_in, -1)
+        n = x.shape[1]
+        out = np.zeros((self.n_out, n), np.float32)
+        _ref_chk(self.ref, self._process(self.h, self.n_in, self.n_out, C.c_int64(block_start),
+                                                   C.c_size_t(n), ptr(x), C.c_size_t(n), ptr(out), C.c_size_t(n)))
+        return out
+
+    def __del__(self):
+        try:
+            self._destroy(self.h)
+        except Exception:
+            pass
+
+
+class RefObjects:
+    """the objects gain stage on libear's interpolator: one GainInterpolator<LinearInterpVector> per object, outputs summed
+    into the bus in object order (the composition ObjectsRenderer's direct bus restates)"""
+
+    def __init__(self, ref, n_obj, n_out):
+        self.ref, self.M, self.N = ref, n_obj, n_out
+        self.h = C.c_void_p(ref.ref_objects_create(n_obj, n_out))
+
+    def set_points(self, obj, times, gains):
+        t = np.ascontiguousarray(times, dtype=np.int64)
+        g = _f32(gains).reshape(len(t), self.N)
+        _ref_chk(self.ref, self.ref.ref_objects_set_points(self.h, obj, len(t), ptr(t, i64p), ptr(g)))
+
+    def process(self, block_start, x):
+        x = _f32(x).reshape(self.M, -1)
+        out = np.zeros((self.N, x.shape[1]), np.float32)
+        _ref_chk(self.ref, self.ref.ref_objects_process(self.h, C.c_int64(block_start), C.c_size_t(x.shape[1]),
+                                                        ptr(x), ptr(out)))
+        return out
+
+    def __del__(self):
+        try:
+            self.ref.ref_objects_destroy(self.h)
+        except Exception:
+            pass
+
+
 class OracleError(Exception):
     def __init__(self, code, msg):
         super().__init__(msg)
@@ -249,6 +366,10 @@ class ObjectsRenderer:
         rc = self.lib.oracle_render_set_points(self.h, C.c_size_t(obj), bus, len(t), ptr(t, i64p), ptr(g),
                                                C.c_size_t(self.N))
         assert rc == 0
+
+    def set_time(self, sample_time):
+        """the sample index of the next block's first sample (the renderer's reset clock)"""
+        self.lib.oracle_render_set_time(self.h, C.c_int64(sample_time))
 
     def process(self, x):
         x = _f32(x).reshape(self.M, -1)

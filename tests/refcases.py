@@ -173,3 +173,15 @@ def is_approx(a, b, prec=1e-5):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return np.linalg.norm(a - b) <= prec * min(np.linalg.norm(a), np.linalg.norm(b))
+
+
+def interp_golden():
+    """(the generator module tests/golden/make_interp_golden.py — case definitions and readers —, its cases: the inputs
+    it builds, checked against the digests in tests/golden/gain_interp_ref.npz, with libear's outputs from that file)"""
+    import importlib.util
+    import os
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_interp_golden", os.path.join(here, "make_interp_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod, mod.load()

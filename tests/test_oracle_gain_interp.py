@@ -1,5 +1,7 @@
 """CPU oracle GainInterpolator vs the reference tests' expectations
 (reference tests/gain_interpolator_tests.cpp:58-257)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -111,3 +113,203 @@ def test_config1_one_object_to_0_5_0_vector_closed_form():
         got = _oracle.gain_interp("vector", times, vals, x, sizes)
         assert np.array_equal(got, want)
     assert not want[3].any()
+
+
+# ---- pinned to libear's own GainInterpolator -------------------------------------------------------------------------
+# (1) the committed fixture generated from it (tests/golden/make_interp_golden.py): always, so the suite checks the
+#     oracle against libear where the reference is absent; (2) live, against oracle/_ref/libref_interp.so
+#     (oracle/ref_interp_capi.cpp) where it was built: every fixture case, regeneration of the fixture, and a seeded
+#     fuzz of ragged curves.  All bit for bit (value equality; NaN equals NaN).
+from refcases import interp_golden  # noqa: E402
+
+GEN, GOLD = interp_golden()
+
+
+def same(a, b):
+    nan = np.issubdtype(a.dtype, np.floating)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=nan)
+
+
+def needs_ref():
+    ref = _oracle.load_ref_interp()
+    if ref is None:
+        pytest.skip("oracle/_ref/libref_interp.so not built (reference tree absent)")
+    return ref
+
+
+def policy_run(lib_, g, name):
+    m = GEN.meta(g, name)
+    out = np.zeros_like(g[name + ".want"])
+    return _oracle.ref_policy(lib_, m["kind"], g[name + ".x"], out, m["r0"], m["r1"], m["block_start"], m["start"],
+                              m["end"], g[name + ".sp"], g[name + ".ep"] if m["interp"] else None)
+
+
+def gi_run(lib_, g, name):
+    m = GEN.meta(g, name)
+    sets = GEN.gi_point_sets(g, name)
+    x = g[name + ".x"]
+    out = np.zeros_like(g[name + ".want"])
+    gi = _oracle.RefGainInterp(lib_, m["n_in"], m["n_out"])
+    ofs = 0
+    for bs, n, ps in g[name + ".calls"]:
+        if ps >= 0:
+            gi.set_points(*sets[ps])
+        if n:
+            out[:, ofs:ofs + n] = gi.process(int(bs), x[:, ofs:ofs + n])
+        ofs += int(n)
+    return out
+
+
+def render_oracle(g, name):
+    """the oracle's ObjectsRenderer, direct bus only (zero decorrelators, no delay: out == direct bus), clock at t0"""
+    m = GEN.meta(g, name)
+    o = _oracle.ObjectsRenderer(m["M"], m["N"], m["B"], np.zeros((m["N"], 1), np.float32), 0)
+    for i, (t, gains) in enumerate(GEN.render_curves(g, name)):
+        o.set_points(i, 0, t, gains)
+        o.set_points(i, 1, t[:1], np.zeros((1, m["N"]), np.float32))
+    o.set_time(m["t0"])
+    return o.process(g[name + ".x"])
+
+
+def render_ref(ref, g, name):
+    m = GEN.meta(g, name)
+    objs = _oracle.RefObjects(ref, m["M"], m["N"])
+    for i, (t, gains) in enumerate(GEN.render_curves(g, name)):
+        objs.set_points(i, t, gains)
+    x, B = g[name + ".x"], m["B"]
+    out = np.zeros_like(g[name + ".want"])
+    for b in range(m["nblocks"]):
+        out[:, b * B:(b + 1) * B] = objs.process(m["t0"] + b * B, x[:, b * B:(b + 1) * B])
+    return out
+
+
+@pytest.mark.parametrize("name", GEN.cases(GOLD, "pol"))
+def test_policy_matches_libear_fixture(name):
+    assert same(policy_run(_oracle.lib(), GOLD, name), GOLD[name + ".want"])
+
+
+@pytest.mark.parametrize("name", GEN.cases(GOLD, "gi"))
+def test_gain_interpolator_matches_libear_fixture(name):
+    assert same(gi_run(_oracle.lib(), GOLD, name), GOLD[name + ".want"])
+
+
+@pytest.mark.parametrize("name", GEN.cases(GOLD, "rn"))
+def test_objects_gain_stage_matches_libear_fixture(name):
+    assert same(render_oracle(GOLD, name), GOLD[name + ".want"])
+
+
+def test_fixture_covers_the_edges():
+    """the cases the fixture must hold (a regenerated fixture that lost some would pass the comparisons above)"""
+    names = set(GEN.cases(GOLD, "pol")) | set(GEN.cases(GOLD, "gi")) | set(GEN.cases(GOLD, "rn"))
+    for L in GEN.RAMPS:
+        assert any(n.startswith(f"rn.ramp{L}_") for n in names), L
+        assert any(n.startswith(f"pol.ramp{L}_") for n in names), L
+    for n_in in (1, 2, 3, 33, 64, 257):
+        for n_out in (1, 2, 7, 24, 64):
+            assert f"pol.shape_{n_in}x{n_out}_interp" in names and f"pol.shape_{n_in}x{n_out}_const" in names
+    blocks = {GEN.meta(GOLD, n)["B"] for n in GEN.cases(GOLD, "rn")}
+    objects = {GEN.meta(GOLD, n)["M"] for n in GEN.cases(GOLD, "rn")}
+    assert {16, 45, 64, 480, 512, 1000, 4096} <= blocks and {1, 33, 257} <= objects
+    times = {GEN.meta(GOLD, n)["t0"] for n in GEN.cases(GOLD, "rn")}
+    assert min(times) < -(1 << 40) + (1 << 32) and max(times) > (1 << 40) and any(-(1 << 20) < t < 0 for t in times)
+    sizes = {int(n) for c in GEN.cases(GOLD, "gi") for n in GOLD[c + ".calls"][:, 1]}
+    assert {0, 1, 2, 3} <= sizes
+    assert np.isnan(GOLD["rn.nan_gains.want"]).any() and np.isinf(GOLD["rn.overflow.want"]).any()
+    den = GOLD["rn.denormals.want"]
+    assert ((den != 0) & (np.abs(den) < np.finfo(np.float32).tiny)).any()
+
+
+def test_fixture_regenerates_identically():
+    ref = needs_ref()
+    fresh = GEN.generate(ref)
+    committed = np.load(os.path.join(os.path.dirname(os.path.abspath(GEN.__file__)), GEN.NAME))
+    assert sorted(fresh) == sorted(committed.files)
+    for k, v in fresh.items():
+        assert same(np.asarray(v), committed[k]), k
+
+
+def test_every_fixture_case_live_against_libear():
+    """the oracle and the compiled reference agree on every fixture case, computed afresh on both sides"""
+    ref = needs_ref()
+    o = _oracle.lib()
+    for name in GEN.cases(GOLD, "pol"):
+        assert same(policy_run(o, GOLD, name), policy_run(ref, GOLD, name)), name
+    for name in GEN.cases(GOLD, "gi"):
+        assert same(gi_run(o, GOLD, name), gi_run(ref, GOLD, name)), name
+    for name in GEN.cases(GOLD, "rn"):
+        assert same(render_oracle(GOLD, name), render_ref(ref, GOLD, name)), name
+
+
+def _fuzz_points(rng, npts, n_in, n_out, t_lo, t_hi):
+    t = np.sort(rng.integers(t_lo, t_hi, npts)).astype(np.int64)
+    rep = rng.random(npts) < 0.25  # steps: a time repeated
+    for k in range(1, npts):
+        if rep[k]:
+            t[k] = t[k - 1]
+    v = rng.uniform(-1, 1, (npts, n_in, n_out)).astype(np.float32)
+    for k in range(1, npts):
+        r = rng.random()
+        if r < 0.2:
+            v[k] = v[k - 1]  # bit-equal neighbours
+        elif r < 0.25:
+            v[k] = -v[k - 1] * 0.0  # zeros of the other sign than the previous point's
+            v[k - 1] = 0.0
+        elif r < 0.28:
+            v[k] = np.nan
+    return t, v
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_fuzz_ragged_curves_against_libear(seed):
+    ref = needs_ref()
+    rng = np.random.default_rng(9000 + seed)
+    kind = ("single", "vector", "matrix")[seed % 3]
+    n_in = 1 if kind != "matrix" else int(rng.integers(1, 6))
+    n_out = 1 if kind == "single" else int(rng.integers(1, 9))
+    base = int(rng.choice([0, -700, 1 << 40, -(1 << 40), 123456789]))
+    t, v = _fuzz_points(rng, int(rng.integers(1, 30)), n_in, n_out, base - 100, base + 900)
+    sizes = [int(s) for s in rng.choice([0, 1, 2, 3, 17, 64, 129], int(rng.integers(1, 14)))]
+    total = sum(sizes)
+    x = rng.uniform(-1, 1, (n_in, total)).astype(np.float32)
+    t0 = base + int(rng.integers(-200, 200))
+    got = _oracle.gain_interp(kind, t, v, x, sizes, t0=t0)
+    assert same(got, _oracle.ref_gain_interp(ref, kind, t, v, x, sizes, t0=t0))
+    # a live interpolator whose points change between calls, against libear's (its search cache included)
+    t2, v2 = _fuzz_points(rng, int(rng.integers(1, 30)), n_in, n_out, base - 100, base + 900)
+    a, b = _oracle.RefGainInterp(_oracle.lib(), n_in, n_out), _oracle.RefGainInterp(ref, n_in, n_out)
+    for gi in (a, b):
+        gi.set_points(t, v)
+    ofs, starts = 0, [t0 + int(s) for s in rng.integers(-300, 900, len(sizes))]
+    for k, (n, bs) in enumerate(zip(sizes, starts)):
+        if k == len(sizes) // 2:
+            for gi in (a, b):
+                gi.set_points(t2, v2)
+        xs = x[:, ofs:ofs + n]
+        assert same(a.process(bs, xs), b.process(bs, xs)), k
+        ofs += n
+    # the objects gain stage
+    M, N, B, nblocks = int(rng.integers(1, 12)), int(rng.integers(1, 9)), int(rng.choice([16, 45, 64])), 4
+    objs = _oracle.RefObjects(ref, M, N)
+    o = _oracle.ObjectsRenderer(M, N, B, np.zeros((N, 1), np.float32), 0)
+    for i in range(M):
+        ti, vi = _fuzz_points(rng, int(rng.integers(1, 12)), 1, N, base - 50, base + B * nblocks + 50)
+        objs.set_points(i, ti, vi[:, 0])
+        o.set_points(i, 0, ti, vi[:, 0])
+        o.set_points(i, 1, ti[:1], np.zeros((1, N), np.float32))
+    xr = rng.uniform(-1, 1, (M, B * nblocks)).astype(np.float32)
+    o.set_time(base)
+    want = np.concatenate([objs.process(base + k * B, xr[:, k * B:(k + 1) * B]) for k in range(nblocks)], axis=1)
+    assert same(o.process(xr), want)
+
+
+def test_fixture_refuses_inputs_it_was_not_made_from(tmp_path):
+    """the fixture holds libear's outputs and the digests of the inputs behind them; inputs built differently (another
+    generator, another random stream) must stop the tests, not be compared with outputs of other inputs"""
+    import json
+    committed = np.load(os.path.join(os.path.dirname(os.path.abspath(GEN.__file__)), GEN.NAME))
+    index = json.loads(str(committed["index"]))
+    index[len(index) // 2]["inputs"] = "0" * 64
+    path = tmp_path / "tampered.npz"
+    np.savez_compressed(path, index=np.array(json.dumps(index)), want=committed["want"])
+    with pytest.raises(AssertionError, match="inputs differ"):
+        GEN.load(str(path))
