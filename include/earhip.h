@@ -453,6 +453,63 @@ int earhip_direct_speakers_calculate(earhip_direct_speakers *ds, size_t n,
 int earhip_direct_speakers_missed(earhip_direct_speakers *ds, unsigned *count);
 
 /* ------------------------------------------------------------------------
+ * (K) Conversion of Objects metadata between polar and Cartesian — replaces ear::conversion
+ * (include/ear/conversion.hpp:1-83, src/conversion.cpp:14-281): ITU-R BS.2127 section 10, the
+ * mapping of positions through five azimuth sectors (mapping points 0, -30, -110, 110, 30 degrees;
+ * elevations through el_top 30 / el_top_tilde 45) and of extents through the source's local
+ * coordinate system, in double precision with libear's arithmetic and operation order.
+ * The arrays are SoA, one per component, n elements each.  Positions are (x, y, z) or (azimuth,
+ * elevation, distance) in degrees (ADM convention).  width / height / depth: the input extents
+ * (degrees, degrees, distance units when polar; sizes when Cartesian), each may be NULL (0).
+ * width_out / height_out / depth_out: all NULL for the point forms (pointCartToPolar,
+ * pointPolarToCart), else all given (extentCartToPolar, extentPolarToCart).  An output may alias
+ * the input of the SAME component (in place: azimuth over x, ..., width_out over width), so that
+ * toPolar can run in place on the arrays earhip_panner_calculate_extent_device then reads.
+ * Per element, as in libear:
+ *   - no sector found (a NaN azimuth or coordinate): EARHIP_INTERNAL_ERROR (libear throws
+ *     internal_error "could not find sector", conversion.cpp:86-92);
+ *   - the sector position p outside [-1e-6, 1 + 1e-6]: EARHIP_INTERNAL_ERROR (libear's ear_assert,
+ *     :143);
+ *   - inputs for which libear returns NaN (Cartesian infinities, Cartesian extents whose sizes
+ *     exceed 1, ...): EARHIP_OK, the NaN passed through.
+ * ONE DIFFERENCE from libear: libear reduces angles with while loops that add or subtract 360
+ * (src/common/geom.hpp:31-39, geom.cpp:7-28), which never end for an infinite azimuth and in
+ * practice not for a huge one.  Here the reduction is an exact fmod followed by at most two
+ * steps of 360: the same value wherever libear's loops end.  A polar azimuth that is infinite
+ * or beyond +-2^40 degrees is EARHIP_INVALID_ARGUMENT; libear does not return at all.
+ *
+ * The host forms are computed on the calling thread with the same code as the device kernel,
+ * need no context and no device, and are the counterparts of libear's free functions, which take
+ * no device either.  They are a deliberate CPU computation, not a fall-back of a device path.  On
+ * the first failing element they return its code, and earhip_last_error() names its index and
+ * the reason; the elements before it are written, it and those after it are not.
+ * The _device forms take device pointers (device-reachable host memory included), run one
+ * thread per element on the context's stream and do not synchronise; they never compute on the
+ * CPU.  status: [n] per-element codes (the host form's code of that element), may be NULL.  A
+ * failed element's outputs are NaN.  n < 2^31.
+ * ---------------------------------------------------------------------- */
+int earhip_conversion_to_polar(size_t n, const double *x, const double *y, const double *z,
+                               const double *width, const double *height, const double *depth,
+                               double *azimuth, double *elevation, double *distance,
+                               double *width_out, double *height_out, double *depth_out);
+int earhip_conversion_to_cartesian(size_t n, const double *azimuth, const double *elevation,
+                                   const double *distance, const double *width,
+                                   const double *height, const double *depth, double *x, double *y,
+                                   double *z, double *width_out, double *height_out,
+                                   double *depth_out);
+int earhip_conversion_to_polar_device(earhip_ctx *ctx, size_t n, const double *x, const double *y,
+                                      const double *z, const double *width, const double *height,
+                                      const double *depth, double *azimuth, double *elevation,
+                                      double *distance, double *width_out, double *height_out,
+                                      double *depth_out, int *status);
+int earhip_conversion_to_cartesian_device(earhip_ctx *ctx, size_t n, const double *azimuth,
+                                          const double *elevation, const double *distance,
+                                          const double *width, const double *height,
+                                          const double *depth, double *x, double *y, double *z,
+                                          double *width_out, double *height_out, double *depth_out,
+                                          int *status);
+
+/* ------------------------------------------------------------------------
  * (F) Composed Objects render block — the chain libear documents but does not
  * implement (docs/dsp.rst:40-71, include/ear/gain_calculators.hpp:45-56):
  *   per object: interpolated direct and diffuse gain vectors (a

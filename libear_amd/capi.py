@@ -587,6 +587,79 @@ class DirectSpeakers:
             self.h = C.c_void_p()
 
 
+# (K) conversion of Objects metadata between polar and Cartesian (ear::conversion)
+
+def _conv_host(fn, pos, extent):
+    f64 = C.POINTER(C.c_double)
+    pos = [np.ascontiguousarray(np.atleast_1d(v), np.float64) for v in pos]
+    n = pos[0].size
+    assert all(v.size == n for v in pos), "the position arrays must have one size"
+    ext_in = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,)))
+              for v in (extent if extent is not None else (None, None, None))]
+    out = [np.empty(n, np.float64) for _ in range(3)]
+    ext_out = [np.empty(n, np.float64) for _ in range(3)] if extent is not None else [None] * 3
+
+    def opt(v):
+        return None if v is None else _ptr(v, f64)
+    check(fn(C.c_size_t(n), *[_ptr(v, f64) for v in pos], *[opt(v) for v in ext_in], *[_ptr(v, f64) for v in out],
+             *[opt(v) for v in ext_out]))
+    return tuple(out) if extent is None else (tuple(out), tuple(ext_out))
+
+
+def to_polar(x, y, z, width=None, height=None, depth=None, extent=None):
+    """Cartesian -> polar on the calling thread (libear's pointCartToPolar / extentCartToPolar; no device needed).
+    Arrays [n] -> (azimuth, elevation, distance); with extents (extent=True, or any of width / height / depth given;
+    a missing one is 0) -> ((azimuth, elevation, distance), (width, height, depth)).  Raises on the first failing
+    element, the message naming its index."""
+    if extent is None:
+        extent = width is not None or height is not None or depth is not None
+    return _conv_host(load().earhip_conversion_to_polar, (x, y, z), (width, height, depth) if extent else None)
+
+
+def to_cartesian(azimuth, elevation, distance, width=None, height=None, depth=None, extent=None):
+    """polar -> Cartesian on the calling thread (pointPolarToCart / extentPolarToCart), as to_polar"""
+    if extent is None:
+        extent = width is not None or height is not None or depth is not None
+    return _conv_host(load().earhip_conversion_to_cartesian, (azimuth, elevation, distance),
+                      (width, height, depth) if extent else None)
+
+
+def _dev_ptr(a, n, dtype_name):
+    """a device address: an int, None (absent), or a tensor on the device with n elements of the named dtype"""
+    if a is None or isinstance(a, int):
+        return None if a is None else C.c_void_p(a)
+    assert a.is_cuda and a.is_contiguous(), "device tensors must be contiguous and on the GPU"
+    assert str(a.dtype) == "torch." + dtype_name and a.numel() >= n, (a.dtype, a.numel(), n)
+    return C.c_void_p(a.data_ptr())
+
+
+def _conv_device(fn, ctx, n, pos, extent, out, ext_out, status):
+    ext = extent if extent is not None else (None, None, None)
+    eo = ext_out if ext_out is not None else (None, None, None)
+    args = [_dev_ptr(v, n, "float64") for v in (*pos, *ext, *out, *eo)]
+    check(fn(ctx.h, C.c_size_t(n), *args, _dev_ptr(status, n, "int32")))
+
+
+def to_polar_device(ctx, n, x, y, z, azimuth, elevation, distance, width=None, height=None, depth=None,
+                    width_out=None, height_out=None, depth_out=None, status=None):
+    """Cartesian -> polar on the device: float64 tensors (or device addresses) of n elements, status an int32
+    tensor [n] of per-element codes (may be None).  Enqueues on the context's stream and does not synchronise.
+    An output may be the input tensor of the same component (in place)."""
+    ext_out = None if width_out is None and height_out is None and depth_out is None else (width_out, height_out,
+                                                                                          depth_out)
+    _conv_device(load().earhip_conversion_to_polar_device, ctx, n, (x, y, z), (width, height, depth),
+                 (azimuth, elevation, distance), ext_out, status)
+
+
+def to_cartesian_device(ctx, n, azimuth, elevation, distance, x, y, z, width=None, height=None, depth=None,
+                        width_out=None, height_out=None, depth_out=None, status=None):
+    """polar -> Cartesian on the device, as to_polar_device"""
+    ext_out = None if width_out is None and height_out is None and depth_out is None else (width_out, height_out,
+                                                                                          depth_out)
+    _conv_device(load().earhip_conversion_to_cartesian_device, ctx, n, (azimuth, elevation, distance),
+                 (width, height, depth), (x, y, z), ext_out, status)
+
+
 class Comm:
     """(J) RCCL communicator of the multi-GPU exchange: one per rank, made from rank 0's 128-byte id"""
 
