@@ -577,6 +577,55 @@ int earhip_render_process_device(earhip_render *r, size_t nblocks,
  * last-call queries describe the last chunk. */
 int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *in,
                           float *const *out);
+/* Interleaved PCM frames in — the way BW64 / WAV programmes store them — converted on the DEVICE: the bus carries the
+ * packed samples (2 bytes per sample for s16, 3 for s24) instead of 4-byte floats, and the caller has no deinterleave
+ * or conversion pass of its own.
+ *
+ * frames: nblocks * block_size frames of `frame_channels` interleaved little-endian samples; a frame is
+ * frame_channels * sample size bytes, no padding (s24: 3 bytes a sample, frames may start at any byte).  The renderer's
+ * n_objects inputs are channels [first_channel, first_channel + n_objects) of each frame: one renderer of several
+ * sharing a frame buffer (a file whose tracks feed several renderers, a rank of a multi-GPU render taking its shard).
+ * Conversion to float, exactly (a caller can reproduce it bit for bit):
+ *   EARHIP_PCM_S16: (float)x * 2^-15
+ *   EARHIP_PCM_S24: 3 bytes, little-endian, sign-extended from bit 23: (float)x * 2^-23
+ *   EARHIP_PCM_S32: (float)x rounded to nearest even, then * 2^-31
+ *   EARHIP_PCM_F32: the bits as given (NaN payloads and denormals included)
+ * out_interleaved == 0: out = n_out planar float rows, as earhip_render_process; != 0: out[0] is [frames][n_out]
+ * interleaved float32 (one contiguous transfer back).
+ * The result is bit-identical to earhip_render_process on the converted planar rows held in the same kind of memory
+ * (pageable, or earhip_host_alloc / _register): both take their chunk plan — short call or pipeline, chunk boundaries —
+ * from the same function of the FLOAT-EQUIVALENT size of the call (n_objects * frames * 4 bytes; 16 MB and more: a
+ * pipeline).  A long call runs the pipeline of earhip_render_process with a time chunk = one contiguous byte range of
+ * `frames`: staged into pinned memory by the staging threads (pageable frames) or copied by DMA from the caller's
+ * buffer (device-reachable frames); the packed bytes go H2D, and a conversion kernel writes the chunk's planar rows
+ * on the device before the chunk's render.
+ * Memory, made at the first call of this form and kept (grown by a later call of wider frames): pinned staging of
+ * max_blocks * block_size * frame_channels * sample size bytes (pageable frames only), the same on the device, and
+ * n_out * max_blocks * block_size floats on the device for interleaved outputs; with the staging of earhip_render_process.
+ * EARHIP_INVALID_ARGUMENT, with nothing written to out: an unknown format, first_channel < 0,
+ * first_channel + n_objects > frame_channels, a NULL pointer (frames, out, a row of out), nblocks > max_blocks, frames
+ * of s16 / s32 / f32 not aligned to the sample size.  (A device error in the middle of a long call leaves in out the
+ * chunks that had come back before it, and nothing else.) */
+typedef enum {
+  EARHIP_PCM_S16 = 1,
+  EARHIP_PCM_S24 = 2,
+  EARHIP_PCM_S32 = 3,
+  EARHIP_PCM_F32 = 4
+} earhip_pcm_format;
+int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *frames,
+                                 earhip_pcm_format fmt, int frame_channels, int first_channel,
+                                 float *const *out, int out_interleaved);
+/* The same from device memory (device-reachable host memory included: the conversion kernel reads it where it is) to
+ * device memory: out_interleaved == 0: out_dev [n_out][out_stride] (out_stride >= nblocks * block_size);
+ * != 0: out_dev [frames][out_stride] (out_stride >= n_out floats between frames).  Bit-identical to
+ * earhip_render_process_device on the converted rows with in_stride = nblocks * block_size.  The renderer keeps its own
+ * device buffers for the converted rows (n_objects * max_blocks * block_size floats) and, for interleaved outputs, the
+ * planar ones (n_out * ...), made at the first call.  The conversion reads the input from the device's memory once more
+ * than float rows would be read: in HBM this form moves more bytes than earhip_render_process_device.
+ * Errors as earhip_render_process_frames.  Enqueues on the context's stream; does not synchronise. */
+int earhip_render_process_frames_device(earhip_render *r, size_t nblocks, const void *frames_dev,
+                                        earhip_pcm_format fmt, int frame_channels, int first_channel,
+                                        float *out_dev, size_t out_stride, int out_interleaved);
 /* Kernel timing (HIP events on the context's stream around each launch).
  * enable != 0 starts collecting and zeroes the counters; enable = n > 1 times
  * every n-th process call only, starting with the next one (each timed call

@@ -149,16 +149,19 @@ class Context:
         return ms[0], ms[1]
 
     # --- host memory the device reaches directly (earhip_host_alloc / _register / _release)
-    def pinned_array(self, shape):
-        """float32 array in pinned, device-reachable host memory (C-contiguous: the rows of a [channels][samples]
-        array are evenly spaced channel buffers).  Valid until close() or release(array)."""
+    def pinned_array(self, shape, dtype=np.float32):
+        """array (float32 unless dtype says otherwise: int16 / int32 / uint8 for PCM frames) in pinned, device-reachable host
+        memory (C-contiguous: the rows of a [channels][samples] array are evenly spaced channel buffers).  Valid until close() or
+        release(array)."""
         shape = tuple(int(v) for v in np.atleast_1d(shape))
+        dtype = np.dtype(dtype)
         count = int(np.prod(shape))
         p = C.c_void_p()
-        check(load().earhip_host_alloc(self.h, C.c_size_t(4 * max(count, 1)), C.byref(p)))
-        buf = (C.c_float * max(count, 1)).from_address(p.value)
-        a = np.frombuffer(buf, dtype=np.float32, count=count).reshape(shape)
-        a[...] = 0.0
+        nbytes = dtype.itemsize * max(count, 1)
+        check(load().earhip_host_alloc(self.h, C.c_size_t(nbytes), C.byref(p)))
+        buf = (C.c_char * nbytes).from_address(p.value)
+        a = np.frombuffer(buf, dtype=dtype, count=count).reshape(shape)
+        a[...] = 0
         return a
 
     def register(self, a):
@@ -740,6 +743,20 @@ def hoa_decode_matrix(ctx, layout, orders, degrees, normalization="SN3D", positi
     return out[:, :len(o)]
 
 
+PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4
+_PCM = {"s16": (PCM_S16, np.int16, 1), "s24": (PCM_S24, np.uint8, 3), "s32": (PCM_S32, np.int32, 1),
+        "f32": (PCM_F32, np.float32, 1)}
+_PCM_BY_CODE = {v[0]: k for k, v in _PCM.items()}
+
+
+def pcm_format(fmt):
+    """(code, numpy dtype, array columns per channel) of a PCM format given as 's16' / 's24' / 's32' / 'f32' or its code"""
+    name = _PCM_BY_CODE.get(fmt, fmt)
+    if name not in _PCM:
+        raise ValueError(f"unknown PCM format {fmt!r}")
+    return _PCM[name]
+
+
 class Renderer:
     """(F) composed Objects render block."""
 
@@ -795,6 +812,43 @@ class Renderer:
         check(load().earhip_render_process_device(self.h, C.c_size_t(nblocks), C.c_void_p(in_ptr),
                                                   C.c_size_t(in_stride), C.c_void_p(out_ptr),
                                                   C.c_size_t(out_stride)))
+
+    def _frames_shape(self, x, fmt):
+        code, dtype, cols = pcm_format(fmt)
+        assert x.dtype == dtype and x.ndim == 2 and x.flags["C_CONTIGUOUS"], (x.dtype, dtype, x.shape)
+        assert x.shape[1] % cols == 0
+        frames, channels = x.shape[0], x.shape[1] // cols
+        nblocks = frames // self.B
+        assert nblocks * self.B == frames, "frames must be whole blocks"
+        return code, nblocks, channels
+
+    def process_frames(self, x, fmt, first_channel=0, interleaved_out=False):
+        """x [frames][C] interleaved PCM (int16 's16', int32 's32', float32 'f32'; uint8 [frames][3 C] 's24'), whole blocks;
+        the renderer's inputs are channels [first_channel, first_channel + n_objects) -> [N][frames] float32, or [frames][N] with
+        interleaved_out (include/earhip.h: earhip_render_process_frames)."""
+        x = np.ascontiguousarray(x)
+        frames = x.shape[0]
+        out = np.empty((frames, self.N) if interleaved_out else (self.N, frames), np.float32)
+        return self.process_frames_into(x, out, fmt, first_channel, interleaved_out)
+
+    def process_frames_into(self, x, out, fmt, first_channel=0, interleaved_out=False):
+        """the same with the caller's own arrays, used as they are (Context.pinned_array: DMA, no staging copies)"""
+        code, nblocks, channels = self._frames_shape(x, fmt)
+        frames = nblocks * self.B
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"]
+        assert out.shape == ((frames, self.N) if interleaved_out else (self.N, frames)), out.shape
+        ptrs = (f32p * 1)(_ptr(out)) if interleaved_out else _chan_ptrs(out)
+        check(load().earhip_render_process_frames(self.h, C.c_size_t(nblocks), C.c_void_p(x.ctypes.data), C.c_int(code),
+                                                  C.c_int(channels), C.c_int(first_channel), ptrs, int(bool(interleaved_out))))
+        return out
+
+    def process_frames_device(self, nblocks, frames_ptr, fmt, frame_channels, first_channel, out_ptr, out_stride,
+                              interleaved_out=False):
+        """device pointers (e.g. torch tensors' data_ptr()); enqueues on the context's stream"""
+        code = pcm_format(fmt)[0] if isinstance(fmt, str) else int(fmt)
+        check(load().earhip_render_process_frames_device(self.h, C.c_size_t(nblocks), C.c_void_p(frames_ptr), C.c_int(code),
+                                                         C.c_int(frame_channels), C.c_int(first_channel), C.c_void_p(out_ptr),
+                                                         C.c_size_t(out_stride), int(bool(interleaved_out))))
 
     def enable_timing(self, on=True):
         """True / 1: time the kernels of every process call; n > 1: of every n-th call; False: stop"""

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "curves.h"
 #include "host_gather.h"
+#include "pcm_kernels.h"
 #include "fft_kernels.h"
 #include "render_kernels.h"
 
@@ -115,9 +116,11 @@ static int wave_run_len(int T, int N, int num_cus) {
 // neither creates threads nor allocates.  A long call is cut into TIME chunks (a few blocks each: ~8 MB of inputs); a job =
 // gather every channel's samples of chunk g into the pinned buffer, chunk-major ([chunk][channel][samples of the chunk]: a
 // chunk is one linear transfer), thread t taking every nthreads-th channel; done[g] counts the threads that have finished
-// chunk g (the caller starts that chunk's transfer then, while the threads gather the next one).
+// chunk g (the caller starts that chunk's transfer then, while the threads gather the next one).  The contiguous-range job
+// (submit_range: interleaved PCM frames, earhip_render_process_frames) copies chunk g's byte range of the caller's buffer to the
+// same offset of the pinned buffer instead, thread t taking its slice of the range (range_slice).
 struct GatherPool {
-  static constexpr int kMaxGroups = 64;
+  static constexpr int kMaxGroups = HostChunkPlan::kMaxChunks;
   NumaMap numa;
   bool streaming = true;              // (option HOST_NT, read when a job is submitted)
   int job_node = -1;                  // the node this job's rows live on (-1: run anywhere)
@@ -134,6 +137,9 @@ struct GatherPool {
   size_t n = 0;                      // samples per channel in the call
   size_t cstart[kMaxGroups + 1] = {0};  // chunk g = samples [cstart[g], cstart[g + 1]) of every channel
   int M = 0, groups = 0;
+  const unsigned char *src_bytes = nullptr;  // contiguous-range job: source and destination of chunk g = bytes
+  unsigned char *dst_bytes = nullptr;        // [cstart[g] * unit, cstart[g + 1] * unit) (src_bytes NULL: a row job)
+  size_t unit = 0;
   std::atomic<int> done[kMaxGroups];
   int nthreads() const { return (int)threads.size(); }
   size_t group_len(int g) const { return cstart[g + 1] - cstart[g]; }
@@ -163,7 +169,18 @@ struct GatherPool {
           for (int g = 0; g < groups; g++) {
             const size_t len = group_len(g), at = cstart[g];
             float *base = dst + (size_t)M * at;
-            if (streaming) {
+            if (src_bytes) {
+              size_t lo, hi;
+              range_slice(len * unit, t, nt, &lo, &hi);
+              const size_t o = at * unit + lo;
+              if (hi > lo) {
+                if (streaming) stream_copy_bytes(dst_bytes + o, src_bytes + o, hi - lo);
+                else std::memcpy(dst_bytes + o, src_bytes + o, hi - lo);
+              }
+#if defined(__x86_64__)
+              if (streaming) _mm_sfence();
+#endif
+            } else if (streaming) {
               for (int m = t; m < M; m += nt) stream_copy(base + (size_t)m * len, in[m] + at, len);
 #if defined(__x86_64__)
               _mm_sfence();  // (streaming stores are weakly ordered: globally visible before the chunk counts as gathered)
@@ -182,6 +199,22 @@ struct GatherPool {
     const int node = bind && numa.ok ? NumaMap::rows_node(in_, M_, n_) : -1;
     std::lock_guard<std::mutex> lk(mu);
     in = in_, dst = dst_, n = n_, M = M_;
+    src_bytes = nullptr;
+    for (int g = 0; g <= nchunks; g++) cstart[g] = starts[g];
+    streaming = nt;
+    job_cpus = numa.cpus_of(node);
+    job_node = job_cpus ? node : -1;
+    groups = nchunks;
+    for (auto &d : done) d.store(0);
+    finished = 0;
+    generation++;
+    go.notify_all();
+  }
+  void submit_range(const void *src, void *dst_, size_t unit_, const size_t *starts, int nchunks, bool bind, bool nt) {
+    const int node = bind && numa.ok ? NumaMap::range_node(src, starts[nchunks] * unit_) : -1;
+    std::lock_guard<std::mutex> lk(mu);
+    src_bytes = static_cast<const unsigned char *>(src), dst_bytes = static_cast<unsigned char *>(dst_), unit = unit_;
+    in = nullptr, dst = nullptr, n = starts[nchunks], M = 0;
     for (int g = 0; g <= nchunks; g++) cstart[g] = starts[g];
     streaming = nt;
     job_cpus = numa.cpus_of(node);
@@ -278,6 +311,13 @@ struct earhip_render {
   std::unique_ptr<GatherPool> gather;  // staging threads of long host-pointer calls
   StreamPipe pipe;                     // ... their copy streams and events
   int last_host_chunks = 0;            // time chunks the last host-pointer call ran as (0: one piece)
+  // interleaved PCM frames (earhip_render_process_frames): the packed bytes of a call, pinned (staged from pageable memory) and on
+  // the device, sized at the first frames call for max_blocks frames of that call's width (grown by a call of wider frames); the
+  // interleaved outputs on the device; the device form's own converted rows and render outputs (a device-form call is still in
+  // flight when it returns: it keeps off the host forms' buffers)
+  PinBuf<unsigned char> p_bytes;
+  DevBuf<unsigned char> d_bytes;
+  DevBuf<float> d_ilv, d_rows, d_rows_out;
   // timing
   bool timing = false;
   bool last_timed = false;
@@ -326,6 +366,25 @@ struct earhip_render {
         if (e) pool.push_back(e);
     }
     pending.clear();
+  }
+
+  // Channel pointers that are evenly spaced inside memory the device reaches (earhip_host_alloc / earhip_host_register: the
+  // columns of a pinned matrix) need no staging copy: strided DMA in, and the output rows written in place.  The stride in
+  // floats; 0: not that shape.
+  size_t direct_stride(const float *const *ch, int count, size_t n) const {
+    if (ctx->host_ranges.empty() || count < 1) return 0;
+    // (addresses as integers: the channel pointers need not belong to one array as far as C++ knows)
+    const uintptr_t a0 = (uintptr_t)ch[0];
+    const uintptr_t step = count > 1 ? (uintptr_t)ch[1] - a0 : sizeof(float) * n;
+    if ((a0 & 15) != 0 || step % 16 != 0 || step < sizeof(float) * n || step > ((uintptr_t)1 << 40)) return 0;
+    for (int c = 1; c < count; c++)
+      if ((uintptr_t)ch[c] - (uintptr_t)ch[c - 1] != step) return 0;
+    return ctx->host_reachable(ch[0], step * (count - 1) + sizeof(float) * n) ? (size_t)(step / sizeof(float)) : 0;
+  }
+
+  // the chunk plan of a call from host memory (earhip_render_process and _process_frames alike)
+  HostChunkPlan host_plan(size_t nblocks, bool direct) const {
+    return plan_host_chunks(nblocks, B, M, direct, ctx->has(OPT_HOST_CHUNK_MB), ctx->get(OPT_HOST_CHUNK_MB), ctx->get(OPT_HOST_FIRST, 0));
   }
 
   // the launch plan of a call of nblocks blocks at the current sample clock
@@ -729,22 +788,9 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     const bool dbg = ctx->get(OPT_DEBUG_TIMING) != 0;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_a = dbg ? now() : 0.0;
-    const bool short_call = in_bytes < ((size_t)16 << 20) || r->M < 16 || (ctx->has(OPT_HOST_CHUNK_MB) && ctx->get(OPT_HOST_CHUNK_MB) <= 0);
-    // Channel pointers that are evenly spaced inside memory the device reaches (earhip_host_alloc /
-    // earhip_host_register: the columns of a pinned matrix) need no staging copy: strided DMA in, and
-    // the output rows written in place.  stride in floats; 0: not that shape.
-    auto direct_stride = [&](const float *const *ch, int count) -> size_t {
-      if (ctx->host_ranges.empty() || count < 1) return 0;
-      // (addresses as integers: the channel pointers need not belong to one array as far as C++ knows)
-      const uintptr_t a0 = (uintptr_t)ch[0];
-      const uintptr_t step = count > 1 ? (uintptr_t)ch[1] - a0 : sizeof(float) * n;
-      if ((a0 & 15) != 0 || step % 16 != 0 || step < sizeof(float) * n || step > ((uintptr_t)1 << 40)) return 0;
-      for (int c = 1; c < count; c++)
-        if ((uintptr_t)ch[c] - (uintptr_t)ch[c - 1] != step) return 0;
-      return ctx->host_reachable(ch[0], step * (count - 1) + sizeof(float) * n) ? (size_t)(step / sizeof(float)) : 0;
-    };
-    const size_t in_st = direct_stride(in, r->M);
-    const size_t out_st = r->NP <= 1 || !short_call ? direct_stride(out, r->N) : 0;
+    const bool short_call = r->host_plan(nblocks, false).short_call;
+    const size_t in_st = r->direct_stride(in, r->M, n);
+    const size_t out_st = r->NP <= 1 || !short_call ? r->direct_stride(out, r->N, n) : 0;
     r->last_host_chunks = 0;
     if (!short_call) {
       // Long calls (libear's calling convention for offline renders: host channel pointers, any length): the call is cut
@@ -756,26 +802,11 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
       // pointers the staging threads gather chunk c + 1 into the pinned buffer (chunk-major: one linear transfer per
       // chunk) while chunk c is on the bus, and the outputs of finished chunks are handed back to the caller's rows while
       // later chunks are still in flight; from device-reachable rows (earhip_host_alloc / _register) neither copy exists.
-      const size_t block_bytes = sizeof(float) * (size_t)r->B * r->M;
-      // (rows in device-reachable memory go by strided DMA, which wants long row pieces: 32 MB chunks = 32 KB pieces at 1024
-      // objects; staged rows: 16 MB — the pieces the staging threads copy are then 16 KB, and the first chunk's gather, which
-      // nothing overlaps, stays short)
-      const size_t want_bytes = (size_t)std::max(1, ctx->get(OPT_HOST_CHUNK_MB, in_st ? 32 : 16)) << 20;
-      size_t cb = std::max<size_t>(1, want_bytes / block_bytes);
-      cb = std::max(cb, (nblocks + GatherPool::kMaxGroups - 2) / (GatherPool::kMaxGroups - 1));
-      size_t gran = 1;  // (chunks start on 16-byte boundaries of the staging rows: vector loads)
-      while ((gran * (size_t)r->B) % 4 != 0) gran++;
-      cb = (cb + gran - 1) / gran * gran;
-      // (option HOST_FIRST = 1: from staged rows the first chunk a quarter of the others — its gather is the one nothing overlaps —;
-      // measured level with whole chunks (2.906 vs 2.905 ms per 64-block call): the staging threads are through ALL chunks of such a
-      // call after 0.66 ms, the call's time is the bus's plus ~19 us per chunk — 11 between two copies on a stream, 8 for the event
-      // and the kernels' stream behind it, tools/experiments/h2d_chunks.hip — so the default keeps whole chunks)
-      size_t cb0 = in_st || ctx->get(OPT_HOST_FIRST, 0) == 0 ? cb : std::max(gran, cb / 4 / gran * gran);
-      if (cb0 >= nblocks) cb0 = cb;
-      size_t cstart[GatherPool::kMaxGroups + 1];
-      int nch = 0;
-      for (size_t b = 0; b < nblocks; b += nch == 1 ? cb0 : cb) cstart[nch++] = b * r->B;  // (nch counts the chunk being opened)
-      cstart[nch] = n;
+      // (the plan, the same for earhip_render_process_frames: host_gather.h, plan_host_chunks)
+      const HostChunkPlan plan = r->host_plan(nblocks, in_st != 0);
+      const size_t cb = plan.cb;
+      const size_t *cstart = plan.cstart;
+      const int nch = plan.nch;
       r->pipe.make();
       if (!in_st) {
         if (!r->gather) {
@@ -889,6 +920,209 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     if (dbg)
       fprintf(stderr, "render_process: gather+H2D enqueue %.1f us, launches %.1f us, wait %.1f us, scatter %.1f us\n", t_b - t_a,
               t_c - t_b, t_d - t_c, now() - t_d);
+  });
+}
+
+// ---- interleaved PCM frames (include/earhip.h, group F: earhip_render_process_frames) --------------------------------------
+static int pcm_sample_bytes(int fmt) {
+  switch (fmt) {
+    case EARHIP_PCM_S16: return 2;
+    case EARHIP_PCM_S24: return 3;
+    case EARHIP_PCM_S32: case EARHIP_PCM_F32: return 4;
+    default: return 0;
+  }
+}
+
+// what both forms refuse before they touch anything
+static void check_frames_args(const earhip_render *r, size_t nblocks, const void *frames, int fmt, int frame_channels, int first_channel) {
+  require(r != nullptr, "render must not be NULL");
+  const int S = pcm_sample_bytes(fmt);
+  require(S != 0, "unknown PCM format");
+  require(frames != nullptr, "frames must not be NULL");
+  require(first_channel >= 0, "first_channel must be >= 0");
+  require((int64_t)first_channel + r->M <= (int64_t)frame_channels, "first_channel + n_objects exceeds frame_channels");
+  require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
+  require(fmt == EARHIP_PCM_S24 || reinterpret_cast<uintptr_t>(frames) % (uintptr_t)S == 0, "frames not aligned to the sample size");
+}
+
+// frames -> planar rows out [M][row_stride] (samples [0, len)), on stream s
+static void launch_pcm_to_rows(int fmt, const void *frames, size_t frame_bytes, size_t first_byte, int M, size_t len, float *out,
+                               size_t row_stride, hipStream_t s) {
+  const dim3 grid((unsigned)((len + kPcmFrames - 1) / kPcmFrames), (unsigned)((M + kPcmChans - 1) / kPcmChans));
+  const unsigned char *f = static_cast<const unsigned char *>(frames);
+  switch (fmt) {
+    case EARHIP_PCM_S16: hipLaunchKernelGGL((k_pcm_to_rows<2, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
+    case EARHIP_PCM_S24: hipLaunchKernelGGL((k_pcm_to_rows<3, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
+    case EARHIP_PCM_S32: hipLaunchKernelGGL((k_pcm_to_rows<4, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
+    default: hipLaunchKernelGGL((k_pcm_to_rows<4, true>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
+  }
+  EARHIP_HIP(hipGetLastError());
+}
+
+// planar rows [N][in_stride] -> frames [len][out_stride], on stream s
+static void launch_rows_to_frames(const float *in, size_t in_stride, int N, size_t len, float *out, size_t out_stride, hipStream_t s) {
+  const dim3 grid((unsigned)((len + kIlvFrames - 1) / kIlvFrames), (unsigned)((N + kIlvChans - 1) / kIlvChans));
+  hipLaunchKernelGGL(k_rows_to_frames, grid, dim3(256), 0, s, in, in_stride, N, len, out, out_stride);
+  EARHIP_HIP(hipGetLastError());
+}
+
+int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels,
+                                 int first_channel, float *const *out, int out_interleaved) {
+  return guarded([&] {
+    check_frames_args(r, nblocks, frames, fmt, frame_channels, first_channel);
+    require(out != nullptr, "out must not be NULL");
+    for (int c = 0; c < (out_interleaved ? 1 : r->N); c++) require(out[c] != nullptr, "out must not be NULL");
+    if (nblocks == 0) return;
+    earhip_ctx *ctx = r->ctx;
+    ctx->use();
+    const int M = r->M, N = r->N;
+    const size_t S = (size_t)pcm_sample_bytes(fmt);
+    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
+    const size_t fb = (size_t)frame_channels * S, first_byte = (size_t)first_channel * S, bytes = n * fb;
+    const bool direct = ctx->host_reachable(frames, bytes);  // (device-reachable frames: DMA straight from the caller's buffer)
+    // (the plan of earhip_render_process on rows in the same kind of memory: the same chunks, the same results)
+    const HostChunkPlan plan = r->host_plan(nblocks, direct);
+    float *const out0 = out[0];
+    const size_t out_st = out_interleaved ? 0 : r->NP <= 1 || !plan.short_call ? r->direct_stride(out, N, n) : 0;
+    const bool out_direct = out_interleaved ? ctx->host_reachable(out0, sizeof(float) * n * N) : out_st != 0;
+    r->d_in.reserve(cap * M);
+    r->d_out.reserve(cap * N);
+    r->p_out.reserve(cap * N);
+    r->d_bytes.reserve(cap * fb + 16);  // (+16: the conversion kernel reads whole dwords)
+    if (!direct) r->p_bytes.reserve(cap * fb);
+    if (out_interleaved) r->d_ilv.reserve(cap * N);
+    const unsigned char *src = static_cast<const unsigned char *>(frames);
+    r->last_host_chunks = 0;
+    if (plan.short_call) {
+      if (!direct) {
+        std::memcpy(r->p_bytes.p, frames, bytes);
+        src = r->p_bytes.p;
+      }
+      EARHIP_HIP(hipMemcpyAsync(r->d_bytes.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+      launch_pcm_to_rows(fmt, r->d_bytes.p, fb, first_byte, M, n, r->d_in.p, n, ctx->stream);
+      if (out_interleaved) {
+        r->process_device(nblocks, r->d_in.p, n, r->d_out.p, n);
+        launch_rows_to_frames(r->d_out.p, n, N, n, r->d_ilv.p, N, ctx->stream);
+        EARHIP_HIP(hipMemcpyAsync(out_direct ? out0 : r->p_out.p, r->d_ilv.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
+      } else {
+        // (as earhip_render_process: a single-partition render writes its outputs straight into host memory)
+        const bool direct_out = r->NP <= 1;
+        float *dst = out_st ? out0 : direct_out ? r->p_out.p : r->d_out.p;
+        r->process_device(nblocks, r->d_in.p, n, dst, out_st ? out_st : n);
+        if (!out_st && !direct_out)
+          EARHIP_HIP(hipMemcpyAsync(r->p_out.p, r->d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+      if (out_interleaved && !out_direct) std::memcpy(out0, r->p_out.p, sizeof(float) * n * N);
+      if (!out_interleaved && !out_st)
+        for (int c = 0; c < N; c++) std::memcpy(out[c], r->p_out.p + (size_t)c * n, sizeof(float) * n);
+      return;
+    }
+    // Long calls: the pipeline of earhip_render_process, on the packed bytes.  Chunk c is one contiguous byte range of the caller's
+    // buffer: staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all (device-reachable
+    // frames); H2D on the copy stream; on the context's stream the conversion into the chunk's rows of d_in, then the chunk's
+    // render as an ordinary process call; D2H of its outputs on the second copy stream.
+    const size_t *cstart = plan.cstart;
+    const int nch = plan.nch;
+    r->pipe.make();
+    if (!direct) {
+      if (!r->gather) {
+        r->gather.reset(new GatherPool);
+        const int want = ctx->get(OPT_HOST_THREADS, 0);
+        r->gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
+      }
+      r->gather->submit_range(frames, r->p_bytes.p, fb, cstart, nch, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
+      src = r->p_bytes.p;
+    }
+    hipError_t err = hipSuccess;
+    std::string fail;
+    int recorded = 0;   // chunks whose output transfer THIS call has queued (ev_out[c] recorded)
+    int scattered = 0;  // ... whose outputs have been handed to the caller (only from pinned staging)
+    auto scatter_chunk = [&](int c) {
+      const size_t at = cstart[c], len = cstart[c + 1] - at;
+      if (out_interleaved) {
+        std::memcpy(out0 + (size_t)N * at, r->p_out.p + (size_t)N * at, sizeof(float) * len * N);
+      } else {
+        const float *base = r->p_out.p + (size_t)N * at;
+        for (int ch = 0; ch < N; ch++) std::memcpy(out[ch] + at, base + (size_t)ch * len, sizeof(float) * len);
+      }
+    };
+    for (int c = 0; c < nch; c++) {
+      const size_t at = cstart[c], len = cstart[c + 1] - at;
+      float *din = r->d_in.p + (size_t)M * at, *dout = r->d_out.p + (size_t)N * at;
+      if (!direct) {
+        GatherPool &gp = *r->gather;
+        while (gp.done[c].load(std::memory_order_acquire) < gp.nthreads()) {
+          // (meanwhile: outputs of chunks whose transfer this call queued and that have landed go back to the caller)
+          if (!out_direct && scattered < recorded && err == hipSuccess && fail.empty() &&
+              hipEventQuery(r->pipe.ev_out[scattered]) == hipSuccess)
+            scatter_chunk(scattered++);
+          else
+            std::this_thread::yield();
+        }
+      }
+      if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
+      err = hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
+      if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_in[c], r->pipe.in);
+      if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream, r->pipe.ev_in[c], 0);
+      if (err != hipSuccess) continue;
+      try {
+        launch_pcm_to_rows(fmt, r->d_bytes.p + at * fb, fb, first_byte, M, len, din, len, ctx->stream);
+        r->process_device(len / r->B, din, len, dout, len);
+        if (out_interleaved) launch_rows_to_frames(dout, len, N, len, r->d_ilv.p + (size_t)N * at, N, ctx->stream);
+      } catch (const Error &e) {
+        fail = e.msg;
+        continue;
+      }
+      err = hipEventRecord(r->pipe.ev_k[c], ctx->stream);
+      if (err == hipSuccess) err = hipStreamWaitEvent(r->pipe.out, r->pipe.ev_k[c], 0);
+      if (err != hipSuccess) continue;
+      if (out_interleaved)
+        err = hipMemcpyAsync((out_direct ? out0 : r->p_out.p) + (size_t)N * at, r->d_ilv.p + (size_t)N * at, sizeof(float) * len * N,
+                             hipMemcpyDeviceToHost, r->pipe.out);
+      else if (out_st)
+        err = hipMemcpy2DAsync(out0 + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, N, hipMemcpyDeviceToHost,
+                               r->pipe.out);
+      else
+        err = hipMemcpyAsync(r->p_out.p + (size_t)N * at, dout, sizeof(float) * len * N, hipMemcpyDeviceToHost, r->pipe.out);
+      if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_out[c], r->pipe.out);
+      if (err == hipSuccess) recorded = c + 1;
+    }
+    if (!direct) r->gather->wait_all();
+    (void)hipStreamSynchronize(r->pipe.in);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(r->pipe.out);
+    EARHIP_HIP(err);
+    if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
+    if (!out_direct)
+      for (; scattered < nch; scattered++) scatter_chunk(scattered);
+    r->last_host_chunks = nch;
+  });
+}
+
+int earhip_render_process_frames_device(earhip_render *r, size_t nblocks, const void *frames_dev, earhip_pcm_format fmt,
+                                        int frame_channels, int first_channel, float *out_dev, size_t out_stride, int out_interleaved) {
+  return guarded([&] {
+    check_frames_args(r, nblocks, frames_dev, fmt, frame_channels, first_channel);
+    require(out_dev != nullptr, "out_dev must not be NULL");
+    require(out_interleaved ? out_stride >= (size_t)r->N : out_stride >= nblocks * r->B, "stride too small");
+    if (nblocks == 0) return;
+    earhip_ctx *ctx = r->ctx;
+    ctx->use();
+    const size_t S = (size_t)pcm_sample_bytes(fmt);
+    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
+    if (r->d_rows.n < cap * r->M || (out_interleaved && r->d_rows_out.n < cap * r->N)) {
+      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (first use: nothing of this renderer may still read them)
+      r->d_rows.reserve(cap * r->M);
+      if (out_interleaved) r->d_rows_out.reserve(cap * r->N);
+    }
+    launch_pcm_to_rows(fmt, frames_dev, (size_t)frame_channels * S, (size_t)first_channel * S, r->M, n, r->d_rows.p, n, ctx->stream);
+    if (out_interleaved) {
+      r->process_device(nblocks, r->d_rows.p, n, r->d_rows_out.p, n);
+      launch_rows_to_frames(r->d_rows_out.p, n, r->N, n, out_dev, out_stride, ctx->stream);
+    } else {
+      r->process_device(nblocks, r->d_rows.p, n, out_dev, out_stride);
+    }
   });
 }
 

@@ -46,6 +46,12 @@ struct NumaMap {
     const int a = page_node(in[0]), b = page_node(in[M / 2] + n / 2), c = page_node(in[M - 1] + (n ? n - 1 : 0));
     return a >= 0 && a == b && b == c ? a : -1;
   }
+  // the node of the first, middle and last byte of a contiguous range when they agree
+  static int range_node(const void *p, size_t bytes) {
+    const char *c = static_cast<const char *>(p);
+    const int a = page_node(c), b = page_node(c + bytes / 2), e = page_node(c + (bytes ? bytes - 1 : 0));
+    return a >= 0 && a == b && b == e ? a : -1;
+  }
   const cpu_set_t *cpus_of(int node) {
     if (!ok || node < 0 || node >= 1024) return nullptr;
     if ((size_t)node >= known.size()) known.resize(node + 1, 0), node_cpus.resize(node + 1);
@@ -99,6 +105,84 @@ static inline void stream_copy(float *dst, const float *src, size_t nfloats) {
 #else
   std::memcpy(dst, src, nfloats * sizeof(float));
 #endif
+}
+
+// The contiguous-range form for interleaved PCM frames (earhip_render_process_frames): a time chunk of the caller's frame buffer is
+// one byte range, copied into the pinned staging buffer at the same offset.  Any alignment of either side; streaming stores on the
+// destination's 64-byte lines as in stream_copy.  (The caller fences before it publishes the chunk.)
+static inline void stream_copy_bytes(void *dst_, const void *src_, size_t bytes) {
+  char *dst = static_cast<char *>(dst_);
+  const char *src = static_cast<const char *>(src_);
+#if defined(__x86_64__)
+  const size_t head = std::min(bytes, (size_t)((64 - (reinterpret_cast<uintptr_t>(dst) & 63)) & 63));
+  if (head) std::memcpy(dst, src, head);
+  dst += head, src += head, bytes -= head;
+  const size_t lines = bytes / 64;
+  const __m128i *s = reinterpret_cast<const __m128i *>(src);
+  __m128i *d = reinterpret_cast<__m128i *>(dst);
+  for (size_t i = 0; i < lines; i++) {
+    const __m128i a = _mm_loadu_si128(s + 4 * i), b = _mm_loadu_si128(s + 4 * i + 1), c = _mm_loadu_si128(s + 4 * i + 2), e = _mm_loadu_si128(s + 4 * i + 3);
+    _mm_stream_si128(d + 4 * i, a);
+    _mm_stream_si128(d + 4 * i + 1, b);
+    _mm_stream_si128(d + 4 * i + 2, c);
+    _mm_stream_si128(d + 4 * i + 3, e);
+  }
+  const size_t done = lines * 64;
+  if (bytes > done) std::memcpy(dst + done, src + done, bytes - done);
+#else
+  std::memcpy(dst, src, bytes);
+#endif
+}
+
+// Thread t's share [*lo, *hi) of a byte range of `bytes` split among nt threads: contiguous slices whose inner boundaries fall on
+// multiples of 64 bytes (no two threads write one cache line of the destination when both sides share their offset mod 64).
+static inline void range_slice(size_t bytes, int t, int nt, size_t *lo, size_t *hi) {
+  const size_t lines = (bytes + 63) / 64;
+  *lo = std::min(bytes, lines * (size_t)t / (size_t)nt * 64);
+  *hi = t + 1 == nt ? bytes : std::min(bytes, lines * (size_t)(t + 1) / (size_t)nt * 64);
+}
+
+// The chunk plan of a call from host memory: whether it runs as one piece (a short call) or as the pipeline of time chunks, and
+// where the chunks start.  earhip_render_process and earhip_render_process_frames both take it from here, from the FLOAT-
+// EQUIVALENT size of the call (4 bytes per input sample whatever the frames' format), so that both forms cut a call at the same
+// block boundaries — each chunk is a process call of its own, and a different cut changes results in the last bits.
+//   direct: the inputs lie in device-reachable memory (earhip_host_alloc / _register): 32 MB chunks by DMA, else 16 MB staged;
+//   has_chunk_mb / chunk_mb: option HOST_CHUNK_MB (set / its value), host_first: option HOST_FIRST.
+struct HostChunkPlan {
+  static constexpr int kMaxChunks = 64;
+  bool short_call = true;
+  int nch = 0;                          // chunks (long calls)
+  size_t cb = 0;                        // blocks per chunk (the first may be shorter: HOST_FIRST)
+  size_t cstart[kMaxChunks + 1] = {0};  // chunk c = samples [cstart[c], cstart[c + 1]) of every channel
+};
+static inline HostChunkPlan plan_host_chunks(size_t nblocks, int B, int M, bool direct, bool has_chunk_mb, int chunk_mb, int host_first) {
+  HostChunkPlan p;
+  const size_t n = nblocks * (size_t)B;
+  const size_t in_bytes = sizeof(float) * n * (size_t)M;
+  p.short_call = in_bytes < ((size_t)16 << 20) || M < 16 || (has_chunk_mb && chunk_mb <= 0);
+  if (p.short_call) return p;
+  const size_t block_bytes = sizeof(float) * (size_t)B * (size_t)M;
+  // (rows in device-reachable memory go by strided DMA, which wants long row pieces: 32 MB chunks = 32 KB pieces at 1024
+  // objects; staged rows: 16 MB — the pieces the staging threads copy are then 16 KB, and the first chunk's gather, which
+  // nothing overlaps, stays short)
+  const size_t want_bytes = (size_t)std::max(1, has_chunk_mb ? chunk_mb : direct ? 32 : 16) << 20;
+  size_t cb = std::max<size_t>(1, want_bytes / block_bytes);
+  cb = std::max(cb, (nblocks + HostChunkPlan::kMaxChunks - 2) / (HostChunkPlan::kMaxChunks - 1));
+  size_t gran = 1;  // (chunks start on 16-byte boundaries of the staging rows: vector loads)
+  while ((gran * (size_t)B) % 4 != 0) gran++;
+  cb = (cb + gran - 1) / gran * gran;
+  // (option HOST_FIRST = 1: from staged rows the first chunk a quarter of the others — its gather is the one nothing overlaps —;
+  // measured level with whole chunks (2.906 vs 2.905 ms per 64-block call): the staging threads are through ALL chunks of such a
+  // call after 0.66 ms, the call's time is the bus's plus ~19 us per chunk — 11 between two copies on a stream, 8 for the event
+  // and the kernels' stream behind it, tools/experiments/h2d_chunks.hip — so the default keeps whole chunks)
+  size_t cb0 = direct || host_first == 0 ? cb : std::max(gran, cb / 4 / gran * gran);
+  if (cb0 >= nblocks) cb0 = cb;
+  int nch = 0;
+  for (size_t b = 0; b < nblocks; b += nch == 1 ? cb0 : cb) p.cstart[nch++] = b * (size_t)B;  // (nch counts the chunk being opened)
+  p.cstart[nch] = n;
+  p.nch = nch;
+  p.cb = cb;
+  return p;
 }
 
 // How many staging threads a long host-pointer call gets by default: 8 — the gather is bound by its memory accesses' latency, not by

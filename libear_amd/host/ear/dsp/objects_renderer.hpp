@@ -75,10 +75,66 @@ namespace ear {
                           size_t out_stride) {
         hip::check(earhip_render_process_device(h_, nblocks, in_dev, in_stride, out_dev, out_stride));
       }
+      /// Interleaved PCM frames (include/earhip.h: earhip_render_process_frames): nblocks * block_size frames of
+      /// frame_channels samples; this renderer's inputs are channels [first_channel, first_channel + n_objects).  The
+      /// samples are converted to float on the device: int16_t s16, int32_t s32, float f32, and uint8_t s24 (3 bytes a
+      /// sample).  out: n_out planar rows, as process().
+      void process_frames(size_t nblocks, const int16_t *frames, int frame_channels, int first_channel, float *const *out) {
+        frames_(nblocks, frames, EARHIP_PCM_S16, frame_channels, first_channel, out, 0);
+      }
+      void process_frames(size_t nblocks, const uint8_t *frames, int frame_channels, int first_channel, float *const *out) {
+        frames_(nblocks, frames, EARHIP_PCM_S24, frame_channels, first_channel, out, 0);
+      }
+      void process_frames(size_t nblocks, const int32_t *frames, int frame_channels, int first_channel, float *const *out) {
+        frames_(nblocks, frames, EARHIP_PCM_S32, frame_channels, first_channel, out, 0);
+      }
+      void process_frames(size_t nblocks, const float *frames, int frame_channels, int first_channel, float *const *out) {
+        frames_(nblocks, frames, EARHIP_PCM_F32, frame_channels, first_channel, out, 0);
+      }
+      /// the same with interleaved outputs: out_interleaved [frames][n_out]
+      void process_frames(size_t nblocks, const int16_t *frames, int frame_channels, int first_channel, float *out_interleaved) {
+        frames_(nblocks, frames, EARHIP_PCM_S16, frame_channels, first_channel, &out_interleaved, 1);
+      }
+      void process_frames(size_t nblocks, const uint8_t *frames, int frame_channels, int first_channel, float *out_interleaved) {
+        frames_(nblocks, frames, EARHIP_PCM_S24, frame_channels, first_channel, &out_interleaved, 1);
+      }
+      void process_frames(size_t nblocks, const int32_t *frames, int frame_channels, int first_channel, float *out_interleaved) {
+        frames_(nblocks, frames, EARHIP_PCM_S32, frame_channels, first_channel, &out_interleaved, 1);
+      }
+      void process_frames(size_t nblocks, const float *frames, int frame_channels, int first_channel, float *out_interleaved) {
+        frames_(nblocks, frames, EARHIP_PCM_F32, frame_channels, first_channel, &out_interleaved, 1);
+      }
+      /// device-resident frames (or device-reachable host memory) -> device outputs, asynchronous on the context's stream:
+      /// out_interleaved false: out_dev [n_out][out_stride]; true: out_dev [frames][out_stride] (out_stride >= n_out)
+      void process_frames_device(size_t nblocks, const int16_t *frames_dev, int frame_channels, int first_channel, float *out_dev,
+                                 size_t out_stride, bool out_interleaved = false) {
+        frames_device_(nblocks, frames_dev, EARHIP_PCM_S16, frame_channels, first_channel, out_dev, out_stride, out_interleaved);
+      }
+      void process_frames_device(size_t nblocks, const uint8_t *frames_dev, int frame_channels, int first_channel, float *out_dev,
+                                 size_t out_stride, bool out_interleaved = false) {
+        frames_device_(nblocks, frames_dev, EARHIP_PCM_S24, frame_channels, first_channel, out_dev, out_stride, out_interleaved);
+      }
+      void process_frames_device(size_t nblocks, const int32_t *frames_dev, int frame_channels, int first_channel, float *out_dev,
+                                 size_t out_stride, bool out_interleaved = false) {
+        frames_device_(nblocks, frames_dev, EARHIP_PCM_S32, frame_channels, first_channel, out_dev, out_stride, out_interleaved);
+      }
+      void process_frames_device(size_t nblocks, const float *frames_dev, int frame_channels, int first_channel, float *out_dev,
+                                 size_t out_stride, bool out_interleaved = false) {
+        frames_device_(nblocks, frames_dev, EARHIP_PCM_F32, frame_channels, first_channel, out_dev, out_stride, out_interleaved);
+      }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
       size_t block_size() const { return block_size_; }
 
      private:
+      void frames_(size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels, int first_channel, float *const *out,
+                   int interleaved) {
+        hip::check(earhip_render_process_frames(h_, nblocks, frames, fmt, frame_channels, first_channel, out, interleaved));
+      }
+      void frames_device_(size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels, int first_channel,
+                          float *out_dev, size_t out_stride, bool interleaved) {
+        hip::check(earhip_render_process_frames_device(h_, nblocks, frames, fmt, frame_channels, first_channel, out_dev, out_stride,
+                                                       interleaved ? 1 : 0));
+      }
       size_t n_objects_, n_out_, block_size_;
       bool two_buses_;
       earhip_render *h_ = nullptr;
