@@ -16,10 +16,15 @@ between dense uniform(0,1) gain vectors (worst case).
 on: 1024 objects in total); `--objects/--layout/--block-size/--blocks/--buses/--hoa` override single
 fields.  Rank 0 prints ONE JSON line.  `value` = object-samples consumed per second over all GPUs
 (Msamples/s = M*B*T / t_step / 1e6); `rtf` = real-time factor (B*T/48000) / t_step.
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line; `--full` adds
+everything else the line can carry: the parity gates against the CPU path, the CPU baselines, the other
+precisions, block mode and host-pointer calls, per-step events, the measured read bandwidth, the `secondary`
+workloads of the default configuration and, on several GPUs, the link probe, the exchange self-check, the
+weak-scaling figure and the other decompositions.
 Multi-GPU: the scene's objects are sharded over the ranks (BASELINE config 4: strong scaling), each
 rank renders its shard and the partial loudspeaker buses are summed by one RCCL reduce-scatter over the
 channel axis, overlapped with the next step's render; the weak-scaling figure (--objects per rank) is
-reported in the same line under `weak_scaling`.
+reported in the same line under `weak_scaling` (--full).
 """
 import argparse
 import json
@@ -154,6 +159,15 @@ def producer_bench(args):
     ms = (time.perf_counter() - t0) * 1e3 / steps
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, [("direct", direct, 0), ("diffuse", diffuse, 0)])
+    line = {"metric": "gain vectors per second of the Objects gain producer (point source + polar extent panners)",
+            "value": round(n / ms / 1e3, 2), "unit": "Mpositions/s", "n_gpus": 1, "steps": steps, "ms_per_step": round(ms, 4),
+            "higher_is_better": True, "dtype": "f64 set-up / f32 weights and sums (as libear)", "data": "synthetic",
+            "config": {"workload": f"{n} (object, metadata block) positions, layout {layout}, widths 0-120, heights 0-60 "
+                                   "degrees, distances 0.5-1.5, a quarter with depth", "entry": "earhip_panner_calculate_extent_device"}}
+    if not args.full:
+        print(json.dumps(line))
+        pan.close()
+        return
     # parity of what was timed (a sample of it) and the CPU baseline: the oracle's PolarExtent, one thread
     import _oracle
     k = min(n, 2000)
@@ -169,16 +183,11 @@ def producer_bench(args):
     md, mf = host["diffuse"][:k] < 1.0, host["diffuse"][:k] > 0.0
     worst = max(rel(gd[md], wd[md].astype(np.float64)), rel(gf[mf], wf[mf].astype(np.float64)))
     ok = worst <= 1e-5
-    print(json.dumps({
-        "metric": "gain vectors per second of the Objects gain producer (point source + polar extent panners)",
-        "value": round(n / ms / 1e3, 2), "unit": "Mpositions/s", "n_gpus": 1, "steps": steps, "ms_per_step": round(ms, 4),
-        "higher_is_better": True, "dtype": "f64 set-up / f32 weights and sums (as libear)", "data": "synthetic",
-        "config": {"workload": f"{n} (object, metadata block) positions, layout {layout}, widths 0-120, heights 0-60 "
-                               "degrees, distances 0.5-1.5, a quarter with depth", "entry": "earhip_panner_calculate_extent_device"},
-        "parity": {"against": "oracle PolarExtent (scalar float core)", "sample": k, "max_rel_norm": worst, "tolerance": 1e-5,
-                   "pass": ok},
-        "cpu_baseline": {"value": round(k / cpu_s / 1e6, 5), "unit": "Mpositions/s", "cores": 1, "kind": "port",
-                         "sample": f"{k} of the same positions", "cpu": cpu_model()}}))
+    line["parity"] = {"against": "oracle PolarExtent (scalar float core)", "sample": k, "max_rel_norm": worst, "tolerance": 1e-5,
+                      "pass": ok}
+    line["cpu_baseline"] = {"value": round(k / cpu_s / 1e6, 5), "unit": "Mpositions/s", "cores": 1, "kind": "port",
+                            "sample": f"{k} of the same positions", "cpu": cpu_model()}
+    print(json.dumps(line))
     pan.close()
     if not ok:
         print("producer parity FAILED", file=sys.stderr)
@@ -191,7 +200,8 @@ def refbench(args):
     100 samples (tests/gain_interpolator_tests.cpp:259-296) — the latency-bound end of the path.  Block mode = that
     very call through the drop-in entry point (host channel pointers: H2D, kernels, D2H, sync); stream mode = the same
     curve density over 2^20 samples per call, device resident; the CPU path (the oracle's restatement, -O3 -DNDEBUG,
-    one thread) beside both; and where one host core and the GPU cross over as the call shrinks."""
+    one thread) beside both; and where one host core and the GPU cross over as the call shrinks (block mode, the CPU path
+    and the crossover: --full)."""
     import numpy as np
     import torch
     import _oracle
@@ -208,9 +218,11 @@ def refbench(args):
         t = np.arange(100, total, 100, dtype=np.int64)
         return t, rng.uniform(0.0, 1.0, (len(t), m, n_out)).astype(np.float32)
 
-    def block_mode(m, calls=200):
+    def block_inputs(m):
         t, v = points(m, n)
-        x = rng.uniform(-1.0, 1.0, (m, n)).astype(np.float32)
+        return m, t, v, rng.uniform(-1.0, 1.0, (m, n)).astype(np.float32)
+
+    def block_mode(m, t, v, x, calls=200):
         g = capi.GainInterp(ctx, m, n_out)
         g.set_points(t, v)
         for _ in range(20):
@@ -230,12 +242,15 @@ def refbench(args):
         cpu = (time.perf_counter() - c0) / reps
         return lat[len(lat) // 2], lat[int(0.95 * len(lat))], cpu, scenes.rel_rms(got, want)
 
-    gpu_ms, gpu_p95, cpu_s, err = block_mode(32)
-    sweep = []
-    for m in (1, 2, 4, 8, 16, 32, 64, 128):
-        g_, _, c_, e_ = block_mode(m, calls=100)
-        sweep.append({"inputs": m, "gpu_block_ms": round(g_ * 1e3, 4), "cpu_ms": round(c_ * 1e3, 4), "rel_rms": float(f"{e_:.2e}")})
-    cross = next((s["inputs"] for s in sweep if s["gpu_block_ms"] < s["cpu_ms"]), None)
+    # (drawn without --full too: the stream mode's inputs come from the same generator after these)
+    call_in, sweep_in = block_inputs(32), [block_inputs(m) for m in (1, 2, 4, 8, 16, 32, 64, 128)]
+    if args.full:
+        gpu_ms, gpu_p95, cpu_s, err = block_mode(*call_in)
+        sweep = []
+        for inp in sweep_in:
+            g_, _, c_, e_ = block_mode(*inp, calls=100)
+            sweep.append({"inputs": inp[0], "gpu_block_ms": round(g_ * 1e3, 4), "cpu_ms": round(c_ * 1e3, 4), "rel_rms": float(f"{e_:.2e}")})
+        cross = next((s["inputs"] for s in sweep if s["gpu_block_ms"] < s["cpu_ms"]), None)
     # stream mode: the same point density over a long device-resident call
     m, total = 32, n * 1024
     t, v = points(m, total)
@@ -256,6 +271,22 @@ def refbench(args):
     dt = (time.perf_counter() - t0) / steps
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, [("outputs", out, 1)])
+    bytes_alg = 4 * (m * total + n_out * total) + v.nbytes
+    line = {
+        "metric": "Msamples/s", "value": round(m * total / dt / 1e6, 1), "unit": "Msamples/s", "n_gpus": 1, "steps": steps,
+        "warmup": warm, "ms_per_step": round(dt * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 io / f16x2-split MFMA, f32 accumulate", "data": "synthetic",
+        "config": {"workload": "refbench: GainInterpolator<LinearInterpMatrix>::process, 32 -> 24 channels, a random matrix "
+                               "point every 100 samples (the reference's matrix_benchmark, tests/gain_interpolator_tests.cpp:"
+                               "259-296); stream mode: 1024 x 1024 samples per call, device resident", "baseline_config": "refbench"},
+        "roofline": {"bound": "hbm", "achieved": round(bytes_alg / dt / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(bytes_alg / dt / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
+                     "note": "algorithmic bytes: inputs + outputs + the matrix points, per call"}}
+    if not args.full:
+        g.close()
+        print(json.dumps(line))
+        ctx.close()
+        return
     # parity of the stream call on a window, and the CPU path's rate on the same window
     w = 8 * n
     xs = x[:, :w].cpu().numpy()
@@ -265,18 +296,8 @@ def refbench(args):
     cpu_stream_s = time.perf_counter() - c0
     serr = scenes.rel_rms(out[:, :w].cpu().numpy(), want)
     g.close()
-    bytes_alg = 4 * (m * total + n_out * total) + v.nbytes
     ok = err <= 1e-6 and serr <= 1e-6
-    print(json.dumps({
-        "metric": "Msamples/s", "value": round(m * total / dt / 1e6, 1), "unit": "Msamples/s", "n_gpus": 1, "steps": steps,
-        "warmup": warm, "ms_per_step": round(dt * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 io / f16x2-split MFMA, f32 accumulate", "data": "synthetic",
-        "config": {"workload": "refbench: GainInterpolator<LinearInterpMatrix>::process, 32 -> 24 channels, a random matrix "
-                               "point every 100 samples (the reference's matrix_benchmark, tests/gain_interpolator_tests.cpp:"
-                               "259-296); stream mode: 1024 x 1024 samples per call, device resident", "baseline_config": "refbench"},
-        "roofline": {"bound": "hbm", "achieved": round(bytes_alg / dt / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(bytes_alg / dt / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
-                     "note": "algorithmic bytes: inputs + outputs + the matrix points, per call"},
+    line.update({
         "block_mode": {"what": "the reference benchmark's own call (1024 samples) through earhip_gain_interp_process: host "
                                "channel pointers, H2D, kernels, D2H, sync", "ms_per_call": round(gpu_ms * 1e3, 4),
                        "p95_ms": round(gpu_p95 * 1e3, 4), "Msamples_per_s": round(32 * n / gpu_ms / 1e6, 1),
@@ -289,7 +310,8 @@ def refbench(args):
                       "note": "one call of 1024 samples from host pointers against one host core; below the crossover the "
                               "call is launch + PCIe latency on the GPU side"},
         "parity": {"block_rel_rms_vs_cpu": float(f"{err:.3e}"), "stream_window_rel_rms_vs_cpu": float(f"{serr:.3e}"),
-                   "tolerance": 1e-6, "pass": bool(ok)}}))
+                   "tolerance": 1e-6, "pass": bool(ok)}})
+    print(json.dumps(line))
     ctx.close()
     if not ok:
         print("refbench parity FAILED", file=sys.stderr)
@@ -331,7 +353,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=sorted(PRESETS) + ["refbench"], default="C4",
                     help="BASELINE.json configuration; refbench: the reference's own matrix_benchmark shape (32 -> 24 channels, "
-                         "1024 samples, a point every 100 samples), block and stream mode, CPU path beside it")
+                         "1024 samples, a point every 100 samples), stream mode (--full: block mode and the CPU path beside it)")
     ap.add_argument("--objects", type=int, default=None, help="objects of the scene (in total; --scaling weak: per GPU)")
     ap.add_argument("--hoa", type=int, default=None, help="extra input channels through a constant decode matrix (config 5)")
     ap.add_argument("--blocks", type=int, default=None, help="blocks per step (stream length T)")
@@ -345,7 +367,14 @@ def main():
                     help="untimed steps of the same workload before the W warm-up steps, until this much wall time "
                          "has passed: an idle MI355X needs 10-20 ms of load to leave its low-power clocks "
                          "(steps measured right after start-up are ~9 %% slower)")
-    ap.add_argument("--cpu-blocks", type=int, default=160, help="blocks of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the line can carry: parity gates against the CPU path, CPU "
+                         "baselines, the exact-f32 and strict gain kernels, block mode, host-pointer calls, per-step events, the "
+                         "measured read bandwidth, the `secondary` workloads of the default invocation; several GPUs: link probe, "
+                         "exchange self-check, weak scaling, the other decompositions; refbench / --producer: their block-mode "
+                         "sweep, CPU path and parity.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--cpu-blocks", type=int, default=160, help="--full: blocks of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--strict", action="store_true", help="bit-exact gain arithmetic (slower)")
     ap.add_argument("--scene", choices=("dense", "adm", "static", "moving", "mixed", "panned", "panned-adm", "levels", "levels-adm",
                                         "bursty", "bursty-adm", "bursty-moving"),
@@ -377,16 +406,17 @@ def main():
                          "0.45 ms, config 5's 0.225 -> 0.220, headline and config 2 unchanged; the caller owns this layout "
                          "(libear takes channel POINTERS: ptr_adapter.hpp:17-24)")
     ap.add_argument("--brief", action="store_true",
-                    help="the timed stream-mode steps, their per-kernel times and the parity gate on the timed buffer only "
-                         "(no block-mode, exact-f32, strict or CPU-baseline legs): what the `secondary` entries of the default line run")
+                    help="--full: of its legs the parity gate on the timed buffer only (no block-mode, exact-f32, strict or "
+                         "CPU-baseline legs): what the `secondary` entries of the --full line run")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="the default invocation (config C4, dense scene, one GPU) without its `secondary` runs of the other workloads")
+                    help="--full on the default invocation (config C4, dense scene, one GPU) without its `secondary` runs of the "
+                         "other workloads")
     ap.add_argument("--stream-only", action="store_true",
                     help="only the timed stream-mode steps (no block-mode, parity or CPU legs): for PMC profiling passes")
     ap.add_argument("--producer", type=int, default=0, metavar="POSITIONS",
                     help="instead of the render path, time the Objects gain producer (libearhip group I: point source "
                          "+ polar extent panners) on this many (object, metadata block) positions with random extents, "
-                         "device pointers; prints its own JSON line with a CPU baseline (the oracle on a sample)")
+                         "device pointers; prints its own JSON line (--full: with a CPU baseline and parity, the oracle on a sample)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path computed in its last step (the loudspeaker outputs; "
                          "refbench: the interpolator's outputs; --producer: the direct and diffuse gains) as DIR/<name>.npy, "
@@ -486,9 +516,9 @@ def main():
             native_comm = None
             native_note = "earhip_comm_create failed on a rank" + (f" ({err})" if err else "") + ": torch.distributed exchange"
     # what RCCL itself reports (every rank's count / device, gathered on rank 0) and the link rate it gives a 50 MB
-    # ncclSend / ncclRecv pair per rank — the exchange model below uses THAT, not an assumed figure
+    # ncclSend / ncclRecv pair per rank — the exchange model below uses THAT, not an assumed figure (--full)
     rccl_info, link_measured = None, None
-    if native_comm is not None:
+    if native_comm is not None and args.full:
         mine = native_comm.info()
         infos = [None] * world
         dist.all_gather_object(infos, mine)
@@ -748,7 +778,7 @@ def main():
     # multi-rank self-check (outside the timed region, all ranks take part): the slice this rank
     # owns after the reduce-scatter equals the sum of all ranks' partial outputs
     exchange_err, exchange_repeat_identical, lead_check = None, None, None
-    if world > 1 and wl.time_sharded:
+    if args.full and world > 1 and wl.time_sharded:
         # time sharding's own check: the rank's blocks after ONE lead block equal the same blocks after THREE (the state a
         # lead block leaves is the stream's: nothing older than one block reaches a block's output)
         far = wl.lead + 2  # (the second render starts two blocks further back)
@@ -767,7 +797,7 @@ def main():
             err = torch.zeros(1, device=dev, dtype=torch.float64)
         dist.all_reduce(err, op=dist.ReduceOp.MAX)
         lead_check = float(err.item())
-    if world > 1 and not wl.time_sharded and (backend == "nccl" or os.environ.get("EARHIP_BENCH_CHECK") == "force"):
+    if args.full and world > 1 and not wl.time_sharded and (backend == "nccl" or os.environ.get("EARHIP_BENCH_CHECK") == "force"):
         # (on the LAST chunk of the last step: the buffers of its exchange slot still hold it)
         w = min(wl.clen, 4096)
         last = (args.steps - 1) % 2
@@ -845,9 +875,9 @@ def main():
     value = M_total * total / t_step / 1e6
     rtf = (total / SAMPLE_RATE) / t_step
 
-    # weak-scaling companion figure (N > 1): --objects per rank, short run, same line
+    # weak-scaling companion figure (N > 1, --full): --objects per rank, short run, same line
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.stream_only:
+    if args.full and world > 1 and args.scaling == "strong" and not args.stream_only:
         ww = Workload(cfg["objects"], cfg["hoa"], "weak", seed_base=100)
         wsteps = max(3, min(args.steps, 10))
         wdt, _ = ww.timed(wsteps, 2)
@@ -857,10 +887,10 @@ def main():
         ww.close()
         del ww
 
-    # the other decompositions of the same scene, short runs in the same line (N > 1: the first contact with a multi-GPU
+    # the other decompositions of the same scene, short runs in the same line (N > 1, --full: the first contact with a multi-GPU
     # node then measures all three)
     other_modes = None
-    if world > 1 and args.scaling == "strong" and not args.stream_only and T % world == 0:
+    if args.full and world > 1 and args.scaling == "strong" and not args.stream_only and T % world == 0:
         other_modes = {}
         for mode in ("objects", "objects-nogather", "time"):
             if mode == args.shard:
@@ -903,7 +933,9 @@ def main():
             exchange_info["model"] = exchange_model(args.shard, world, n_pad, total, t_comp, link, wl.nch)
             exchange_info["model"]["measured_ms_per_step"] = round(t_step * 1e3, 4)
             exchange_info["model"]["link_rate_source"] = ("EARHIP_XGMI_GBPS" if link_env else "measured at start-up: exchange.rccl.link_probe"
-                                                          if link_measured else "assumed (no native communicator to probe with)")
+                                                          if link_measured else "assumed (the link is probed under --full only)"
+                                                          if native_comm is not None and not args.full else
+                                                          "assumed (no native communicator to probe with)")
             exchange_info["model"]["note"] = "compute = this rank's kernels (HIP events); the exchange figures are a model"
         # what the fused chain itself moves: K1's bytes, plus (two buses) K2 reading the buses back and writing the outputs
         fused_b = gain_b + (4 * (K * N * B) + 4 * N * B + 2 * 4 * N * 255 / max(T, 1) if K == 2 else 0)
@@ -927,10 +959,10 @@ def main():
                             l2_requests = int(128 * nreq / k1_launches)
             except Exception:
                 traffic = None
-        # what a kernel that only reads gets out of this box, measured in this run: the 100 % mark
+        # what a kernel that only reads gets out of this box, measured in this run: the 100 % mark (--full)
         peak_measured = None
         try:
-            if total % 256 == 0 and wl.in_stride % 256 == 0 and M >= 32:
+            if args.full and total % 256 == 0 and wl.in_stride % 256 == 0 and M >= 32:
                 ms_lin, ms_rows = ctx.read_bandwidth(wl.x_full.data_ptr(), M, wl.in_stride, total, reps=5)
                 peak_measured = {"linear_read_GBps": round(M * wl.in_stride * 4 / ms_lin / 1e6, 1),
                                  "row_pattern_read_GBps": round(M * total * 4 / ms_rows / 1e6, 1),
@@ -1026,7 +1058,7 @@ def main():
 
         # ---- distribution over steps: each step between its own pair of events on the launch stream
         # (the events cost the GPU a few us of idle time per step: these are not the headline figure)
-        if world == 1 and not args.stream_only and not args.brief:
+        if args.full and world == 1 and not args.stream_only and not args.brief:
             n_ev = max(10, min(args.steps, 100))
             evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
             for i, (e0, e1) in enumerate(evs):
@@ -1041,7 +1073,7 @@ def main():
 
         # ---- the same workload on the exact-f32 gain kernels (the default kernel splits f32 operands into
         # two f16 pieces; these do not): f32 MFMA and strict VALU (libear's arithmetic, bit-identical)
-        if world == 1 and not args.stream_only and not args.strict and not args.brief:
+        if args.full and world == 1 and not args.stream_only and not args.strict and not args.brief:
             keep = os.environ.get("EARHIP_MFMA")
             os.environ["EARHIP_MFMA"] = "1"
             try:
@@ -1081,7 +1113,7 @@ def main():
         # ---- block mode (the latency figure): ONE block per call through the host-pointer
         # entry point, i.e. including H2D of the inputs, K0/K1/K2 and D2H of the outputs.  Reported
         # beside the stream-mode value, never as `value`.
-        if world == 1 and not args.stream_only and not args.brief:
+        if args.full and world == 1 and not args.stream_only and not args.brief:
             rb = wl.renderer(ctx, max_blocks=1, npoints=34)
             import ctypes
             xb = np.ascontiguousarray(wl.x[:, :B].cpu().numpy())
@@ -1127,7 +1159,7 @@ def main():
         # calls (src/dsp/variable_block_size_impl.cpp:44-81: `const float *const *in, float *const *out`) — PCIe-inclusive,
         # never `value`.  The call runs as a pipeline of time chunks (H2D / kernels / D2H on three streams); the 100 % mark is
         # what a plain hipMemcpyAsync of the same bytes from the same kind of memory takes, measured here.
-        if world == 1 and not args.stream_only and not args.brief and M >= 16:
+        if args.full and world == 1 and not args.stream_only and not args.brief and M >= 16:
             hs = {"what": "earhip_render_process (host channel pointers: staging or strided DMA, H2D, K0-K2, D2H, sync) in calls of "
                           "64 and 256 blocks; frac = input bytes per second over the measured H2D rate of a plain copy from the same memory",
                   "never_value": True, "calls": []}
@@ -1186,7 +1218,7 @@ def main():
         # ---- parity gate on the TIMED output: every step starts from reset(0), so the first blocks of
         # the buffer the last timed step wrote are the first blocks of the stream, produced by the very
         # launch plan that was timed; the CPU oracle renders the same blocks.  Per channel.
-        if not args.stream_only and (world == 1 or backend == "nccl"):
+        if args.full and not args.stream_only and (world == 1 or backend == "nccl"):
             import _oracle  # the checker; used only below (parity gate and cpu_baseline)
             nb = 4
             last = (args.steps - 1) % 2
@@ -1270,7 +1302,7 @@ def main():
             par["pass"] = bool(par["max_channel_rel_rms_vs_cpu"] <= 1e-6 and f64_ok and all(w.get("finite", True) for w in windows))
 
         # ---- CPU baseline: the scalar restatement on this host, bounded sample -----------------
-        if world == 1 and args.cpu_blocks > 0 and not args.stream_only and not args.brief:
+        if args.full and world == 1 and args.cpu_blocks > 0 and not args.stream_only and not args.brief:
             import _oracle
             cb = min(args.cpu_blocks, T)
             xc = wl.x[:, :cb * B].cpu().numpy()
@@ -1337,10 +1369,10 @@ def main():
                 "value_sharded_threads": round(mt, 1), "threads": nthreads,
                 "gain_stage_forms_Msamples_per_s": forms or None,
                 "cpu_model": cpu_model(), "host_cpus": os.cpu_count()}
-        # ---- the other workloads in the same record (default invocation only): short runs of the other BASELINE
+        # ---- the other workloads in the same record (default invocation with --full only): short runs of the other BASELINE
         # configurations and of the scenes whose curves take the other gain kernels, each a child process of its own
         # (`--brief`: timed steps between barriers exactly as above, per-kernel events, parity gate on its own timed buffer)
-        default_call = (world == 1 and args.config == "C4" and args.scene == "dense" and not args.strict and not args.brief
+        default_call = (args.full and world == 1 and args.config == "C4" and args.scene == "dense" and not args.strict and not args.brief
                         and not args.stream_only and not args.no_secondary and args.row_pad == 256
                         and all(getattr(args, k) is None for k in ("objects", "hoa", "blocks", "block_size", "layout", "buses")))
         if default_call:
@@ -1387,11 +1419,11 @@ SECONDARY = (("C2", ["--config", "C2"]), ("C3", ["--config", "C3"]), ("C5", ["--
 
 
 def secondary_runs(steps):
-    """the `secondary` array of the default line: every entry one `bench.py --brief` child (a fresh process: its own context,
+    """the `secondary` array of the --full line: every entry one `bench.py --full --brief` child (a fresh process: its own context,
     scene and buffers; this process keeps the GPU but is idle meanwhile), reduced to the figures that matter"""
     out = []
     for name, extra in SECONDARY:
-        cmd = [sys.executable, os.path.abspath(__file__), "--brief", "--no-secondary", "--steps", str(steps), "--warmup", "20",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--brief", "--no-secondary", "--steps", str(steps), "--warmup", "20",
                "--kernel-timing-every", "4"] + extra
         t0 = time.perf_counter()
         entry = {"workload": name, "args": " ".join(extra)}

@@ -1,5 +1,5 @@
-"""bench.py itself, at reduced stream lengths: every BASELINE configuration produces a complete line
-(roofline + cpu_baseline + parity on the timed output, per channel), and the multi-rank control flow
+"""bench.py itself, at reduced stream lengths: a plain run prints the headline line alone, every BASELINE configuration
+produces a complete --full line (roofline + cpu_baseline + parity on the timed output, per channel), and the multi-rank control flow
 (object sharding, ragged channel ownership, the exchange, the self-check) runs with several ranks
 sharing the one GPU of the box over gloo.  Each run is a fresh child process (torchrun for N > 1)."""
 import json
@@ -76,9 +76,24 @@ def run_bench(args, nproc=1, env=None):
     return json.loads(lines[0])
 
 
+def test_plain_run_prints_the_headline_alone(tmp_path):
+    """without --full a run times its steps, writes --dump-outputs and prints the headline fields; none of the legs that
+    --full adds (parity gate, CPU baseline, other precisions, block mode, host-pointer calls, per-step events, the read
+    bandwidth probe, the secondary workloads) runs"""
+    import numpy as np
+    line = run_bench(["--blocks", "64", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["metric"] == "Msamples/s" and line["unit"] == "Msamples/s" and line["higher_is_better"] is True
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 4 and line["dtype"].startswith("f32")
+    assert line["kernels_ms"]["gain_mix"] > 0 and line["roofline"]["peak_measured"] is None
+    moved = {"parity", "cpu_baseline", "value_f32_exact", "value_strict", "block_mode", "host_stream", "step_ms", "secondary"}
+    assert not moved & set(line), sorted(moved & set(line))
+    out = np.load(tmp_path / "outputs.npy")
+    assert out.shape == (line["config"]["channels"], 64 * line["config"]["block"]) and np.isfinite(out).all()
+
+
 @pytest.mark.parametrize("config", ["C2", "C3", "C4", "C5"])
 def test_every_baseline_config_gives_a_complete_parity_checked_line(config):
-    line = run_bench(["--config", config, "--blocks", "64", "--steps", "4", "--warmup", "1", "--cpu-blocks", "4"])
+    line = run_bench(["--full", "--config", config, "--blocks", "64", "--steps", "4", "--warmup", "1", "--cpu-blocks", "4"])
     assert line["metric"] == "Msamples/s" and line["n_gpus"] == 1 and line["value"] > 0
     assert line["config"]["baseline_config"] == config
     assert line["dtype"].startswith("f32")
@@ -98,7 +113,7 @@ def test_every_baseline_config_gives_a_complete_parity_checked_line(config):
 def test_one_gpu_line_is_the_same_measurement_with_or_without_a_shard_mode():
     """`--gpus 1 --shard objects` is the plain one-GPU line: the same workload, launch plan and parity gate, no exchange object,
     and the same figure up to run-to-run noise (a first multi-GPU contact reads its N = 1 point against the headline)."""
-    common = ["--blocks", "256", "--steps", "8", "--warmup", "2", "--cpu-blocks", "0", "--brief"]
+    common = ["--full", "--blocks", "256", "--steps", "8", "--warmup", "2", "--cpu-blocks", "0", "--brief"]
     plain = run_bench(common)
     sharded = run_bench(["--shard", "objects"] + common)
     for line in (plain, sharded):
@@ -111,8 +126,8 @@ def test_one_gpu_line_is_the_same_measurement_with_or_without_a_shard_mode():
 
 def test_default_invocation_measures_libears_own_calling_convention():
     """the host-pointer stream calls (earhip_render_process from pageable and from device-reachable rows, 64 blocks per call here)
-    are part of the line: rate, the measured H2D rate beside it, and their outputs held against the device-resident render"""
-    line = run_bench(["--blocks", "64", "--steps", "4", "--warmup", "1", "--cpu-blocks", "4", "--no-secondary"])
+    are part of the --full line: rate, the measured H2D rate beside it, and their outputs held against the device-resident render"""
+    line = run_bench(["--full", "--blocks", "64", "--steps", "4", "--warmup", "1", "--cpu-blocks", "4", "--no-secondary"])
     hs = line["host_stream"]
     assert hs["pass"] and hs["h2d_GBps_measured"]["pinned"] > 1.0
     srcs = {(c["source"], c["blocks_per_call"]) for c in hs["calls"]}
@@ -132,7 +147,7 @@ def test_scenes_at_the_headline_size_pass_the_parity_gate_of_their_own_launch_pl
     if forced and scene == "moving" and os.environ.get("EARHIP_P2_PAIRS") == "1":
         pytest.skip("paired lists forced onto always-ramping curves: not the layout the library picks for them (its pair "
                     "chunks do not sum per chunk: 1.0e-6 from the CPU path at this size)")
-    line = run_bench(["--scene", scene, "--blocks", "512", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"])
+    line = run_bench(["--full", "--scene", scene, "--blocks", "512", "--steps", "2", "--warmup", "1", "--cpu-blocks", "0"])
     if not forced:
         assert kernel in line["roofline"]["kernel"], line["roofline"]["kernel"]
         assert line["roofline"]["plan"]["tile_samples"] == tile, line["roofline"]["plan"]
@@ -145,7 +160,7 @@ def test_scenes_at_the_headline_size_pass_the_parity_gate_of_their_own_launch_pl
 def test_multi_rank_control_flow_on_one_gpu_over_gloo(nproc, layout):
     """ranks share cuda:0, the collective runs over gloo: sharding, ragged channel ownership (10 channels
     over 3 ranks), the asynchronous exchange and its self-check (owned slice == all-reduce of the partials)"""
-    line = run_bench(["--objects", "96", "--layout", layout, "--blocks", "32", "--steps", "3", "--warmup", "1",
+    line = run_bench(["--full", "--objects", "96", "--layout", layout, "--blocks", "32", "--steps", "3", "--warmup", "1",
                       "--cpu-blocks", "0"], nproc=nproc,
                      env={"EARHIP_BENCH_BACKEND": "gloo", "EARHIP_BENCH_CHECK": "force"})
     assert line["n_gpus"] == nproc and line["scaling"] == "strong"
@@ -162,7 +177,7 @@ def test_multi_rank_control_flow_on_one_gpu_over_gloo(nproc, layout):
 def test_time_sharding_on_one_gpu_over_gloo(nproc):
     """--shard time: every rank renders ALL objects for its T / G blocks behind one lead block; no exchange.  The line's
     own check: a rank's blocks after one lead block are bit-identical to the same blocks after three."""
-    line = run_bench(["--objects", "96", "--blocks", "48", "--steps", "3", "--warmup", "1", "--cpu-blocks", "0", "--shard", "time"],
+    line = run_bench(["--full", "--objects", "96", "--blocks", "48", "--steps", "3", "--warmup", "1", "--cpu-blocks", "0", "--shard", "time"],
                      nproc=nproc, env={"EARHIP_BENCH_BACKEND": "gloo"})
     assert line["n_gpus"] == nproc and line["config"]["shard"] == "time"
     assert line["config"]["objects_total"] == 96 and line["config"]["objects_per_gpu"] == 96
@@ -176,7 +191,7 @@ def test_time_sharding_on_one_gpu_over_gloo(nproc):
 def test_objects_without_gather_on_one_gpu_over_gloo():
     """--shard objects-nogather: the reduce-scatter alone (the consumer takes the bus channel-sharded); the exchange
     model counts one slice instead of two; the same partials exchanged twice give bit-identical slices"""
-    line = run_bench(["--objects", "96", "--blocks", "32", "--steps", "3", "--warmup", "1", "--cpu-blocks", "0",
+    line = run_bench(["--full", "--objects", "96", "--blocks", "32", "--steps", "3", "--warmup", "1", "--cpu-blocks", "0",
                       "--shard", "objects-nogather"], nproc=2, env={"EARHIP_BENCH_BACKEND": "gloo", "EARHIP_BENCH_CHECK": "force"})
     assert line["config"]["shard"] == "objects-nogather"
     assert line["exchange"]["gather_bytes_into_root"] == 0 and line["exchange"]["root"] is None
@@ -194,7 +209,7 @@ def test_plain_invocation_with_gpus_2_launches_its_own_ranks():
     runs one rank per GPU on libearhip's own RCCL communicator."""
     e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     e["EARHIP_BENCH_CHECK"] = "force"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--objects", "128", "--blocks", "32", "--steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--objects", "128", "--blocks", "32", "--steps", "3",
            "--warmup", "1", "--cpu-blocks", "0"]
     res = _run_with_one_retry(cmd, e, 300)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -215,7 +230,7 @@ def test_plain_invocation_with_gpus_2_launches_its_own_ranks():
 def test_refbench_line():
     """bench.py --config refbench: the reference's own benchmark shape (32 -> 24 channels, 1024 samples, a matrix point
     every 100 samples) in block and stream mode with the CPU path beside it, parity-gated"""
-    line = run_bench(["--config", "refbench", "--steps", "5", "--warmup", "2"])
+    line = run_bench(["--full", "--config", "refbench", "--steps", "5", "--warmup", "2"])
     assert line["config"]["baseline_config"] == "refbench" and line["value"] > 0
     assert line["block_mode"]["ms_per_call"] > 0 and line["cpu_baseline"]["ms_per_call"] > 0
     assert line["parity"]["pass"] and line["parity"]["block_rel_rms_vs_cpu"] <= 1e-6
@@ -224,19 +239,19 @@ def test_refbench_line():
 
 def test_producer_line():
     """bench.py --producer: the Objects gain producer with extent through device pointers, parity-gated"""
-    line = run_bench(["--producer", "20000", "--steps", "3", "--warmup", "1"])
+    line = run_bench(["--full", "--producer", "20000", "--steps", "3", "--warmup", "1"])
     assert line["unit"] == "Mpositions/s" and line["value"] > 0
     assert line["parity"]["pass"] and line["parity"]["max_rel_norm"] <= 1e-5
     assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["kind"] == "port"
 
 
 def test_default_line_carries_the_other_workloads():
-    """`python bench.py` as the driver runs it (fewer steps here): the headline line carries a `secondary` array — the other
+    """`python bench.py --full` (fewer steps here): the headline line carries a `secondary` array — the other
     BASELINE configurations and the scenes of the other gain kernels, each timed in a process of its own with the parity gate
     on its own timed buffer"""
     if any(os.environ.get(k) is not None for k in ("EARHIP_P2_PAIRS", "EARHIP_P2_TILE", "EARHIP_H2_TILE", "EARHIP_MFMA", "EARHIP_HINGE", "EARHIP_HG_TILE")):
         pytest.skip("kernel forced")
-    line = run_bench(["--steps", "6", "--warmup", "2", "--cpu-blocks", "4"])
+    line = run_bench(["--full", "--steps", "6", "--warmup", "2", "--cpu-blocks", "4"])
     sec = {e["workload"]: e for e in line["secondary"]}
     assert {"C2", "C3", "C5", "C4 adm", "C4 moving", "C4 bursty"} <= set(sec), sorted(sec)
     for name, e in sec.items():
@@ -251,7 +266,7 @@ def test_dump_outputs_writes_the_last_timed_step_and_repeats(tmp_path):
     """--dump-outputs DIR: the loudspeaker outputs of the last timed step as DIR/outputs.npy (float32, [channels][samples]); the
     same arguments give the same inputs, so a second run writes the same outputs; --steps is the number of timed steps"""
     import numpy as np
-    common = ["--blocks", "64", "--steps", "5", "--warmup", "1", "--cpu-blocks", "0", "--brief"]
+    common = ["--full", "--blocks", "64", "--steps", "5", "--warmup", "1", "--cpu-blocks", "0", "--brief"]
     got = []
     for run in ("a", "b"):
         line = run_bench(common + ["--dump-outputs", str(tmp_path / run)])

@@ -4,7 +4,7 @@
 N=${1:-10}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 for i in $(seq 1 $N); do
-  python3 $ROOT/bench.py --config C2 --brief --steps 60 --warmup 10 "$@" 2>/dev/null | python3 -c "
+  python3 $ROOT/bench.py --full --config C2 --brief --steps 60 --warmup 10 "$@" 2>/dev/null | python3 -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{'):

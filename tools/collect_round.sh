@@ -1,16 +1,17 @@
 #!/bin/bash
-# Collect the bench lines of every configuration / scene for profiles/ (on the GPU box):
-#   bash tools/collect_round.sh <tag>     -> gpurun_out/<tag>_bench_<name>.json
+# Collect the --full bench lines of every configuration / scene for profiles/ (on the GPU box):
+#   bash tools/collect_round.sh <tag> [dir]     -> <dir>/<tag>_bench_<name>.json (dir: bench_out by default)
 TAG=${1:-r06}
+OUT=${2:-bench_out}
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
-cd $ROOT && mkdir -p gpurun_out
+cd $ROOT && mkdir -p $OUT
 run() { # name, bench args...
   local name=$1; shift
-  timeout 400 python bench.py "$@" 2> gpurun_out/${TAG}_bench_${name}.err | tail -1 > gpurun_out/${TAG}_bench_${name}.json
-  python tools/benchline.py < gpurun_out/${TAG}_bench_${name}.json | sed "s/^/$name: /"
+  timeout 400 python bench.py --full "$@" 2> $OUT/${TAG}_bench_${name}.err | tail -1 > $OUT/${TAG}_bench_${name}.json
+  python tools/benchline.py < $OUT/${TAG}_bench_${name}.json | sed "s/^/$name: /"
 }
 # the driver's entry point first: a round must not end with smoke() red
-python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.txt 2>&1 && echo "smoke: ok" || { echo "smoke: FAILED"; tail -5 gpurun_out/${TAG}_smoke.txt; }
+python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1 && echo "smoke: ok" || { echo "smoke: FAILED"; tail -5 $OUT/${TAG}_smoke.txt; }
 run C4
 run C2 --config C2
 run C3 --config C3

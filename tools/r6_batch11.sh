@@ -6,5 +6,5 @@ EARHIP_LIB=$PWD/libear_amd/lib_bprof/libearhip.so python tools/build_phases.py m
 line() { python -c "
 import json,sys; d=json.load(open('$1')); print('$2', d['value'], d['ms_per_step'], d['kernels_ms'], d['roofline']['frac'], d['parity']['pass'], d['parity']['max_channel_rel_rms_vs_cpu'])"; }
 for sc in adm moving bursty-moving bursty-adm; do
-  python bench.py --scene $sc --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/$sc.json; line $OUT/$sc.json "$sc"
+  python bench.py --full --scene $sc --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/$sc.json; line $OUT/$sc.json "$sc"
 done

@@ -5,6 +5,6 @@ line() { python -c "
 import json,sys; d=json.load(open('$1')); print('$2', d['value'], d['ms_per_step'], d['kernels_ms'], d['roofline']['frac'], d['parity']['pass'], d['parity']['max_channel_rel_rms_vs_cpu'])"; }
 for rep in 1 2; do
 for cfg in C4 C2 C3 C5; do
-  python bench.py --config $cfg --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/$cfg.json; line $OUT/$cfg.json "$cfg"
+  python bench.py --full --config $cfg --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/$cfg.json; line $OUT/$cfg.json "$cfg"
 done
 done

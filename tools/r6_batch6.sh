@@ -8,12 +8,12 @@ import json,sys; d=json.load(open('$1')); print('$2', d['value'], d['ms_per_step
 for rep in 1 2; do
   for lib in default fold; do
     [ $lib = fold ] && export EARHIP_LIB=$PWD/libear_amd/lib_fold/libearhip.so || unset EARHIP_LIB
-    python bench.py --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c4_$lib.json; line $OUT/c4_$lib.json "C4 k2=$lib"
-    python bench.py --config C3 --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c3_$lib.json; line $OUT/c3_$lib.json "C3 k2=$lib"
+    python bench.py --full --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c4_$lib.json; line $OUT/c4_$lib.json "C4 k2=$lib"
+    python bench.py --full --config C3 --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c3_$lib.json; line $OUT/c3_$lib.json "C3 k2=$lib"
   done
 done
 unset EARHIP_LIB
-python bench.py --config C5 --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c5.json; line $OUT/c5.json "C5"
+python bench.py --full --config C5 --brief --steps 40 --warmup 10 2>/dev/null | tail -1 > $OUT/c5.json; line $OUT/c5.json "C5"
 for lib in default fold; do
   [ $lib = fold ] && export EARHIP_LIB=$PWD/libear_amd/lib_fold/libearhip.so || unset EARHIP_LIB
   echo "flakiness, k2=$lib:"

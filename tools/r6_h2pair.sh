@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for cfg in "--config C4" "--config C2" "--config C3" "--config C5" "--scene bursty" "--objects 128"; do
   for pair in 0 1; do
-    EARHIP_H2_PAIR=$pair python bench.py $cfg --steps 100 --warmup 20 --no-secondary --brief 2>/dev/null | tail -1 | python -c "
+    EARHIP_H2_PAIR=$pair python bench.py --full $cfg --steps 100 --warmup 20 --no-secondary --brief 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$cfg pair=$pair', d['ms_per_step'], d['kernels_ms'], d['roofline']['frac'], d['roofline']['plan']['form'], d['parity']['max_channel_rel_rms_vs_cpu'], d['parity']['pass'])"
   done
