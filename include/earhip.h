@@ -591,7 +591,8 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
  *   EARHIP_PCM_S32: (float)x rounded to nearest even, then * 2^-31
  *   EARHIP_PCM_F32: the bits as given (NaN payloads and denormals included)
  * out_interleaved == 0: out = n_out planar float rows, as earhip_render_process; != 0: out[0] is [frames][n_out]
- * interleaved float32 (one contiguous transfer back).
+ * interleaved float32 (one contiguous transfer back; for interleaved s16 / s24 / s32 frames out, converted on the device,
+ * see earhip_render_process_frames_pcm below).
  * The result is bit-identical to earhip_render_process on the converted planar rows held in the same kind of memory
  * (pageable, or earhip_host_alloc / _register): both take their chunk plan — short call or pipeline, chunk boundaries —
  * from the same function of the FLOAT-EQUIVALENT size of the call (n_objects * frames * 4 bytes; 16 MB and more: a
@@ -626,6 +627,72 @@ int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *f
 int earhip_render_process_frames_device(earhip_render *r, size_t nblocks, const void *frames_dev,
                                         earhip_pcm_format fmt, int frame_channels, int first_channel,
                                         float *out_dev, size_t out_stride, int out_interleaved);
+/* Interleaved PCM frames OUT as well: file to file in one call.  The render's float32 output samples are converted on the
+ * device, so the bus carries 2 or 3 bytes per output sample too and the caller has no scale / round / saturate / pack pass;
+ * on their way out the device keeps a per-channel peak and a count of clipped samples (earhip_render_output_levels).
+ *
+ * The conversion, exactly (a caller can reproduce it bit for bit).  x is the render's float32 output sample — the one
+ * earhip_render_process_frames hands back for the same call —, every step below is ONE float32 operation rounded to
+ * nearest even, and "rint" rounds to the nearest integer, ties to even:
+ *   EARHIP_PCM_S16: p = x * 2^15 (exact short of overflow); v = p, or with dither v = p + d (one further float32 rounding:
+ *                   the multiply and the add are NOT contracted into an fma); q = rint(v) saturated to [-32768, 32767];
+ *                   stored as 2 bytes, little-endian
+ *   EARHIP_PCM_S24: q = rint(x * 2^23) saturated to [-2^23, 2^23 - 1]; 3 bytes, little-endian, no padding
+ *   EARHIP_PCM_S32: q = rint(x * 2^31); x * 2^31 >= 2^31 gives 2147483647, < -2^31 gives -2147483648 (compared in float
+ *                   before any integer conversion: 2^31 does not fit); 4 bytes, little-endian
+ *   EARHIP_PCM_F32: the bits of x (what out_interleaved != 0 of earhip_render_process_frames gives); 4 bytes
+ * NaN is stored as 0 and counts as a clipped sample; +-inf saturates and counts as clipped.  A sample is CLIPPED when
+ * saturation changed it (the rounded value lay outside the format's range: 1.0 -> 32767 is clipped, -1.0 -> -32768 is not)
+ * or it was NaN.  F32 output never clips.
+ * Dither (earhip_pcm_out.dither = 1): TPDF over (-1, 1) LSB, for EARHIP_PCM_S16 only — float32 accumulation has 24
+ * significant bits, dithering a 24- or 32-bit word made from it would shape nothing; with another format it is
+ * EARHIP_INVALID_ARGUMENT.  d = ((h & 0xFFFF) + (h >> 16) - 65535) * 2^-16 (an exact float32), where h is a 32-bit hash
+ * of (seed, sample time t, output channel n), in uint32 arithmetic (wrapping):
+ *   mix(a): a ^= a >> 16; a *= 0x7FEB352D; a ^= a >> 15; a *= 0x846CA68B; a ^= a >> 16
+ *   h = mix(mix(mix(mix(t_lo + 0x9E3779B9) ^ t_hi) + n * 0x85EBCA6B) ^ seed)
+ * t_lo / t_hi: the low and high 32 bits of t as a 64-bit two's complement number.  t is the renderer's own sample clock
+ * (earhip_render_reset sets it; each call advances it by its frames), not an index into the call: the dither of a sample does
+ * not depend on how the stream is cut into calls, on the pipeline's chunks or on the kernel that rendered it, and a second
+ * renderer with another seed (another rank, another layout) is uncorrelated.  Off by default (a zeroed earhip_pcm_out
+ * but for its format).
+ *
+ * out_frames: nblocks * block_size frames of exactly n_out samples of out->format, no padding.  The host form takes its chunk
+ * plan from the same function of the float-equivalent INPUT size as earhip_render_process_frames, so the float samples that
+ * reach the converter are bit-identical to those that call returns for frames and outputs in the same kind of memory.  In a
+ * long call chunk c is converted on the context's stream behind its render, and its packed bytes go back on the third stream
+ * while chunk c + 1 renders: into out_frames directly when it is device-reachable (earhip_host_alloc / _register), else
+ * through pinned staging and a host memcpy of a contiguous byte range.
+ * Memory, made at the first call of this form and kept (grown by a later call of a wider format): max_blocks * block_size *
+ * n_out * sample size bytes on the device, and as many pinned at the first call whose out_frames is pageable (a renderer that
+ * only ever writes into device-reachable frames has no pinned staging); 768 * n_out bytes of levels (64 copies, so that the waves of a launch do not meet on n_out addresses).
+ * EARHIP_INVALID_ARGUMENT, nothing written: everything earhip_render_process_frames refuses, a NULL out / out_frames, an
+ * unknown out->format, dither other than 0 / 1 or with a format other than S16, out_frames (out_dev) of s16 / s32 / f32 not
+ * aligned to the sample size (s24 may start at any byte); in the device form out_frame_bytes < out_first_byte + n_out *
+ * sample size, or out_first_byte / out_frame_bytes not a multiple of the sample size for s16 / s32 / f32.
+ * Out of scope: PCM out from planar float rows (earhip_render_process: libear's callers there want floats), noise-shaped
+ * dither, big-endian or padded (s24 in 4 bytes) containers, and any file I/O. */
+typedef struct earhip_pcm_out {
+  earhip_pcm_format format; /* EARHIP_PCM_S16 | _S24 | _S32 | _F32 */
+  int dither;               /* 0 | 1 (S16 only) */
+  uint32_t seed;            /* of the dither hash */
+} earhip_pcm_out;
+int earhip_render_process_frames_pcm(earhip_render *r, size_t nblocks, const void *frames,
+                                     earhip_pcm_format fmt, int frame_channels, int first_channel,
+                                     void *out_frames, const earhip_pcm_out *out);
+/* Device memory to device memory.  out_frame_bytes is the distance between output frames; the renderer's samples are bytes
+ * [out_first_byte, out_first_byte + n_out * sample size) of each, and every other byte of out_dev is left as it was — never
+ * written, never read and written back —, so several renderers may fill their channels of the same frames at the same time.
+ * Bit-identical to the conversion above of what earhip_render_process_frames_device gives.  Enqueues on the context's stream;
+ * does not synchronise (but for the first call of this form, which makes the renderer's buffers). */
+int earhip_render_process_frames_pcm_device(earhip_render *r, size_t nblocks, const void *frames_dev,
+                                            earhip_pcm_format fmt, int frame_channels,
+                                            int first_channel, void *out_dev, size_t out_frame_bytes,
+                                            size_t out_first_byte, const earhip_pcm_out *out);
+/* Per output channel, since these numbers were last zeroed: peak[n_out] = the largest |x| that went through a PCM-out call
+ * (the float32 render sample, before scaling and dither; NaN ignored, so +inf is possible), clipped[n_out] = the number of
+ * clipped samples.  Synchronises the stream.  reset != 0: zero them afterwards.  earhip_render_reset zeroes them too.  The
+ * float calls (earhip_render_process*, _process_frames) neither read nor change them. */
+int earhip_render_output_levels(earhip_render *r, float *peak, uint64_t *clipped, int reset);
 /* Kernel timing (HIP events on the context's stream around each launch).
  * enable != 0 starts collecting and zeroes the counters; enable = n > 1 times
  * every n-th process call only, starting with the next one (each timed call

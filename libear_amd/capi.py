@@ -50,7 +50,12 @@ class RenderConfig(C.Structure):
                 ("delay", C.c_int), ("max_blocks", C.c_int)]
 
 
-PROCESS_FUNC = C.CFUNCTYPE(C.c_int, pp_f32, pp_f32, C.c_void_p)
+class PcmOut(C.Structure):
+    """earhip_pcm_out: the output format of Renderer.process_frames_pcm"""
+    _fields_ = [("format", C.c_int), ("dither", C.c_int), ("seed", C.c_uint32)]
+
+
+PROCESS_FUNC =C.CFUNCTYPE(C.c_int, pp_f32, pp_f32, C.c_void_p)
 
 _lib = None
 
@@ -849,6 +854,45 @@ class Renderer:
         check(load().earhip_render_process_frames_device(self.h, C.c_size_t(nblocks), C.c_void_p(frames_ptr), C.c_int(code),
                                                          C.c_int(frame_channels), C.c_int(first_channel), C.c_void_p(out_ptr),
                                                          C.c_size_t(out_stride), int(bool(interleaved_out))))
+
+    def process_frames_pcm(self, x, fmt, first_channel=0, out_fmt="s16", dither=False, seed=0):
+        """interleaved PCM frames in (as process_frames) -> interleaved PCM frames out, converted on the device: int16 's16' /
+        int32 's32' / float32 'f32' [frames][N], or uint8 [frames][3 N] 's24'; dither: TPDF, 's16' only, a function of
+        (seed, sample clock, channel) (include/earhip.h: earhip_render_process_frames_pcm)."""
+        x = np.ascontiguousarray(x)
+        _, dtype, cols = pcm_format(out_fmt)
+        out = np.empty((x.shape[0], self.N * cols), dtype)
+        return self.process_frames_pcm_into(x, out, fmt, first_channel, out_fmt, dither, seed)
+
+    def process_frames_pcm_into(self, x, out, fmt, first_channel=0, out_fmt="s16", dither=False, seed=0):
+        """the same with the caller's own arrays, used as they are (Context.pinned_array: DMA both ways, no staging copies)"""
+        code, nblocks, channels = self._frames_shape(x, fmt)
+        ocode, dtype, cols = pcm_format(out_fmt)
+        assert out.dtype == dtype and out.flags["C_CONTIGUOUS"] and out.shape == (nblocks * self.B, self.N * cols), out.shape
+        spec = PcmOut(ocode, int(dither), int(seed) & 0xFFFFFFFF)
+        check(load().earhip_render_process_frames_pcm(self.h, C.c_size_t(nblocks), C.c_void_p(x.ctypes.data), C.c_int(code),
+                                                      C.c_int(channels), C.c_int(first_channel), C.c_void_p(out.ctypes.data),
+                                                      C.byref(spec)))
+        return out
+
+    def process_frames_pcm_device(self, nblocks, frames_ptr, fmt, frame_channels, first_channel, out_ptr, out_frame_bytes,
+                                  out_first_byte=0, out_fmt="s16", dither=False, seed=0):
+        """device pointers; the renderer's samples are bytes [out_first_byte, + N * sample size) of each output frame of
+        out_frame_bytes, every other byte is left alone; enqueues on the context's stream"""
+        code = pcm_format(fmt)[0] if isinstance(fmt, str) else int(fmt)
+        ocode = pcm_format(out_fmt)[0] if isinstance(out_fmt, str) else int(out_fmt)
+        spec = PcmOut(ocode, int(dither), int(seed) & 0xFFFFFFFF)
+        check(load().earhip_render_process_frames_pcm_device(self.h, C.c_size_t(nblocks), C.c_void_p(frames_ptr), C.c_int(code),
+                                                             C.c_int(frame_channels), C.c_int(first_channel), C.c_void_p(out_ptr),
+                                                             C.c_size_t(out_frame_bytes), C.c_size_t(out_first_byte),
+                                                             C.byref(spec)))
+
+    def output_levels(self, reset=False):
+        """(peak float32 [N], clipped uint64 [N]) of the samples that went through the PCM-out calls since these numbers were
+        last zeroed (reset=True zeroes them afterwards; so does reset()): the largest |x| and the saturated samples"""
+        peak, clipped = np.zeros(self.N, np.float32), np.zeros(self.N, np.uint64)
+        check(load().earhip_render_output_levels(self.h, _ptr(peak), C.c_void_p(clipped.ctypes.data), int(bool(reset))))
+        return peak, clipped
 
     def enable_timing(self, on=True):
         """True / 1: time the kernels of every process call; n > 1: of every n-th call; False: stop"""

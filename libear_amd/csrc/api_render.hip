@@ -16,6 +16,7 @@
 #include "curves.h"
 #include "host_gather.h"
 #include "pcm_kernels.h"
+#include "pcm_out_kernels.h"
 #include "fft_kernels.h"
 #include "render_kernels.h"
 
@@ -318,6 +319,13 @@ struct earhip_render {
   PinBuf<unsigned char> p_bytes;
   DevBuf<unsigned char> d_bytes;
   DevBuf<float> d_ilv, d_rows, d_rows_out;
+  // PCM frames out (earhip_render_process_frames_pcm): the packed output frames of a call on the device and pinned (pageable
+  // out_frames only), sized at the first call of that form for max_blocks frames of its format (grown by a call of a wider
+  // format); the levels the conversion kernel keeps, [kLevelSlots][N] each, made (zeroed) with them
+  DevBuf<unsigned char> d_pcm;
+  PinBuf<unsigned char> p_pcm;
+  DevBuf<unsigned> d_peak;
+  DevBuf<unsigned long long> d_clip;
   // timing
   bool timing = false;
   bool last_timed = false;
@@ -380,6 +388,23 @@ struct earhip_render {
     for (int c = 1; c < count; c++)
       if ((uintptr_t)ch[c] - (uintptr_t)ch[c - 1] != step) return 0;
     return ctx->host_reachable(ch[0], step * (count - 1) + sizeof(float) * n) ? (size_t)(step / sizeof(float)) : 0;
+  }
+
+  void reserve_levels() {
+    if (d_peak.p) return;
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    d_peak.alloc_zero((size_t)kLevelSlots * N, ctx->stream);
+    d_clip.alloc_zero((size_t)kLevelSlots * N, ctx->stream);
+  }
+  void zero_levels() {
+    if (!d_peak.p) return;
+    EARHIP_HIP(hipMemsetAsync(d_peak.p, 0, sizeof(unsigned) * kLevelSlots * N, ctx->stream));
+    EARHIP_HIP(hipMemsetAsync(d_clip.p, 0, sizeof(unsigned long long) * kLevelSlots * N, ctx->stream));
+  }
+  void reserve_pcm_out(size_t bytes, bool pinned) {
+    reserve_levels();
+    d_pcm.reserve(bytes);
+    if (pinned) p_pcm.reserve(bytes);
   }
 
   // the chunk plan of a call from host memory (earhip_render_process and _process_frames alike)
@@ -753,6 +778,7 @@ int earhip_render_reset(earhip_render *r, int64_t sample_time) {
     r->ctx->use();
     r->t = sample_time;
     r->fresh = true;  // the next call reads the all-zero state and rewrites its own pair completely
+    r->zero_levels();  // (only a renderer that has made PCM frames has any)
   });
 }
 
@@ -966,6 +992,184 @@ static void launch_rows_to_frames(const float *in, size_t in_stride, int N, size
   EARHIP_HIP(hipGetLastError());
 }
 
+// what the PCM-out forms refuse on top of check_frames_args; returns the output sample size
+static size_t check_pcm_out(const earhip_pcm_out *out) {
+  require(out != nullptr, "out (earhip_pcm_out) must not be NULL");
+  const int So = pcm_sample_bytes(out->format);
+  require(So != 0, "unknown PCM output format");
+  require(out->dither == 0 || out->dither == 1, "dither must be 0 or 1");
+  require(out->dither == 0 || out->format == EARHIP_PCM_S16, "dither is defined for EARHIP_PCM_S16 only");
+  return (size_t)So;
+}
+
+// planar rows [N][in_stride] (samples [0, len), the first at sample clock t0) -> PCM frames: bytes [first_byte, + N * sample size) of
+// each frame of frame_bytes at `out`; levels into peak / clipped [N]; on stream s
+static void launch_rows_to_pcm(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out,
+                               size_t frame_bytes, size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s) {
+  const dim3 grid((unsigned)((len + kOutFrames - 1) / kOutFrames), (unsigned)((N + kOutChans - 1) / kOutChans));
+  PcmOutArgs a;
+  a.in = in; a.in_stride = in_stride; a.N = N; a.len = len; a.out = out; a.frame_bytes = frame_bytes; a.first_byte = first_byte;
+  a.peak = peak; a.clipped = clipped; a.seed = o.seed; a.t0 = (long long)t0;
+  switch (o.format) {
+    case EARHIP_PCM_S16:
+      if (o.dither) hipLaunchKernelGGL((k_rows_to_pcm<kPcmS16, true>), grid, dim3(kOutThreads), 0, s, a);
+      else hipLaunchKernelGGL((k_rows_to_pcm<kPcmS16, false>), grid, dim3(kOutThreads), 0, s, a);
+      break;
+    case EARHIP_PCM_S24: hipLaunchKernelGGL((k_rows_to_pcm<kPcmS24, false>), grid, dim3(kOutThreads), 0, s, a); break;
+    case EARHIP_PCM_S32: hipLaunchKernelGGL((k_rows_to_pcm<kPcmS32, false>), grid, dim3(kOutThreads), 0, s, a); break;
+    default: hipLaunchKernelGGL((k_rows_to_pcm<kPcmF32, false>), grid, dim3(kOutThreads), 0, s, a); break;
+  }
+  EARHIP_HIP(hipGetLastError());
+}
+
+// The host form of both frames calls (arguments checked by the caller).  po == nullptr: earhip_render_process_frames, float outputs
+// through `out`.  po != nullptr: earhip_render_process_frames_pcm: the outputs are interleaved frames of po->format at out_pcm —
+// the interleaved float path with k_rows_to_pcm in the place of k_rows_to_frames and frames of n_out * (sample size) bytes.
+static void process_frames_host(earhip_render *r, size_t nblocks, const void *frames, int fmt, int frame_channels, int first_channel,
+                                float *const *out, int out_interleaved, const earhip_pcm_out *po, void *out_pcm) {
+  earhip_ctx *ctx = r->ctx;
+  ctx->use();
+  const int M = r->M, N = r->N;
+  const size_t S = (size_t)pcm_sample_bytes(fmt);
+  const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
+  const size_t fb = (size_t)frame_channels * S, first_byte = (size_t)first_channel * S, bytes = n * fb;
+  const bool direct = ctx->host_reachable(frames, bytes);  // (device-reachable frames: DMA straight from the caller's buffer)
+  // (the plan of earhip_render_process on rows in the same kind of memory: the same chunks, the same results)
+  const HostChunkPlan plan = r->host_plan(nblocks, direct);
+  float *const out0 = po ? nullptr : out[0];
+  // interleaved outputs, float or PCM, as bytes: a frame is ofb bytes; ilv_host the caller's frames, ilv_dev / ilv_pin ours
+  const size_t ofb = (size_t)N * (po ? (size_t)pcm_sample_bytes(po->format) : sizeof(float));
+  unsigned char *const ilv_host = po ? static_cast<unsigned char *>(out_pcm) : reinterpret_cast<unsigned char *>(out0);
+  const size_t out_st = out_interleaved ? 0 : r->NP <= 1 || !plan.short_call ? r->direct_stride(out, N, n) : 0;
+  const bool out_direct = out_interleaved ? ctx->host_reachable(ilv_host, n * ofb) : out_st != 0;
+  r->d_in.reserve(cap * M);
+  r->d_out.reserve(cap * N);
+  if (po) {
+    r->reserve_pcm_out(cap * ofb, !out_direct);
+  } else {
+    r->p_out.reserve(cap * N);
+    if (out_interleaved) r->d_ilv.reserve(cap * N);
+  }
+  unsigned char *const ilv_dev = po ? r->d_pcm.p : reinterpret_cast<unsigned char *>(r->d_ilv.p);
+  unsigned char *const ilv_pin = po ? r->p_pcm.p : reinterpret_cast<unsigned char *>(r->p_out.p);
+  // planar rows [N][stride] of `len` frames at sample clock t0 -> the interleaved frames at ilv_dev + at * ofb
+  auto launch_interleave = [&](const float *rows, size_t stride, size_t len, size_t at, int64_t t0) {
+    if (po)
+      launch_rows_to_pcm(*po, rows, stride, N, len, ilv_dev + at * ofb, ofb, 0, r->d_peak.p, r->d_clip.p, t0, ctx->stream);
+    else
+      launch_rows_to_frames(rows, stride, N, len, reinterpret_cast<float *>(ilv_dev + at * ofb), N, ctx->stream);
+  };
+  r->d_bytes.reserve(cap * fb + 16);  // (+16: the conversion kernel reads whole dwords)
+  if (!direct) r->p_bytes.reserve(cap * fb);
+  const unsigned char *src = static_cast<const unsigned char *>(frames);
+  r->last_host_chunks = 0;
+  if (plan.short_call) {
+    if (!direct) {
+      std::memcpy(r->p_bytes.p, frames, bytes);
+      src = r->p_bytes.p;
+    }
+    EARHIP_HIP(hipMemcpyAsync(r->d_bytes.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_pcm_to_rows(fmt, r->d_bytes.p, fb, first_byte, M, n, r->d_in.p, n, ctx->stream);
+    if (out_interleaved) {
+      const int64_t t0 = r->t;
+      r->process_device(nblocks, r->d_in.p, n, r->d_out.p, n);
+      launch_interleave(r->d_out.p, n, n, 0, t0);
+      EARHIP_HIP(hipMemcpyAsync(out_direct ? ilv_host : ilv_pin, ilv_dev, n * ofb, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+      // (as earhip_render_process: a single-partition render writes its outputs straight into host memory)
+      const bool direct_out = r->NP <= 1;
+      float *dst = out_st ? out0 : direct_out ? r->p_out.p : r->d_out.p;
+      r->process_device(nblocks, r->d_in.p, n, dst, out_st ? out_st : n);
+      if (!out_st && !direct_out)
+        EARHIP_HIP(hipMemcpyAsync(r->p_out.p, r->d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    if (out_interleaved && !out_direct) std::memcpy(ilv_host, ilv_pin, n * ofb);
+    if (!out_interleaved && !out_st)
+      for (int c = 0; c < N; c++) std::memcpy(out[c], r->p_out.p + (size_t)c * n, sizeof(float) * n);
+    return;
+  }
+  // Long calls: the pipeline of earhip_render_process, on the packed bytes.  Chunk c is one contiguous byte range of the caller's
+  // buffer: staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all (device-reachable
+  // frames); H2D on the copy stream; on the context's stream the conversion into the chunk's rows of d_in, then the chunk's
+  // render as an ordinary process call; D2H of its outputs on the second copy stream.
+  const size_t *cstart = plan.cstart;
+  const int nch = plan.nch;
+  r->pipe.make();
+  if (!direct) {
+    if (!r->gather) {
+      r->gather.reset(new GatherPool);
+      const int want = ctx->get(OPT_HOST_THREADS, 0);
+      r->gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
+    }
+    r->gather->submit_range(frames, r->p_bytes.p, fb, cstart, nch, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
+    src = r->p_bytes.p;
+  }
+  hipError_t err = hipSuccess;
+  std::string fail;
+  int recorded = 0;   // chunks whose output transfer THIS call has queued (ev_out[c] recorded)
+  int scattered = 0;  // ... whose outputs have been handed to the caller (only from pinned staging)
+  auto scatter_chunk = [&](int c) {
+    const size_t at = cstart[c], len = cstart[c + 1] - at;
+    if (out_interleaved) {
+      std::memcpy(ilv_host + at * ofb, ilv_pin + at * ofb, len * ofb);
+    } else {
+      const float *base = r->p_out.p + (size_t)N * at;
+      for (int ch = 0; ch < N; ch++) std::memcpy(out[ch] + at, base + (size_t)ch * len, sizeof(float) * len);
+    }
+  };
+  for (int c = 0; c < nch; c++) {
+    const size_t at = cstart[c], len = cstart[c + 1] - at;
+    float *din = r->d_in.p + (size_t)M * at, *dout = r->d_out.p + (size_t)N * at;
+    if (!direct) {
+      GatherPool &gp = *r->gather;
+      while (gp.done[c].load(std::memory_order_acquire) < gp.nthreads()) {
+        // (meanwhile: outputs of chunks whose transfer this call queued and that have landed go back to the caller)
+        if (!out_direct && scattered < recorded && err == hipSuccess && fail.empty() &&
+            hipEventQuery(r->pipe.ev_out[scattered]) == hipSuccess)
+          scatter_chunk(scattered++);
+        else
+          std::this_thread::yield();
+      }
+    }
+    if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
+    err = hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
+    if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_in[c], r->pipe.in);
+    if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream, r->pipe.ev_in[c], 0);
+    if (err != hipSuccess) continue;
+    try {
+      launch_pcm_to_rows(fmt, r->d_bytes.p + at * fb, fb, first_byte, M, len, din, len, ctx->stream);
+      const int64_t t0 = r->t;
+      r->process_device(len / r->B, din, len, dout, len);
+      if (out_interleaved) launch_interleave(dout, len, len, at, t0);
+    } catch (const Error &e) {
+      fail = e.msg;
+      continue;
+    }
+    err = hipEventRecord(r->pipe.ev_k[c], ctx->stream);
+    if (err == hipSuccess) err = hipStreamWaitEvent(r->pipe.out, r->pipe.ev_k[c], 0);
+    if (err != hipSuccess) continue;
+    if (out_interleaved)
+      err = hipMemcpyAsync((out_direct ? ilv_host : ilv_pin) + at * ofb, ilv_dev + at * ofb, len * ofb, hipMemcpyDeviceToHost, r->pipe.out);
+    else if (out_st)
+      err = hipMemcpy2DAsync(out0 + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, N, hipMemcpyDeviceToHost,
+                             r->pipe.out);
+    else
+      err = hipMemcpyAsync(r->p_out.p + (size_t)N * at, dout, sizeof(float) * len * N, hipMemcpyDeviceToHost, r->pipe.out);
+    if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_out[c], r->pipe.out);
+    if (err == hipSuccess) recorded = c + 1;
+  }
+  if (!direct) r->gather->wait_all();
+  (void)hipStreamSynchronize(r->pipe.in);
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipStreamSynchronize(r->pipe.out);
+  EARHIP_HIP(err);
+  if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
+  if (!out_direct)
+    for (; scattered < nch; scattered++) scatter_chunk(scattered);
+  r->last_host_chunks = nch;
+}
+
 int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels,
                                  int first_channel, float *const *out, int out_interleaved) {
   return guarded([&] {
@@ -973,130 +1177,7 @@ int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *f
     require(out != nullptr, "out must not be NULL");
     for (int c = 0; c < (out_interleaved ? 1 : r->N); c++) require(out[c] != nullptr, "out must not be NULL");
     if (nblocks == 0) return;
-    earhip_ctx *ctx = r->ctx;
-    ctx->use();
-    const int M = r->M, N = r->N;
-    const size_t S = (size_t)pcm_sample_bytes(fmt);
-    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
-    const size_t fb = (size_t)frame_channels * S, first_byte = (size_t)first_channel * S, bytes = n * fb;
-    const bool direct = ctx->host_reachable(frames, bytes);  // (device-reachable frames: DMA straight from the caller's buffer)
-    // (the plan of earhip_render_process on rows in the same kind of memory: the same chunks, the same results)
-    const HostChunkPlan plan = r->host_plan(nblocks, direct);
-    float *const out0 = out[0];
-    const size_t out_st = out_interleaved ? 0 : r->NP <= 1 || !plan.short_call ? r->direct_stride(out, N, n) : 0;
-    const bool out_direct = out_interleaved ? ctx->host_reachable(out0, sizeof(float) * n * N) : out_st != 0;
-    r->d_in.reserve(cap * M);
-    r->d_out.reserve(cap * N);
-    r->p_out.reserve(cap * N);
-    r->d_bytes.reserve(cap * fb + 16);  // (+16: the conversion kernel reads whole dwords)
-    if (!direct) r->p_bytes.reserve(cap * fb);
-    if (out_interleaved) r->d_ilv.reserve(cap * N);
-    const unsigned char *src = static_cast<const unsigned char *>(frames);
-    r->last_host_chunks = 0;
-    if (plan.short_call) {
-      if (!direct) {
-        std::memcpy(r->p_bytes.p, frames, bytes);
-        src = r->p_bytes.p;
-      }
-      EARHIP_HIP(hipMemcpyAsync(r->d_bytes.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-      launch_pcm_to_rows(fmt, r->d_bytes.p, fb, first_byte, M, n, r->d_in.p, n, ctx->stream);
-      if (out_interleaved) {
-        r->process_device(nblocks, r->d_in.p, n, r->d_out.p, n);
-        launch_rows_to_frames(r->d_out.p, n, N, n, r->d_ilv.p, N, ctx->stream);
-        EARHIP_HIP(hipMemcpyAsync(out_direct ? out0 : r->p_out.p, r->d_ilv.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
-      } else {
-        // (as earhip_render_process: a single-partition render writes its outputs straight into host memory)
-        const bool direct_out = r->NP <= 1;
-        float *dst = out_st ? out0 : direct_out ? r->p_out.p : r->d_out.p;
-        r->process_device(nblocks, r->d_in.p, n, dst, out_st ? out_st : n);
-        if (!out_st && !direct_out)
-          EARHIP_HIP(hipMemcpyAsync(r->p_out.p, r->d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
-      }
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-      if (out_interleaved && !out_direct) std::memcpy(out0, r->p_out.p, sizeof(float) * n * N);
-      if (!out_interleaved && !out_st)
-        for (int c = 0; c < N; c++) std::memcpy(out[c], r->p_out.p + (size_t)c * n, sizeof(float) * n);
-      return;
-    }
-    // Long calls: the pipeline of earhip_render_process, on the packed bytes.  Chunk c is one contiguous byte range of the caller's
-    // buffer: staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all (device-reachable
-    // frames); H2D on the copy stream; on the context's stream the conversion into the chunk's rows of d_in, then the chunk's
-    // render as an ordinary process call; D2H of its outputs on the second copy stream.
-    const size_t *cstart = plan.cstart;
-    const int nch = plan.nch;
-    r->pipe.make();
-    if (!direct) {
-      if (!r->gather) {
-        r->gather.reset(new GatherPool);
-        const int want = ctx->get(OPT_HOST_THREADS, 0);
-        r->gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
-      }
-      r->gather->submit_range(frames, r->p_bytes.p, fb, cstart, nch, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
-      src = r->p_bytes.p;
-    }
-    hipError_t err = hipSuccess;
-    std::string fail;
-    int recorded = 0;   // chunks whose output transfer THIS call has queued (ev_out[c] recorded)
-    int scattered = 0;  // ... whose outputs have been handed to the caller (only from pinned staging)
-    auto scatter_chunk = [&](int c) {
-      const size_t at = cstart[c], len = cstart[c + 1] - at;
-      if (out_interleaved) {
-        std::memcpy(out0 + (size_t)N * at, r->p_out.p + (size_t)N * at, sizeof(float) * len * N);
-      } else {
-        const float *base = r->p_out.p + (size_t)N * at;
-        for (int ch = 0; ch < N; ch++) std::memcpy(out[ch] + at, base + (size_t)ch * len, sizeof(float) * len);
-      }
-    };
-    for (int c = 0; c < nch; c++) {
-      const size_t at = cstart[c], len = cstart[c + 1] - at;
-      float *din = r->d_in.p + (size_t)M * at, *dout = r->d_out.p + (size_t)N * at;
-      if (!direct) {
-        GatherPool &gp = *r->gather;
-        while (gp.done[c].load(std::memory_order_acquire) < gp.nthreads()) {
-          // (meanwhile: outputs of chunks whose transfer this call queued and that have landed go back to the caller)
-          if (!out_direct && scattered < recorded && err == hipSuccess && fail.empty() &&
-              hipEventQuery(r->pipe.ev_out[scattered]) == hipSuccess)
-            scatter_chunk(scattered++);
-          else
-            std::this_thread::yield();
-        }
-      }
-      if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
-      err = hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
-      if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_in[c], r->pipe.in);
-      if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream, r->pipe.ev_in[c], 0);
-      if (err != hipSuccess) continue;
-      try {
-        launch_pcm_to_rows(fmt, r->d_bytes.p + at * fb, fb, first_byte, M, len, din, len, ctx->stream);
-        r->process_device(len / r->B, din, len, dout, len);
-        if (out_interleaved) launch_rows_to_frames(dout, len, N, len, r->d_ilv.p + (size_t)N * at, N, ctx->stream);
-      } catch (const Error &e) {
-        fail = e.msg;
-        continue;
-      }
-      err = hipEventRecord(r->pipe.ev_k[c], ctx->stream);
-      if (err == hipSuccess) err = hipStreamWaitEvent(r->pipe.out, r->pipe.ev_k[c], 0);
-      if (err != hipSuccess) continue;
-      if (out_interleaved)
-        err = hipMemcpyAsync((out_direct ? out0 : r->p_out.p) + (size_t)N * at, r->d_ilv.p + (size_t)N * at, sizeof(float) * len * N,
-                             hipMemcpyDeviceToHost, r->pipe.out);
-      else if (out_st)
-        err = hipMemcpy2DAsync(out0 + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, N, hipMemcpyDeviceToHost,
-                               r->pipe.out);
-      else
-        err = hipMemcpyAsync(r->p_out.p + (size_t)N * at, dout, sizeof(float) * len * N, hipMemcpyDeviceToHost, r->pipe.out);
-      if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_out[c], r->pipe.out);
-      if (err == hipSuccess) recorded = c + 1;
-    }
-    if (!direct) r->gather->wait_all();
-    (void)hipStreamSynchronize(r->pipe.in);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipStreamSynchronize(r->pipe.out);
-    EARHIP_HIP(err);
-    if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
-    if (!out_direct)
-      for (; scattered < nch; scattered++) scatter_chunk(scattered);
-    r->last_host_chunks = nch;
+    process_frames_host(r, nblocks, frames, fmt, frame_channels, first_channel, out, out_interleaved, nullptr, nullptr);
   });
 }
 
@@ -1123,6 +1204,76 @@ int earhip_render_process_frames_device(earhip_render *r, size_t nblocks, const 
     } else {
       r->process_device(nblocks, r->d_rows.p, n, out_dev, out_stride);
     }
+  });
+}
+
+int earhip_render_process_frames_pcm(earhip_render *r, size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels,
+                                     int first_channel, void *out_frames, const earhip_pcm_out *out) {
+  return guarded([&] {
+    check_frames_args(r, nblocks, frames, fmt, frame_channels, first_channel);
+    const size_t So = check_pcm_out(out);
+    require(out_frames != nullptr, "out_frames must not be NULL");
+    require(So == 3 || reinterpret_cast<uintptr_t>(out_frames) % So == 0, "out_frames not aligned to the sample size");
+    if (nblocks == 0) return;
+    process_frames_host(r, nblocks, frames, fmt, frame_channels, first_channel, nullptr, 1, out, out_frames);
+  });
+}
+
+int earhip_render_process_frames_pcm_device(earhip_render *r, size_t nblocks, const void *frames_dev, earhip_pcm_format fmt,
+                                            int frame_channels, int first_channel, void *out_dev, size_t out_frame_bytes,
+                                            size_t out_first_byte, const earhip_pcm_out *out) {
+  return guarded([&] {
+    check_frames_args(r, nblocks, frames_dev, fmt, frame_channels, first_channel);
+    const size_t So = check_pcm_out(out);
+    require(out_dev != nullptr, "out_dev must not be NULL");
+    require(So == 3 || reinterpret_cast<uintptr_t>(out_dev) % So == 0, "out_dev not aligned to the sample size");
+    require(out_frame_bytes >= (size_t)r->N * So, "out_frame_bytes smaller than n_out samples");
+    require(out_first_byte <= out_frame_bytes - (size_t)r->N * So, "out_first_byte + n_out samples exceed out_frame_bytes");
+    require(So == 3 || (out_frame_bytes % So == 0 && out_first_byte % So == 0), "out_frame_bytes / out_first_byte not multiples of the sample size");
+    if (nblocks == 0) return;
+    earhip_ctx *ctx = r->ctx;
+    ctx->use();
+    const size_t S = (size_t)pcm_sample_bytes(fmt);
+    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
+    if (r->d_rows.n < cap * r->M || r->d_rows_out.n < cap * r->N) {
+      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (first use: nothing of this renderer may still read them)
+      r->d_rows.reserve(cap * r->M);
+      r->d_rows_out.reserve(cap * r->N);
+    }
+    r->reserve_levels();
+    launch_pcm_to_rows(fmt, frames_dev, (size_t)frame_channels * S, (size_t)first_channel * S, r->M, n, r->d_rows.p, n, ctx->stream);
+    const int64_t t0 = r->t;
+    r->process_device(nblocks, r->d_rows.p, n, r->d_rows_out.p, n);
+    launch_rows_to_pcm(*out, r->d_rows_out.p, n, r->N, n, static_cast<unsigned char *>(out_dev), out_frame_bytes, out_first_byte,
+                       r->d_peak.p, r->d_clip.p, t0, ctx->stream);
+  });
+}
+
+int earhip_render_output_levels(earhip_render *r, float *peak, uint64_t *clipped, int reset) {
+  return guarded([&] {
+    require(r != nullptr, "render must not be NULL");
+    require(peak != nullptr && clipped != nullptr, "peak and clipped must not be NULL");
+    earhip_ctx *ctx = r->ctx;
+    ctx->use();
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    if (!r->d_peak.p) {  // (no PCM-out call yet)
+      for (int c = 0; c < r->N; c++) peak[c] = 0.f, clipped[c] = 0;
+      return;
+    }
+    // (the kernel keeps kLevelSlots copies: the maximum / the sum over them; bits of non-negative floats order as integers)
+    const size_t cnt = (size_t)kLevelSlots * r->N;
+    std::vector<unsigned> pk(cnt);
+    std::vector<unsigned long long> cl(cnt);
+    EARHIP_HIP(hipMemcpy(pk.data(), r->d_peak.p, sizeof(unsigned) * cnt, hipMemcpyDeviceToHost));
+    EARHIP_HIP(hipMemcpy(cl.data(), r->d_clip.p, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost));
+    for (int c = 0; c < r->N; c++) {
+      unsigned m = 0;
+      uint64_t sum = 0;
+      for (int k = 0; k < kLevelSlots; k++) m = std::max(m, pk[(size_t)k * r->N + c]), sum += cl[(size_t)k * r->N + c];
+      std::memcpy(&peak[c], &m, sizeof(float));
+      clipped[c] = sum;
+    }
+    if (reset) r->zero_levels();
   });
 }
 

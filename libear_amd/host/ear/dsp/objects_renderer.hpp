@@ -122,10 +122,65 @@ namespace ear {
                                  size_t out_stride, bool out_interleaved = false) {
         frames_device_(nblocks, frames_dev, EARHIP_PCM_F32, frame_channels, first_channel, out_dev, out_stride, out_interleaved);
       }
+      /// Interleaved PCM frames in AND out (include/earhip.h: earhip_render_process_frames_pcm): file to file in one call.  The
+      /// output format is the type of the output pointer — int16_t s16, uint8_t s24 (3 bytes a sample, packed), int32_t s32,
+      /// float f32 —, out_frames holds nblocks * block_size frames of n_out samples.  The conversion (scale, round half to even,
+      /// saturate; optional TPDF dither for s16, a function of (seed, sample clock, channel)) runs on the device.
+      struct PcmOutOptions {
+        bool dither;    ///< s16 only
+        uint32_t seed;  ///< of the dither hash
+        PcmOutOptions(bool dither_ = false, uint32_t seed_ = 0) : dither(dither_), seed(seed_) {}
+      };
+      template <typename In>
+      void process_frames(size_t nblocks, const In *frames, int frame_channels, int first_channel, int16_t *out_frames,
+                          const PcmOutOptions &opt = PcmOutOptions()) {
+        frames_pcm_(nblocks, frames, pcm_format_of(frames), frame_channels, first_channel, out_frames, EARHIP_PCM_S16, opt);
+      }
+      template <typename In>
+      void process_frames(size_t nblocks, const In *frames, int frame_channels, int first_channel, uint8_t *out_frames,
+                          const PcmOutOptions &opt = PcmOutOptions()) {
+        frames_pcm_(nblocks, frames, pcm_format_of(frames), frame_channels, first_channel, out_frames, EARHIP_PCM_S24, opt);
+      }
+      template <typename In>
+      void process_frames(size_t nblocks, const In *frames, int frame_channels, int first_channel, int32_t *out_frames,
+                          const PcmOutOptions &opt = PcmOutOptions()) {
+        frames_pcm_(nblocks, frames, pcm_format_of(frames), frame_channels, first_channel, out_frames, EARHIP_PCM_S32, opt);
+      }
+      /// device memory to device memory, asynchronous on the context's stream: the renderer's samples are bytes
+      /// [out_first_byte, + n_out * sample size) of each output frame of out_frame_bytes; every other byte is left alone
+      template <typename In, typename Out>
+      void process_frames_pcm_device(size_t nblocks, const In *frames_dev, int frame_channels, int first_channel, Out *out_dev,
+                                     size_t out_frame_bytes, size_t out_first_byte = 0, const PcmOutOptions &opt = PcmOutOptions()) {
+        earhip_pcm_out o;
+        o.format = pcm_format_of(static_cast<const Out *>(out_dev));
+        o.dither = opt.dither ? 1 : 0;
+        o.seed = opt.seed;
+        hip::check(earhip_render_process_frames_pcm_device(h_, nblocks, frames_dev, pcm_format_of(frames_dev), frame_channels,
+                                                           first_channel, out_dev, out_frame_bytes, out_first_byte, &o));
+      }
+      /// per output channel since the last reset of these numbers: the largest |x| that went through a PCM-out call and the
+      /// number of clipped samples (synchronises the stream); reset_after: zero them afterwards.  reset() zeroes them too.
+      void output_levels(std::vector<float> &peak, std::vector<uint64_t> &clipped, bool reset_after = false) {
+        peak.assign(n_out_, 0.0f);
+        clipped.assign(n_out_, 0);
+        hip::check(earhip_render_output_levels(h_, peak.data(), clipped.data(), reset_after ? 1 : 0));
+      }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
       size_t block_size() const { return block_size_; }
 
      private:
+      static earhip_pcm_format pcm_format_of(const int16_t *) { return EARHIP_PCM_S16; }
+      static earhip_pcm_format pcm_format_of(const uint8_t *) { return EARHIP_PCM_S24; }
+      static earhip_pcm_format pcm_format_of(const int32_t *) { return EARHIP_PCM_S32; }
+      static earhip_pcm_format pcm_format_of(const float *) { return EARHIP_PCM_F32; }
+      void frames_pcm_(size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels, int first_channel,
+                       void *out_frames, earhip_pcm_format out_fmt, const PcmOutOptions &opt) {
+        earhip_pcm_out o;
+        o.format = out_fmt;
+        o.dither = opt.dither ? 1 : 0;
+        o.seed = opt.seed;
+        hip::check(earhip_render_process_frames_pcm(h_, nblocks, frames, fmt, frame_channels, first_channel, out_frames, &o));
+      }
       void frames_(size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels, int first_channel, float *const *out,
                    int interleaved) {
         hip::check(earhip_render_process_frames(h_, nblocks, frames, fmt, frame_channels, first_channel, out, interleaved));
