@@ -807,6 +807,75 @@ int earhip_comm_info(earhip_comm *comm, int info[4]);
  * HIP events on the communicator's stream.  *GBps = bytes a rank sent per second / 1e9 (0 with one rank).  Collective. */
 int earhip_comm_link_probe(earhip_comm *comm, size_t bytes, int shift, int reps, double *GBps);
 
+/* ------------------------------------------------------------------------
+ * (L) Programme loudness — ITU-R BS.1770-4, no libear counterpart (libear has no meter).  The number EBU R 128 and ATSC A/85
+ * are written around (LKFS), measured on the DEVICE from the render's float32 output rows while they are still in its memory:
+ * no transfer of the samples, and the PCM-out forms keep their 2- or 3-byte samples on the bus.
+ *
+ * The measurement, exactly (a caller can reproduce it).  Per channel a cascade of two biquads in FLOAT64 arithmetic on the
+ * float32 samples, y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2], state zero at create and reset.
+ * BS.1770-4's coefficients at 48 kHz:
+ *     stage 1 (shelf)      b0 1.53512485958697  b1 -2.69169618940638  b2 1.19839281085285  a1 -1.69065929318241  a2 0.73248077421585
+ *     stage 2 (high-pass)  b0 1.0               b1 -2.0               b2 1.0               a1 -1.99004745483398  a2 0.99007225036621
+ *   - STEP ENERGIES are the meter's raw product: z[s][c] = the mean of y^2 over step s of channel c; a step is 100 ms =
+ *     sample_rate / 10 samples, counted on the meter's own sample clock since its reset, not per call.  The samples of an
+ *     unfinished last step are kept in the state and belong to no step yet.
+ *   - gating block j (400 ms, 75 % overlap) is steps j .. j + 3: P_j = sum over c of G_c (z[j][c] + .. + z[j+3][c]) / 4,
+ *     l_j = -0.691 + 10 log10 P_j.
+ *   - INTEGRATED loudness, gated twice: J_a = {j : l_j > -70}; Gamma_r = -0.691 + 10 log10(mean over J_a of P_j) - 10;
+ *     J_g = {j in J_a : l_j > Gamma_r}; L = -0.691 + 10 log10(mean over J_g of P_j).  With fewer than 4 steps or an empty
+ *     J_a, L = -infinity: a valid answer, EARHIP_OK.
+ *   - MAXIMUM MOMENTARY loudness = max over j of l_j; MAXIMUM SHORT-TERM loudness = the same formula over 30 consecutive steps
+ *     (3 s), hop one step.  Both -infinity when there is no whole window.
+ *   - channel weights G_c of a BS.2051 layout, from the nominal positions of group H: 0 for an LFE channel, 1.41 where
+ *     |elevation| < 30 and 60 <= |azimuth| <= 120 degrees, else 1.0 (0+5+0: 1 1 1 0 1.41 1.41).
+ * Float64 formulations of the cascade differ among themselves by 5e-15 .. 2e-11 relative per step energy (the high-pass poles
+ * lie 0.005 inside the unit circle); the device's — the time axis cut into chunks that run in parallel, the filter state carried
+ * across them exactly — stays within 1e-9 of scipy.signal.lfilter in float64 (tests), float32 arithmetic would be
+ * 1.6e-6 away.  Step energies are summed in a fixed order: the same calls give the same bits.
+ *
+ * Out of scope: true-peak metering (BS.1770 annex 2), loudness range (EBU Tech 3342; computable from earhip_loudness_steps),
+ * coefficients for other sample rates, any normalisation of the output gain, any file I/O.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_loudness earhip_loudness;
+/* sample_rate: a multiple of 10.  coeffs: [2][5] = b0 b1 b2 a1 a2 per stage, or NULL = the table above, which is allowed at
+ * 48000 only (another rate must bring its own coefficients).  max_steps: capacity of the step store (100 ms each), made HERE
+ * with everything else the meter needs: a process call allocates nothing and synchronises nothing. */
+int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs,
+                           size_t max_steps, earhip_loudness **out);
+/* (detach it from its renderers first: earhip_render_attach_loudness(r, NULL)) */
+int earhip_loudness_destroy(earhip_loudness *m);
+int earhip_loudness_reset(earhip_loudness *m); /* state, clock and steps to zero */
+/* planar float32 rows in device memory (channel c at rows_dev + c * stride), any nsamples >= 0 (no block size, no alignment);
+ * enqueues on the context's stream, does not synchronise.  A call that would pass max_steps is EARHIP_INVALID_ARGUMENT and
+ * consumes nothing. */
+int earhip_loudness_process_device(earhip_loudness *m, size_t nsamples, const float *rows_dev, size_t stride);
+/* host rows: H2D + the above, in pieces through a staging buffer of fixed size made at create; synchronises */
+int earhip_loudness_process(earhip_loudness *m, size_t nsamples, const float *const *rows);
+int earhip_loudness_num_steps(earhip_loudness *m, size_t *steps); /* finished steps; synchronises */
+/* energy [n][n_channels] = z of steps [first, first + n), which must be finished; synchronises */
+int earhip_loudness_steps(earhip_loudness *m, size_t first, size_t n, double *energy);
+/* the gating above over all finished steps; weights [n_channels]; any output pointer may be NULL; synchronises */
+int earhip_loudness_result(earhip_loudness *m, const double *weights, double *integrated,
+                           double *max_momentary, double *max_short_term);
+/* Pure host functions, no context and no device.  Like the host forms of group K they are a deliberate CPU computation on a
+ * few numbers, not a fall-back of the device path.
+ * earhip_loudness_gate is what a multi-GPU render (group J) uses: after the reduce-scatter each rank owns whole channels of
+ * the summed bus (earhip_comm_channel_range) and runs a meter over its own rows; the ranks' energy columns are put side by
+ * side — a channel's step energies do not depend on the other channels of its meter — and gated once. */
+int earhip_loudness_gate(size_t n_steps, int n_channels, const double *energy /* [n_steps][n_channels] */,
+                         const double *weights, double *integrated, double *max_momentary,
+                         double *max_short_term);
+/* weights [n_channels of the full layout, LFE channels included]; an unknown name is EARHIP_UNKNOWN_LAYOUT */
+int earhip_loudness_layout_weights(const char *layout, double *weights);
+/* From now on every process call of r, of EVERY form, feeds its float32 output samples to m on the device, behind its kernels
+ * on the context's stream: the samples earhip_render_process_frames would hand back, before any PCM conversion or dither.
+ * m == NULL detaches.  m must have n_out channels and the renderer's context (else EARHIP_INVALID_ARGUMENT).
+ * earhip_render_reset does not touch m (a programme may be rendered in several passes); earhip_loudness_reset does.  A call
+ * that would pass m's max_steps fails with EARHIP_INVALID_ARGUMENT before anything is rendered.  A call that runs as two spans
+ * or as a pipeline of chunks is metered once per sample.  Without a meter the render paths are what they were. */
+int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m);
+
 #ifdef __cplusplus
 }
 #endif

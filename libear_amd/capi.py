@@ -969,7 +969,88 @@ class Renderer:
         check(load().earhip_render_last_plan(self.h, out))
         return {"kernel": out[0], "tile": out[1], "ntiles": out[2], "gsplit": out[3]}
 
+    def attach_loudness(self, meter):
+        """every process call of every form feeds its float32 output samples to `meter` (a Loudness of n_out channels on this
+        context) on the device; None detaches (include/earhip.h: earhip_render_attach_loudness)"""
+        check(load().earhip_render_attach_loudness(self.h, meter.h if meter is not None else None))
+        self._meter = meter  # (kept alive while attached)
+
     def close(self):
         if self.h:
             load().earhip_render_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+# (L) programme loudness, ITU-R BS.1770-4
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def loudness_gate(energy, weights):
+    """step energies [steps][channels] (Loudness.steps; the columns of several meters side by side) and channel weights ->
+    (integrated, max momentary, max short-term) in LKFS, -inf where undefined; on the calling thread, no device"""
+    w = _f64(weights).reshape(-1)
+    e = _f64(energy).reshape(-1, w.size)
+    out = [C.c_double(0) for _ in range(3)]
+    check(load().earhip_loudness_gate(C.c_size_t(e.shape[0]), C.c_int(w.size), C.c_void_p(e.ctypes.data), C.c_void_p(w.ctypes.data),
+                                      *[C.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+def loudness_layout_weights(layout):
+    """BS.1770-4's channel weights of a BS.2051 layout, float64 [channels of the full layout] (LFE channels 0)"""
+    n = C.c_int(0)
+    check(load().earhip_layout_num_channels(layout.encode(), C.byref(n)))
+    w = np.zeros(n.value, np.float64)
+    check(load().earhip_loudness_layout_weights(layout.encode(), C.c_void_p(w.ctypes.data)))
+    return w
+
+
+class Loudness:
+    """(L) the meter: K-weighted 100 ms step energies kept on the device, gated on request."""
+
+    def __init__(self, ctx, n_channels, sample_rate=48000, max_steps=36000, coeffs=None):
+        self.ctx, self.C = ctx, n_channels
+        c = None if coeffs is None else _f64(coeffs).reshape(2, 5)
+        self.h = C.c_void_p()
+        check(load().earhip_loudness_create(ctx.h, C.c_int(n_channels), C.c_int(sample_rate),
+                                            None if c is None else C.c_void_p(c.ctypes.data), C.c_size_t(max_steps),
+                                            C.byref(self.h)))
+
+    def process(self, x):
+        """x [channels][n] host array, any n"""
+        x = _f32(x).reshape(self.C, -1)
+        check(load().earhip_loudness_process(self.h, C.c_size_t(x.shape[1]), _chan_ptrs(x)))
+
+    def process_device(self, nsamples, rows_ptr, stride):
+        """planar float32 rows in device memory (e.g. a torch tensor's data_ptr()); enqueues on the context's stream"""
+        check(load().earhip_loudness_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(rows_ptr), C.c_size_t(stride)))
+
+    def num_steps(self):
+        v = C.c_size_t(0)
+        check(load().earhip_loudness_num_steps(self.h, C.byref(v)))
+        return v.value
+
+    def steps(self, first=0, n=None):
+        """step energies [n][channels] float64 of the finished steps [first, first + n) (default: all from first)"""
+        if n is None:
+            n = self.num_steps() - first
+        e = np.zeros((n, self.C), np.float64)
+        check(load().earhip_loudness_steps(self.h, C.c_size_t(first), C.c_size_t(n), C.c_void_p(e.ctypes.data)))
+        return e
+
+    def result(self, weights):
+        """(integrated, max momentary, max short-term) in LKFS over all finished steps"""
+        w = _f64(weights).reshape(self.C)
+        out = [C.c_double(0) for _ in range(3)]
+        check(load().earhip_loudness_result(self.h, C.c_void_p(w.ctypes.data), *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
+    def reset(self):
+        check(load().earhip_loudness_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_loudness_destroy(self.h)
             self.h = C.c_void_p()

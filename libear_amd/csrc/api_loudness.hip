@@ -1,0 +1,244 @@
+// api_loudness.hip — group L of include/earhip.h: programme loudness (ITU-R BS.1770-4) measured on the device.  The kernels:
+// loudness_kernels.h; the maths they share with the host functions and the CPU tests: loudness.h.
+#include <cstring>
+#include <memory>
+
+#include "common.h"
+#include "layout_table.h"
+#include "loudness_kernels.h"
+
+using namespace earhip;
+
+struct earhip_loudness {
+  earhip_ctx *ctx = nullptr;
+  int C = 0, rate = 0, step = 0, L = 0;
+  size_t max_steps = 0;
+  KCoeffs<double> k;
+  unsigned long long clock = 0;  // samples since create / reset (the kernels get what they need of it as arguments)
+  int par = 0;                   // which `open` word holds the sum of the unfinished step
+  // everything a process call touches, made at create
+  DevBuf<double> e, start, q, state, open, steps, P, Q;
+  // host rows: pieces of kStage samples per channel through these
+  static constexpr size_t kStage = 65536;
+  PinBuf<float> p_stage;
+  DevBuf<float> d_stage;
+
+  size_t max_launch() const { return (size_t)(kLoudMaxChunks - 1) * (size_t)L; }
+  size_t num_steps() const { return (size_t)(clock / (unsigned long long)step); }
+
+  void check_room(size_t nsamples) const {
+    if ((clock + nsamples) / (unsigned long long)step > max_steps)
+      fail_invalid("the call would pass the loudness meter's max_steps (nothing was consumed)");
+  }
+
+  void zero() {
+    EARHIP_HIP(hipMemsetAsync(state.p, 0, sizeof(double) * state.n, ctx->stream));
+    EARHIP_HIP(hipMemsetAsync(open.p, 0, sizeof(double) * open.n, ctx->stream));
+    EARHIP_HIP(hipMemsetAsync(steps.p, 0, sizeof(double) * steps.n, ctx->stream));
+    clock = 0;
+    par = 0;
+  }
+
+  void launch(size_t n, const float *rows, size_t stride) {
+    LoudArgs a;
+    a.rows = rows;
+    a.stride = stride;
+    a.n = (unsigned)n;
+    a.off0 = (unsigned)(clock % (unsigned long long)L);
+    a.nchunks = (unsigned)((a.off0 + n + (size_t)L - 1) / (size_t)L);
+    a.L = L;
+    a.C = C;
+    a.k = k;
+    a.e = e.p, a.start = start.p, a.q = q.p, a.state = state.p, a.P = P.p, a.Q = Q.p;
+    a.open = open.p;
+    a.par = par;
+    a.cps = (unsigned)(step / L);
+    a.chunk0_in_step = (unsigned)((clock / (unsigned long long)L) % a.cps);
+    a.step0 = clock / (unsigned long long)step;
+    a.steps = steps.p;
+    a.step_samples = (double)step;
+    if (a.nchunks > (unsigned)kLoudMaxChunks) fail_internal("loudness launch beyond its scratch");
+    const unsigned touched = (a.chunk0_in_step + a.nchunks + a.cps - 1) / a.cps;
+    const dim3 grid((a.nchunks + 63) / 64, (unsigned)C);
+    hipLaunchKernelGGL(k_loudness_pass<false>, grid, dim3(64), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_loudness_propagate, dim3((unsigned)C), dim3(kLoudPropThreads), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_loudness_pass<true>, grid, dim3(64), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_loudness_steps, dim3((touched * (unsigned)C + 63) / 64), dim3(64), 0, ctx->stream, a, touched);
+    EARHIP_HIP(hipGetLastError());
+    clock += n;
+    par ^= 1;
+  }
+
+  // device rows; the caller has checked the room
+  void feed(size_t nsamples, const float *rows, size_t stride) {
+    const size_t most = max_launch();
+    for (size_t at = 0; at < nsamples;) {
+      const size_t n = std::min(most, nsamples - at);
+      launch(n, rows + at, stride);
+      at += n;
+    }
+  }
+};
+
+namespace earhip {
+void loudness_check_room(const earhip_loudness *m, size_t nsamples) { m->check_room(nsamples); }
+void loudness_feed(earhip_loudness *m, size_t nsamples, const float *rows, size_t stride) { m->feed(nsamples, rows, stride); }
+const earhip_ctx *loudness_ctx(const earhip_loudness *m) { return m->ctx; }
+int loudness_channels(const earhip_loudness *m) { return m->C; }
+}  // namespace earhip
+
+extern "C" {
+
+int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs, size_t max_steps,
+                           earhip_loudness **out) {
+  return guarded([&] {
+    require(ctx != nullptr && out != nullptr, "ctx and out must not be NULL");
+    require(n_channels >= 1 && n_channels <= 65535, "n_channels must be in [1, 65535]");
+    require(sample_rate >= 10 && sample_rate % 10 == 0, "sample_rate must be a positive multiple of 10");
+    require(coeffs != nullptr || sample_rate == 48000,
+            "the built-in K-weighting coefficients are those of 48000 Hz: another rate must bring its own");
+    require(max_steps >= 1 && max_steps <= ((size_t)1 << 32) / (size_t)n_channels, "max_steps out of range");
+    ctx->use();
+    std::unique_ptr<earhip_loudness> m(new earhip_loudness);
+    m->ctx = ctx;
+    m->C = n_channels;
+    m->rate = sample_rate;
+    m->step = sample_rate / 10;
+    m->L = loudness_chunk_length(m->step, 240);
+    m->max_steps = max_steps;
+    double c[2][5];
+    for (int s = 0; s < 2; s++)
+      for (int i = 0; i < 5; i++) {
+        c[s][i] = coeffs ? coeffs[5 * s + i] : kLoudnessCoeffs48k[s][i];
+        require(std::isfinite(c[s][i]), "coefficients must be finite");
+        m->k.c[s][i] = c[s][i];
+      }
+    const size_t C = (size_t)n_channels;
+    m->e.alloc(C * kLoudMaxChunks * 4);
+    m->start.alloc(C * kLoudMaxChunks * 4);
+    m->q.alloc(C * kLoudMaxChunks);
+    m->state.alloc(C * 4);
+    m->open.alloc(2 * C);
+    m->steps.alloc(max_steps * C);
+    std::vector<double> P(16 * (size_t)(m->L + 1)), Q(16 * 65);
+    k_state_powers(c, (size_t)m->L + 1, 1, P.data());
+    k_state_powers(c, 65, (size_t)m->L, Q.data());
+    m->P.alloc(P.size());
+    m->Q.alloc(Q.size());
+    EARHIP_HIP(hipMemcpy(m->P.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice));
+    EARHIP_HIP(hipMemcpy(m->Q.p, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice));
+    m->p_stage.reserve(C * earhip_loudness::kStage);
+    m->d_stage.alloc(C * earhip_loudness::kStage);
+    m->zero();
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    *out = m.release();
+  });
+}
+
+int earhip_loudness_destroy(earhip_loudness *m) {
+  return guarded([&] {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);
+    delete m;
+  });
+}
+
+int earhip_loudness_reset(earhip_loudness *m) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    m->ctx->use();
+    m->zero();
+  });
+}
+
+int earhip_loudness_process_device(earhip_loudness *m, size_t nsamples, const float *rows_dev, size_t stride) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    if (nsamples == 0) return;
+    require(rows_dev != nullptr, "rows_dev must not be NULL");
+    require(stride >= nsamples, "stride too small");
+    m->check_room(nsamples);
+    m->ctx->use();
+    m->feed(nsamples, rows_dev, stride);
+  });
+}
+
+int earhip_loudness_process(earhip_loudness *m, size_t nsamples, const float *const *rows) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    if (nsamples == 0) return;
+    require(rows != nullptr, "rows must not be NULL");
+    for (int c = 0; c < m->C; c++) require(rows[c] != nullptr, "a row pointer is NULL");
+    m->check_room(nsamples);
+    earhip_ctx *ctx = m->ctx;
+    ctx->use();
+    const size_t cap = earhip_loudness::kStage;
+    for (size_t at = 0; at < nsamples;) {
+      const size_t n = std::min(cap, nsamples - at);
+      for (int c = 0; c < m->C; c++) std::memcpy(m->p_stage.p + (size_t)c * n, rows[c] + at, sizeof(float) * n);
+      EARHIP_HIP(hipMemcpyAsync(m->d_stage.p, m->p_stage.p, sizeof(float) * n * m->C, hipMemcpyHostToDevice, ctx->stream));
+      m->feed(n, m->d_stage.p, n);
+      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (the one staging buffer is free again)
+      at += n;
+    }
+  });
+}
+
+int earhip_loudness_num_steps(earhip_loudness *m, size_t *steps) {
+  return guarded([&] {
+    require(m != nullptr && steps != nullptr, "meter and steps must not be NULL");
+    m->ctx->use();
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+    *steps = m->num_steps();
+  });
+}
+
+int earhip_loudness_steps(earhip_loudness *m, size_t first, size_t n, double *energy) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    require(first <= m->num_steps() && n <= m->num_steps() - first, "steps [first, first + n) are not all finished");
+    if (n == 0) return;
+    require(energy != nullptr, "energy must not be NULL");
+    m->ctx->use();
+    EARHIP_HIP(hipMemcpyAsync(energy, m->steps.p + first * (size_t)m->C, sizeof(double) * n * (size_t)m->C, hipMemcpyDeviceToHost,
+                              m->ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+  });
+}
+
+int earhip_loudness_result(earhip_loudness *m, const double *weights, double *integrated, double *max_momentary,
+                           double *max_short_term) {
+  return guarded([&] {
+    require(m != nullptr && weights != nullptr, "meter and weights must not be NULL");
+    m->ctx->use();
+    const size_t n = m->num_steps();
+    std::vector<double> en(std::max<size_t>(n * (size_t)m->C, 1));
+    if (n) EARHIP_HIP(hipMemcpyAsync(en.data(), m->steps.p, sizeof(double) * n * (size_t)m->C, hipMemcpyDeviceToHost, m->ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+    loudness_gate(n, m->C, en.data(), weights, integrated, max_momentary, max_short_term);
+  });
+}
+
+int earhip_loudness_gate(size_t n_steps, int n_channels, const double *energy, const double *weights, double *integrated,
+                         double *max_momentary, double *max_short_term) {
+  return guarded([&] {
+    require(n_channels >= 1, "n_channels must be >= 1");
+    require(weights != nullptr && (n_steps == 0 || energy != nullptr), "energy and weights must not be NULL");
+    loudness_gate(n_steps, n_channels, energy, weights, integrated, max_momentary, max_short_term);
+  });
+}
+
+int earhip_loudness_layout_weights(const char *layout, double *weights) {
+  return guarded([&] {
+    require(layout != nullptr && weights != nullptr, "layout and weights must not be NULL");
+    const LayoutEntry *L = nullptr;
+    for (int i = 0; i < kNumLayouts; i++)
+      if (std::strcmp(kLayouts[i].name, layout) == 0) L = &kLayouts[i];
+    if (!L) throw Error{EARHIP_UNKNOWN_LAYOUT, std::string("unknown layout: ") + layout};
+    for (int c = 0; c < L->n; c++)
+      weights[c] = loudness_channel_weight(L->channels[c].azimuth, L->channels[c].elevation, L->channels[c].is_lfe);
+  });
+}
+
+}  // extern "C"

@@ -459,7 +459,20 @@ struct earhip_render {
   // which the planner spreads over the chip by splitting the objects (as in block mode).  The cut costs a second K0, a
   // second K2 launch and the boundaries (~30 us): taken when the tail is at most a quarter of a round.  Results are those
   // of two consecutive calls (every call length is a valid call: the state carries over).
+  // The one place every form of process call passes.  An attached loudness meter (earhip_render_attach_loudness) reads the
+  // planar rows the call wrote — the caller's, d_out or d_rows_out — behind the call's kernels: after the tail cut, so a call
+  // that ran as two spans is metered once per sample.  Without a meter this is render_spans and nothing else.
+  earhip_loudness *meter = nullptr;
+  void check_meter(size_t nblocks) const {
+    if (meter) loudness_check_room(meter, nblocks * (size_t)B);
+  }
   void process_device(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
+    if (!meter) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
+    loudness_check_room(meter, nblocks * (size_t)B);
+    render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
+    loudness_feed(meter, nblocks * (size_t)B, out_dev, out_stride);
+  }
+  void render_spans(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
     MixLaunch whole;  // the plan of the uncut call, made once (process_span takes it as it is)
     bool have_plan = false;
     if (!ctx->strict && ctx->get(OPT_TAILCUT, 1) != 0 && nblocks >= 2) {
@@ -782,12 +795,24 @@ int earhip_render_reset(earhip_render *r, int64_t sample_time) {
   });
 }
 
+int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m) {
+  return guarded([&] {
+    require(r != nullptr, "render must not be NULL");
+    if (m) {
+      require(loudness_ctx(m) == r->ctx, "the meter must belong to the renderer's context");
+      require(loudness_channels(m) == r->N, "the meter must have n_out channels");
+    }
+    r->meter = m;
+  });
+}
+
 int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *in_dev,
                                  size_t in_stride, float *out_dev, size_t out_stride) {
   return guarded([&] {
     require(r != nullptr, "render must not be NULL");
     require(in_dev != nullptr && out_dev != nullptr, "device pointers must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
+    r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
     require(in_stride >= nblocks * r->B && out_stride >= nblocks * r->B, "stride too small");
     if (nblocks == 0) return;
     r->ctx->use();
@@ -801,6 +826,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     require(r != nullptr, "render must not be NULL");
     require(in != nullptr && out != nullptr, "in and out must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
+    r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
     if (nblocks == 0) return;
     earhip_ctx *ctx = r->ctx;
     ctx->use();
@@ -968,6 +994,7 @@ static void check_frames_args(const earhip_render *r, size_t nblocks, const void
   require(first_channel >= 0, "first_channel must be >= 0");
   require((int64_t)first_channel + r->M <= (int64_t)frame_channels, "first_channel + n_objects exceeds frame_channels");
   require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
+  r->check_meter(nblocks);
   require(fmt == EARHIP_PCM_S24 || reinterpret_cast<uintptr_t>(frames) % (uintptr_t)S == 0, "frames not aligned to the sample size");
 }
 

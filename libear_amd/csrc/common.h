@@ -199,3 +199,13 @@ namespace earhip {
 int panner_create(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth, const double *elevation,
                   earhip_panner **out, bool with_extent);
 }  // namespace earhip
+
+struct earhip_loudness;
+namespace earhip {
+// the programme loudness meter (api_loudness.hip) as the renderer's tap sees it (earhip_render_attach_loudness): does a call of
+// nsamples fit its step store (throws EARHIP_INVALID_ARGUMENT), and the meter's kernels over planar device rows on the context's stream
+void loudness_check_room(const earhip_loudness *m, size_t nsamples);
+void loudness_feed(earhip_loudness *m, size_t nsamples, const float *rows, size_t stride);
+const earhip_ctx *loudness_ctx(const earhip_loudness *m);
+int loudness_channels(const earhip_loudness *m);
+}  // namespace earhip

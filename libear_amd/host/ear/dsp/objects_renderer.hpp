@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 #include "../hip.hpp"
+#include "../hip_loudness.hpp"
 
 namespace ear {
   namespace dsp {
@@ -165,6 +166,11 @@ namespace ear {
         clipped.assign(n_out_, 0);
         hip::check(earhip_render_output_levels(h_, peak.data(), clipped.data(), reset_after ? 1 : 0));
       }
+      /// From now on every process call of every form feeds its float32 output samples to `meter` on the device (before any PCM
+      /// conversion); detach_loudness() ends it.  The meter must have n_out channels and this renderer's context, and outlive
+      /// the attachment.  reset() leaves the meter alone.
+      void attach_loudness(hip::LoudnessMeter &meter) { hip::check(earhip_render_attach_loudness(h_, meter.get())); }
+      void detach_loudness() { hip::check(earhip_render_attach_loudness(h_, nullptr)); }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
       size_t block_size() const { return block_size_; }
 
