@@ -834,8 +834,36 @@ int earhip_comm_link_probe(earhip_comm *comm, size_t bytes, int shift, int reps,
  * across them exactly — stays within 1e-9 of scipy.signal.lfilter in float64 (tests), float32 arithmetic would be
  * 1.6e-6 away.  Step energies are summed in a fixed order: the same calls give the same bits.
  *
- * Out of scope: true-peak metering (BS.1770 annex 2), loudness range (EBU Tech 3342; computable from earhip_loudness_steps),
- * coefficients for other sample rates, any normalisation of the output gain, any file I/O.
+ *
+ * TRUE PEAK (BS.1770-4 annex 2) is measured by a meter made with earhip_loudness_create_tp, over the same samples in the same
+ * calls, exactly (a caller can reproduce it):
+ *   - the interpolator has `phases` FIR filters of `taps` coefficients each: y[phases n + p] = sum over k = 0 .. taps - 1 of
+ *     h[p][k] x[n - k], x the float32 sample stream of one channel on the meter's own clock, zero before create and reset.
+ *     The history of taps - 1 samples is carried across calls exactly: how a stream is cut into calls, launches, spans or
+ *     pipeline chunks does not change a single bit of any peak.  Arithmetic is float32, the coefficients rounded once to
+ *     float32, in a fixed order: an accumulator of zero, then k = 0 first, one fused multiply-add per tap;
+ *   - the default table is that of annex 2, phases = 4, taps = 12, every coefficient an integer over 8192 (exact in float32):
+ *         h[0] * 8192 =   14    90  -161   272   -487  1125  7964   -838   390  -218   122   -68
+ *         h[1] * 8192 = -239   240  -424   730  -1364  3810  6388  -1641   832  -477   271  -155
+ *         h[2][k] = h[1][11 - k]      h[3][k] = h[0][11 - k]
+ *     (the interleaved 48-tap filter is symmetric; its gain is 3.95 .. 4.05 up to 20 kHz at 48 kHz and below 0.041 from 30 kHz
+ *     upwards).  It is allowed at 44100 and 48000 Hz only: another rate brings its own table, e.g. 2 phases at 96 kHz;
+ *   - per channel the TRUE PEAK is the largest |y| and the SAMPLE PEAK the largest |x|, both with a max that ignores NaN, as
+ *     earhip_render_output_levels does (+infinity is possible), both linear float32: dBTP = 20 log10 is the caller's or the
+ *     binding's job.  No 12 dB pad, no output gain;
+ *   - both are kept per 100 ms step as well: y[phases n + p] belongs to the step of input sample n.  The filter's group delay
+ *     (5.5 samples of the default table) is NOT compensated: a peak within that of a step's end is booked to the next step.
+ *     The peaks of the unfinished step are carried to the next call, and earhip_loudness_peaks includes them.
+ * A float64 evaluation of the same sums differs from this one by at most (taps + 1) 2^-24 A X_c, A the largest sum over k of
+ * |h[p][k]| of any phase (2.023 for the default table), X_c the channel's sample peak.
+ *
+ * LOUDNESS RANGE (EBU Tech 3342) comes from the step energies on the host: the short-term powers P_j over 30 consecutive steps,
+ * hop one step, l_j = -0.691 + 10 log10 P_j; the absolute gate l_j > -70; the relative gate l_j > -0.691 + 10 log10(mean of
+ * P_j over the absolute-gated windows) - 20; s[0 .. n - 1] the surviving l_j sorted ascending;
+ * low = s[floor((n - 1) 0.10 + 0.5)], high = s[floor((n - 1) 0.95 + 0.5)], LRA = high - low.  With no surviving window
+ * LRA = 0 and low = high = -infinity: a valid answer, EARHIP_OK.
+ *
+ * Out of scope: K-weighting coefficients for other sample rates, any normalisation of the output gain, any file I/O.
  * ---------------------------------------------------------------------- */
 typedef struct earhip_loudness earhip_loudness;
 /* sample_rate: a multiple of 10.  coeffs: [2][5] = b0 b1 b2 a1 a2 per stage, or NULL = the table above, which is allowed at
@@ -843,9 +871,21 @@ typedef struct earhip_loudness earhip_loudness;
  * with everything else the meter needs: a process call allocates nothing and synchronises nothing. */
 int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs,
                            size_t max_steps, earhip_loudness **out);
+/* The same meter with true peak.  tp == NULL is earhip_loudness_create exactly: such a meter runs and costs what it did.
+ * tp->coeffs: [phases][taps], phases in [1, 8], taps in [1, 64], every coefficient finite (else EARHIP_INVALID_ARGUMENT), or
+ * NULL = the table above (phases and taps are then ignored), which is allowed at 44100 and 48000 only.  The history, the
+ * per-step peak stores [max_steps + 1][n_channels] and the table are made here: a process call still allocates nothing and
+ * synchronises nothing. */
+typedef struct earhip_true_peak {
+  int phases;
+  int taps;
+  const double *coeffs;
+} earhip_true_peak;
+int earhip_loudness_create_tp(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs,
+                              size_t max_steps, const earhip_true_peak *tp, earhip_loudness **out);
 /* (detach it from its renderers first: earhip_render_attach_loudness(r, NULL)) */
 int earhip_loudness_destroy(earhip_loudness *m);
-int earhip_loudness_reset(earhip_loudness *m); /* state, clock and steps to zero */
+int earhip_loudness_reset(earhip_loudness *m); /* state, clock, steps, true-peak history and peaks to zero */
 /* planar float32 rows in device memory (channel c at rows_dev + c * stride), any nsamples >= 0 (no block size, no alignment);
  * enqueues on the context's stream, does not synchronise.  A call that would pass max_steps is EARHIP_INVALID_ARGUMENT and
  * consumes nothing. */
@@ -858,6 +898,15 @@ int earhip_loudness_steps(earhip_loudness *m, size_t first, size_t n, double *en
 /* the gating above over all finished steps; weights [n_channels]; any output pointer may be NULL; synchronises */
 int earhip_loudness_result(earhip_loudness *m, const double *weights, double *integrated,
                            double *max_momentary, double *max_short_term);
+/* True and sample peak so far per channel [n_channels], the unfinished step included; either pointer may be NULL;
+ * synchronises.  The step stores are reduced on the device (one small kernel over ten rows per second of programme) and
+ * 2 x n_channels numbers come back.  EARHIP_INVALID_ARGUMENT on a meter made without true peak, as for earhip_loudness_step_peaks. */
+int earhip_loudness_peaks(earhip_loudness *m, float *true_peak, float *sample_peak);
+/* [n][n_channels] each, of steps [first, first + n), which must be finished; either pointer may be NULL; synchronises */
+int earhip_loudness_step_peaks(earhip_loudness *m, size_t first, size_t n, float *true_peak, float *sample_peak);
+/* loudness range over all finished steps (LU; low and high in LKFS); any output pointer may be NULL; synchronises */
+int earhip_loudness_result_range(earhip_loudness *m, const double *weights, double *lra, double *low,
+                                 double *high);
 /* Pure host functions, no context and no device.  Like the host forms of group K they are a deliberate CPU computation on a
  * few numbers, not a fall-back of the device path.
  * earhip_loudness_gate is what a multi-GPU render (group J) uses: after the reduce-scatter each rank owns whole channels of
@@ -868,10 +917,15 @@ int earhip_loudness_gate(size_t n_steps, int n_channels, const double *energy /*
                          double *max_short_term);
 /* weights [n_channels of the full layout, LFE channels included]; an unknown name is EARHIP_UNKNOWN_LAYOUT */
 int earhip_loudness_layout_weights(const char *layout, double *weights);
+/* loudness range of step energies, pure host like earhip_loudness_gate and joined over ranks the same way.  (Peak columns
+ * of the ranks' meters join by concatenation too: a channel's peaks do not depend on the other channels of its meter.) */
+int earhip_loudness_range(size_t n_steps, int n_channels, const double *energy /* [n_steps][n_channels] */,
+                          const double *weights, double *lra, double *low, double *high);
 /* From now on every process call of r, of EVERY form, feeds its float32 output samples to m on the device, behind its kernels
  * on the context's stream: the samples earhip_render_process_frames would hand back, before any PCM conversion or dither.
  * m == NULL detaches.  m must have n_out channels and the renderer's context (else EARHIP_INVALID_ARGUMENT).
- * earhip_render_reset does not touch m (a programme may be rendered in several passes); earhip_loudness_reset does.  A call
+ * earhip_render_reset does not touch m, its true-peak history and peaks included (a programme may be rendered in several
+ * passes); earhip_loudness_reset does.  A call
  * that would pass m's max_steps fails with EARHIP_INVALID_ARGUMENT before anything is rendered.  A call that runs as two spans
  * or as a pipeline of chunks is metered once per sample.  Without a meter the render paths are what they were. */
 int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m);

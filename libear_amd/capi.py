@@ -998,6 +998,21 @@ def loudness_gate(energy, weights):
     return tuple(v.value for v in out)
 
 
+def loudness_range(energy, weights):
+    """step energies [steps][channels] and channel weights -> (LRA in LU, low, high in LKFS) by EBU Tech 3342; (0, -inf, -inf)
+    where no short-term window survives the gates; on the calling thread, no device"""
+    w = _f64(weights).reshape(-1)
+    e = _f64(energy).reshape(-1, w.size)
+    out = [C.c_double(0) for _ in range(3)]
+    check(load().earhip_loudness_range(C.c_size_t(e.shape[0]), C.c_int(w.size), C.c_void_p(e.ctypes.data), C.c_void_p(w.ctypes.data),
+                                       *[C.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+class _TruePeak(C.Structure):
+    _fields_ = [("phases", C.c_int), ("taps", C.c_int), ("coeffs", C.c_void_p)]
+
+
 def loudness_layout_weights(layout):
     """BS.1770-4's channel weights of a BS.2051 layout, float64 [channels of the full layout] (LFE channels 0)"""
     n = C.c_int(0)
@@ -1008,15 +1023,31 @@ def loudness_layout_weights(layout):
 
 
 class Loudness:
-    """(L) the meter: K-weighted 100 ms step energies kept on the device, gated on request."""
+    """(L) the meter: K-weighted 100 ms step energies kept on the device, gated on request.  true_peak=True also measures
+    true and sample peak with BS.1770-4's 4 x 12 interpolator (44100 and 48000 Hz); (phases, taps, coeffs [phases][taps]) brings
+    another table."""
 
-    def __init__(self, ctx, n_channels, sample_rate=48000, max_steps=36000, coeffs=None):
+    def __init__(self, ctx, n_channels, sample_rate=48000, max_steps=36000, coeffs=None, true_peak=False):
         self.ctx, self.C = ctx, n_channels
         c = None if coeffs is None else _f64(coeffs).reshape(2, 5)
         self.h = C.c_void_p()
-        check(load().earhip_loudness_create(ctx.h, C.c_int(n_channels), C.c_int(sample_rate),
-                                            None if c is None else C.c_void_p(c.ctypes.data), C.c_size_t(max_steps),
-                                            C.byref(self.h)))
+        kc = None if c is None else C.c_void_p(c.ctypes.data)
+        if true_peak is False or true_peak is None:
+            check(load().earhip_loudness_create(ctx.h, C.c_int(n_channels), C.c_int(sample_rate), kc, C.c_size_t(max_steps),
+                                                C.byref(self.h)))
+            return
+        if true_peak is True:
+            tp = _TruePeak(0, 0, None)
+        else:
+            phases, taps, table = true_peak
+            table = _f64(table).reshape(-1)
+            if table.size != max(int(phases), 0) * max(int(taps), 0):
+                raise InvalidArgument(INVALID_ARGUMENT, "the true-peak table must be [phases][taps]")
+            if table.size == 0:
+                table = np.zeros(1)  # (a table, not the default: the library refuses its shape)
+            tp = _TruePeak(int(phases), int(taps), table.ctypes.data)
+        check(load().earhip_loudness_create_tp(ctx.h, C.c_int(n_channels), C.c_int(sample_rate), kc, C.c_size_t(max_steps),
+                                               C.byref(tp), C.byref(self.h)))
 
     def process(self, x):
         """x [channels][n] host array, any n"""
@@ -1045,6 +1076,28 @@ class Loudness:
         w = _f64(weights).reshape(self.C)
         out = [C.c_double(0) for _ in range(3)]
         check(load().earhip_loudness_result(self.h, C.c_void_p(w.ctypes.data), *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
+
+    def peaks(self):
+        """(true peak [channels], sample peak [channels]) so far, linear float32, the unfinished step included"""
+        t, s = np.zeros(self.C, np.float32), np.zeros(self.C, np.float32)
+        check(load().earhip_loudness_peaks(self.h, C.c_void_p(t.ctypes.data), C.c_void_p(s.ctypes.data)))
+        return t, s
+
+    def step_peaks(self, first=0, n=None):
+        """(true peak, sample peak), [n][channels] float32 each, of the finished steps [first, first + n) (default: all from first)"""
+        if n is None:
+            n = self.num_steps() - first
+        t, s = np.zeros((n, self.C), np.float32), np.zeros((n, self.C), np.float32)
+        check(load().earhip_loudness_step_peaks(self.h, C.c_size_t(first), C.c_size_t(n), C.c_void_p(t.ctypes.data),
+                                                C.c_void_p(s.ctypes.data)))
+        return t, s
+
+    def range(self, weights):
+        """(LRA in LU, low, high in LKFS) over all finished steps (EBU Tech 3342)"""
+        w = _f64(weights).reshape(self.C)
+        out = [C.c_double(0) for _ in range(3)]
+        check(load().earhip_loudness_result_range(self.h, C.c_void_p(w.ctypes.data), *[C.byref(v) for v in out]))
         return tuple(v.value for v in out)
 
     def reset(self):

@@ -1,11 +1,13 @@
-// api_loudness.hip — group L of include/earhip.h: programme loudness (ITU-R BS.1770-4) measured on the device.  The kernels:
-// loudness_kernels.h; the maths they share with the host functions and the CPU tests: loudness.h.
+// api_loudness.hip — group L of include/earhip.h: programme loudness (ITU-R BS.1770-4), true peak (its annex 2) and loudness
+// range (EBU Tech 3342) measured on the device.  The kernels: loudness_kernels.h, true_peak_kernels.h; the maths they share
+// with the host functions and the CPU tests: loudness.h, true_peak.h.
 #include <cstring>
 #include <memory>
 
 #include "common.h"
 #include "layout_table.h"
 #include "loudness_kernels.h"
+#include "true_peak_kernels.h"
 
 using namespace earhip;
 
@@ -22,6 +24,14 @@ struct earhip_loudness {
   static constexpr size_t kStage = 65536;
   PinBuf<float> p_stage;
   DevBuf<float> d_stage;
+  // true peak (a meter made with a table): also made at create
+  bool tp_on = false;
+  int tp_phases = 0, tp_taps = 0;
+  float tp_h[4][12];                // the table where its shape is 4 x 12
+  DevBuf<float> tp_table, tp_hist;  // [phases][taps]; [2][C][kTpHist], read [par], written [par ^ 1]
+  DevBuf<unsigned> tp_steps, sp_steps;  // [max_steps + 1][C]: the row behind the finished steps is the open step's
+  DevBuf<unsigned> tp_totals;           // [2][C]: what earhip_loudness_peaks reduces the stores to
+  PinBuf<float> p_totals;
 
   size_t max_launch() const { return (size_t)(kLoudMaxChunks - 1) * (size_t)L; }
   size_t num_steps() const { return (size_t)(clock / (unsigned long long)step); }
@@ -35,8 +45,37 @@ struct earhip_loudness {
     EARHIP_HIP(hipMemsetAsync(state.p, 0, sizeof(double) * state.n, ctx->stream));
     EARHIP_HIP(hipMemsetAsync(open.p, 0, sizeof(double) * open.n, ctx->stream));
     EARHIP_HIP(hipMemsetAsync(steps.p, 0, sizeof(double) * steps.n, ctx->stream));
+    if (tp_on) {
+      EARHIP_HIP(hipMemsetAsync(tp_hist.p, 0, sizeof(float) * tp_hist.n, ctx->stream));
+      EARHIP_HIP(hipMemsetAsync(tp_steps.p, 0, sizeof(unsigned) * tp_steps.n, ctx->stream));
+      EARHIP_HIP(hipMemsetAsync(sp_steps.p, 0, sizeof(unsigned) * sp_steps.n, ctx->stream));
+    }
     clock = 0;
     par = 0;
+  }
+
+  // the true-peak pass over one launch's samples: it reads what the loudness passes read and shares nothing else with them
+  void launch_true_peak(size_t n, const float *rows, size_t stride) {
+    TpArgs t;
+    t.rows = rows;
+    t.stride = stride;
+    t.n = (unsigned)n;
+    t.C = C;
+    t.r0 = (unsigned)(clock % (unsigned long long)step);
+    t.step = (unsigned)step;
+    t.step0 = clock / (unsigned long long)step;
+    t.hist_in = tp_hist.p + (size_t)par * (size_t)C * kTpHist;
+    t.hist_out = tp_hist.p + (size_t)(par ^ 1) * (size_t)C * kTpHist;
+    t.tp = tp_steps.p, t.sp = sp_steps.p;
+    t.phases = tp_phases, t.taps = tp_taps;
+    t.table = tp_table.p;
+    std::memcpy(t.h, tp_h, sizeof(tp_h));
+    if (tp_phases == 4 && tp_taps == 12)
+      hipLaunchKernelGGL(k_true_peak_4x12, dim3((unsigned)((n + kTpBlockTile - 1) / kTpBlockTile), (unsigned)C), dim3(64 * kTpWaves), 0,
+                         ctx->stream, t);
+    else
+      hipLaunchKernelGGL(k_true_peak_any, dim3((unsigned)((n + kTpAnyTile - 1) / kTpAnyTile), (unsigned)C), dim3(kTpAnyTile), 0,
+                         ctx->stream, t);
   }
 
   void launch(size_t n, const float *rows, size_t stride) {
@@ -58,6 +97,7 @@ struct earhip_loudness {
     a.steps = steps.p;
     a.step_samples = (double)step;
     if (a.nchunks > (unsigned)kLoudMaxChunks) fail_internal("loudness launch beyond its scratch");
+    if (tp_on) launch_true_peak(n, rows, stride);
     const unsigned touched = (a.chunk0_in_step + a.nchunks + a.cps - 1) / a.cps;
     const dim3 grid((a.nchunks + 63) / 64, (unsigned)C);
     hipLaunchKernelGGL(k_loudness_pass<false>, grid, dim3(64), 0, ctx->stream, a);
@@ -91,6 +131,11 @@ extern "C" {
 
 int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs, size_t max_steps,
                            earhip_loudness **out) {
+  return earhip_loudness_create_tp(ctx, n_channels, sample_rate, coeffs, max_steps, nullptr, out);
+}
+
+int earhip_loudness_create_tp(earhip_ctx *ctx, int n_channels, int sample_rate, const double *coeffs, size_t max_steps,
+                              const earhip_true_peak *tp, earhip_loudness **out) {
   return guarded([&] {
     require(ctx != nullptr && out != nullptr, "ctx and out must not be NULL");
     require(n_channels >= 1 && n_channels <= 65535, "n_channels must be in [1, 65535]");
@@ -98,6 +143,27 @@ int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, con
     require(coeffs != nullptr || sample_rate == 48000,
             "the built-in K-weighting coefficients are those of 48000 Hz: another rate must bring its own");
     require(max_steps >= 1 && max_steps <= ((size_t)1 << 32) / (size_t)n_channels, "max_steps out of range");
+    std::vector<float> table;
+    int phases = 4, taps = 12;
+    if (tp) {
+      if (tp->coeffs) {
+        phases = tp->phases, taps = tp->taps;
+        require(phases >= 1 && phases <= kTpMaxPhases, "true peak: phases must be in [1, 8]");
+        require(taps >= 1 && taps <= kTpMaxTaps, "true peak: taps must be in [1, 64]");
+        table.resize((size_t)phases * (size_t)taps);
+        for (size_t i = 0; i < table.size(); i++) {
+          require(std::isfinite(tp->coeffs[i]) && std::isfinite((float)tp->coeffs[i]), "true peak: coefficients must be finite");
+          table[i] = (float)tp->coeffs[i];
+        }
+      } else {
+        require(sample_rate == 44100 || sample_rate == 48000,
+                "the built-in true-peak table is 4x oversampling for 44100 and 48000 Hz: another rate must bring its own");
+        double h[4][12];
+        true_peak_default_table(h);
+        table.resize(48);
+        for (int i = 0; i < 48; i++) table[(size_t)i] = (float)h[i / 12][i % 12];
+      }
+    }
     ctx->use();
     std::unique_ptr<earhip_loudness> m(new earhip_loudness);
     m->ctx = ctx;
@@ -127,6 +193,19 @@ int earhip_loudness_create(earhip_ctx *ctx, int n_channels, int sample_rate, con
     m->Q.alloc(Q.size());
     EARHIP_HIP(hipMemcpy(m->P.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice));
     EARHIP_HIP(hipMemcpy(m->Q.p, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice));
+    if (tp) {
+      m->tp_on = true;
+      m->tp_phases = phases, m->tp_taps = taps;
+      if (phases == 4 && taps == 12) std::memcpy(m->tp_h, table.data(), sizeof(m->tp_h));
+      else std::memset(m->tp_h, 0, sizeof(m->tp_h));
+      m->tp_table.alloc(table.size());
+      EARHIP_HIP(hipMemcpy(m->tp_table.p, table.data(), sizeof(float) * table.size(), hipMemcpyHostToDevice));
+      m->tp_hist.alloc(2 * C * kTpHist);
+      m->tp_steps.alloc((max_steps + 1) * C);
+      m->sp_steps.alloc((max_steps + 1) * C);
+      m->tp_totals.alloc(2 * C);
+      m->p_totals.reserve(2 * C);
+    }
     m->p_stage.reserve(C * earhip_loudness::kStage);
     m->d_stage.alloc(C * earhip_loudness::kStage);
     m->zero();
@@ -217,6 +296,60 @@ int earhip_loudness_result(earhip_loudness *m, const double *weights, double *in
     if (n) EARHIP_HIP(hipMemcpyAsync(en.data(), m->steps.p, sizeof(double) * n * (size_t)m->C, hipMemcpyDeviceToHost, m->ctx->stream));
     EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
     loudness_gate(n, m->C, en.data(), weights, integrated, max_momentary, max_short_term);
+  });
+}
+
+int earhip_loudness_peaks(earhip_loudness *m, float *true_peak, float *sample_peak) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    require(m->tp_on, "the meter was made without true peak (earhip_loudness_create_tp)");
+    m->ctx->use();
+    // every finished step and the open one, reduced on the device: 2 x C numbers come back, whatever the programme's length
+    const size_t C = (size_t)m->C;
+    hipLaunchKernelGGL(k_true_peak_totals, dim3((unsigned)C, 2), dim3(256), 0, m->ctx->stream, m->tp_steps.p, m->sp_steps.p,
+                       (unsigned long long)(m->num_steps() + 1), m->C, m->tp_totals.p);
+    EARHIP_HIP(hipGetLastError());
+    EARHIP_HIP(hipMemcpyAsync(m->p_totals.p, m->tp_totals.p, sizeof(float) * 2 * C, hipMemcpyDeviceToHost, m->ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+    if (true_peak) std::memcpy(true_peak, m->p_totals.p, sizeof(float) * C);
+    if (sample_peak) std::memcpy(sample_peak, m->p_totals.p + C, sizeof(float) * C);
+  });
+}
+
+int earhip_loudness_step_peaks(earhip_loudness *m, size_t first, size_t n, float *true_peak, float *sample_peak) {
+  return guarded([&] {
+    require(m != nullptr, "meter must not be NULL");
+    require(m->tp_on, "the meter was made without true peak (earhip_loudness_create_tp)");
+    require(first <= m->num_steps() && n <= m->num_steps() - first, "steps [first, first + n) are not all finished");
+    if (n == 0) return;
+    m->ctx->use();
+    const size_t C = (size_t)m->C;
+    if (true_peak)
+      EARHIP_HIP(hipMemcpyAsync(true_peak, m->tp_steps.p + first * C, sizeof(float) * n * C, hipMemcpyDeviceToHost, m->ctx->stream));
+    if (sample_peak)
+      EARHIP_HIP(hipMemcpyAsync(sample_peak, m->sp_steps.p + first * C, sizeof(float) * n * C, hipMemcpyDeviceToHost, m->ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+  });
+}
+
+int earhip_loudness_range(size_t n_steps, int n_channels, const double *energy, const double *weights, double *lra, double *low,
+                          double *high) {
+  return guarded([&] {
+    require(n_channels >= 1, "n_channels must be >= 1");
+    require(weights != nullptr && (n_steps == 0 || energy != nullptr), "energy and weights must not be NULL");
+    loudness_range(n_steps, n_channels, energy, weights, lra, low, high);
+  });
+}
+
+int earhip_loudness_result_range(earhip_loudness *m, const double *weights, double *lra, double *low, double *high) {
+  return guarded([&] {
+    require(m != nullptr && weights != nullptr, "meter and weights must not be NULL");
+    m->ctx->use();
+    const size_t n = m->num_steps();
+    std::vector<double> en(std::max<size_t>(n * (size_t)m->C, 1));
+    if (n) EARHIP_HIP(hipMemcpyAsync(en.data(), m->steps.p, sizeof(double) * n * (size_t)m->C, hipMemcpyDeviceToHost, m->ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(m->ctx->stream));
+    loudness_range(n, m->C, en.data(), weights, lra, low, high);
   });
 }
 

@@ -11,6 +11,7 @@
 //   - the powers of Phi (made once, in long double, by running the cascade on the unit states with no input);
 //   - the gating of BS.1770-4 over 100 ms step energies, and the channel weights of a BS.2051 layout.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <limits>
@@ -207,6 +208,42 @@ inline void loudness_gate(size_t n_steps, int n_channels, const double *energy, 
   if (integrated) *integrated = L;
   if (max_momentary) *max_momentary = mom;
   if (max_short_term) *max_short_term = st;
+}
+
+// ---- loudness range (EBU Tech 3342) over the same step energies --------------------------------------------------------------
+// Short-term windows (30 steps, hop one), gated at -70 LKFS and at 20 LU below the level of the mean power of what passed that;
+// the survivors sorted, LRA = the 95th less the 10th percentile, each the element at floor((n - 1) p + 0.5).
+inline void loudness_range(size_t n_steps, int n_channels, const double *energy, const double *weights, double *lra, double *low,
+                           double *high) {
+  const double ninf = -std::numeric_limits<double>::infinity();
+  double r = 0.0, lo = ninf, hi = ninf;
+  if (n_steps >= 30) {
+    const size_t nw = n_steps - 29;
+    std::vector<double> P(nw), l(nw);
+    double sum = 0.0;
+    size_t cnt = 0;
+    for (size_t j = 0; j < nw; j++) {
+      P[j] = loudness_window_power(energy, n_channels, weights, j, 30);
+      l[j] = loudness_of_power(P[j]);
+      if (l[j] > -70.0) sum += P[j], cnt++;
+    }
+    if (cnt) {
+      const double gamma = loudness_of_power(sum / (double)cnt) - 20.0;
+      std::vector<double> s;
+      for (size_t j = 0; j < nw; j++)
+        if (l[j] > -70.0 && l[j] > gamma) s.push_back(l[j]);
+      if (!s.empty()) {
+        std::sort(s.begin(), s.end());
+        const double n1 = (double)(s.size() - 1);
+        lo = s[(size_t)std::floor(n1 * 0.10 + 0.5)];
+        hi = s[(size_t)std::floor(n1 * 0.95 + 0.5)];
+        r = hi - lo;
+      }
+    }
+  }
+  if (lra) *lra = r;
+  if (low) *low = lo;
+  if (high) *high = hi;
 }
 
 // the weight G of a channel at a nominal position (BS.1770-4 table 4): 0 for an LFE channel, 1.41 where |elevation| < 30 and
