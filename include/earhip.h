@@ -930,6 +930,80 @@ int earhip_loudness_range(size_t n_steps, int n_channels, const double *energy /
  * or as a pipeline of chunks is metered once per sample.  Without a meter the render paths are what they were. */
 int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m);
 
+/* ------------------------------------------------------------------------
+ * (M) FIR filter matrix — n_in rows to n_out rows through one FIR filter per (output, input) pair, on the device.  libear has
+ * no counterpart beyond one BlockConvolver per pair (group C): with n_out = 2 and one HRIR / BRIR pair per loudspeaker this is
+ * virtual-loudspeaker binaural monitoring of the render's bus while it is still in device memory; a diagonal matrix is
+ * per-loudspeaker EQ / alignment; a narrow one is a filtered fold-down.  The caller brings the impulse responses.
+ *
+ * The operation, exactly (a caller can reproduce it):
+ *     y[k][n] = sum over c < n_in, j < n_taps of  h[k][c][j] * x[c][n - j]
+ *   - n runs on the object's own sample clock; x is zero before create and reset.  Inputs, taps and outputs are float32 and
+ *     the arithmetic is float32.
+ *   - METHOD: uniformly partitioned convolution at the block size B, P = ceil(n_taps / B) partitions (the last zero-padded),
+ *     overlap-save on windows of 2B samples [x_{t-1} | x_t].  No latency beyond the filters: output block t is complete when
+ *     input block t has been fed.  The forward transform of a window is taken ONCE and kept in a ring for the P - 1 blocks
+ *     that follow; the products H[k][c][p] X[c][t - p] are summed over c and p in the frequency domain; there is one inverse
+ *     transform per (PAIR of outputs, block) — outputs 2g and 2g + 1 ride through it as real and imaginary part.
+ *   - ZERO PAIRS: a pair (k, c) whose taps are all zero (+0.0 or -0.0) is dropped at create.  A diagonal 24 x 24 matrix costs
+ *     24 pairs, not 576.  The drop is observable: an input channel with no non-zero pair is never read (a NaN in it reaches
+ *     no output), and an output with no non-zero pair is exactly +0.0.  A non-finite sample in a
+ *     channel that IS read may reach every output, as 0 * NaN would in the formula.
+ *   - ORDER: per frequency bin and output, an inner sum over p ascending (fused multiply-adds from zero) for each input
+ *     channel, added to a running sum over c ascending.  No atomics: the same sequence of calls gives the same bits.
+ *   - CUTS: a stream may be cut into calls in any way, always in whole blocks.  Different cuts agree within the accuracy of
+ *     the method (tests: relative error per output channel <= 1.5 x that of one libear BlockConvolver per pair summed in
+ *     float32); bit-identity across different cuts is NOT promised.  (Today every block has a transform of its own — unlike
+ *     the decorrelators' kernel, which sends two consecutive blocks of a call through one complex transform, so that which
+ *     blocks pair depends on where a call starts — but a faster pairing of blocks must stay possible.)
+ * Everything is made at create: the filters' spectra [pairs][P][B] complex, the ring of input spectra
+ * [channels read][max_blocks + P - 1][B] complex, one block of input per channel (double-buffered: the workgroups of a call's
+ * last block rewrite it), and rows for max_blocks of the host form.  A process call allocates nothing and synchronises nothing.
+ *
+ * Out of scope: block sizes that are not powers of two (480, 960, ...), replacing or crossfading filters while running (head
+ * tracking), HRIR data sets and SOFA files, interleaved PCM of the matrix's output, K-weighting of the monitor output (run a
+ * second earhip_loudness over the sink), a multi-GPU matrix (after the exchange a rank owns whole channels and the matrix needs
+ * all of them: run it on the gathering rank).
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_firmix earhip_firmix;
+typedef struct earhip_firmix_config {
+  int n_in;           /* [1, 64] */
+  int n_out;          /* [1, 64] */
+  int block_size;     /* B: a power of two in [64, 4096] */
+  int n_taps;         /* [1, 64 * B]: at most 64 partitions, as the renderer's decorrelators */
+  const float *taps;  /* [n_out][n_in][n_taps], every one finite */
+  int max_blocks;     /* >= 1: the longest process call */
+} earhip_firmix_config;
+/* anything outside the limits above is EARHIP_INVALID_ARGUMENT */
+int earhip_firmix_create(earhip_ctx *ctx, const earhip_firmix_config *config, earhip_firmix **out);
+/* (detach it from its renderers first: earhip_render_attach_firmix(r, NULL, NULL, 0, 0)) */
+int earhip_firmix_destroy(earhip_firmix *fm);
+int earhip_firmix_reset(earhip_firmix *fm); /* state and clock to zero */
+/* info = n_in, n_out, B, partitions, non-zero pairs */
+int earhip_firmix_info(const earhip_firmix *fm, int info[5]);
+/* planar float32 rows in device memory: input channel c at in_dev + c * in_stride, output k at out_dev + k * out_stride,
+ * nblocks * B samples each, nblocks <= max_blocks (else EARHIP_INVALID_ARGUMENT, and nothing is consumed); enqueues on the
+ * context's stream, does not synchronise.  Rows beyond the call's samples and other rows are left alone. */
+int earhip_firmix_process_device(earhip_firmix *fm, size_t nblocks, const float *in_dev, size_t in_stride,
+                                 float *out_dev, size_t out_stride);
+/* host rows in[n_in], out[n_out] (the pointer of an input channel that is never read is not looked at); H2D + the above +
+ * D2H; synchronises */
+int earhip_firmix_process(earhip_firmix *fm, size_t nblocks, const float *const *in, float *const *out);
+/* From now on every process call of r, of EVERY form, feeds its float32 output rows to fm on the device, behind its kernels on
+ * the context's stream and where an attached loudness meter is fed: the samples earhip_render_process_frames would hand back,
+ * before any PCM conversion or dither.  fm's n_out rows go to sink_dev[k * sink_stride + position], position = the samples fed
+ * since the attach (a host counter: the feeds are enqueued in order).  The sink is the caller's: device memory, or
+ * earhip_host_alloc memory that a host caller reads after earhip_ctx_synchronize without a copy call.
+ * fm must have the renderer's context, n_in = the renderer's n_out and its block size; sink_stride >= sink_capacity (else
+ * EARHIP_INVALID_ARGUMENT).  A call that would pass sink_capacity, or fm's max_blocks, fails with EARHIP_INVALID_ARGUMENT
+ * before anything is rendered.  A call that runs as two spans or as a pipeline of chunks is fed once per sample.
+ * fm == NULL detaches (the other arguments are ignored); attaching again rewinds the position to 0.  A meter and a matrix may
+ * be attached together.  earhip_render_reset does not touch fm; earhip_firmix_reset does.  Without a matrix the render paths
+ * are what they were. */
+int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink_dev, size_t sink_stride,
+                                size_t sink_capacity);
+int earhip_render_firmix_position(earhip_render *r, size_t *samples);
+
 #ifdef __cplusplus
 }
 #endif

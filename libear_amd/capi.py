@@ -975,6 +975,21 @@ class Renderer:
         check(load().earhip_render_attach_loudness(self.h, meter.h if meter is not None else None))
         self._meter = meter  # (kept alive while attached)
 
+    def attach_fir_matrix(self, fm, sink_ptr=None, sink_stride=0, sink_capacity=0):
+        """every process call of every form feeds its float32 output rows to `fm` (a FirMatrix with n_in = n_out of this
+        renderer, its block size and its context) on the device; fm's rows go to sink_ptr[k * sink_stride + position] (device
+        memory or a Context.pinned_array's address); None detaches (include/earhip.h: earhip_render_attach_firmix)"""
+        check(load().earhip_render_attach_firmix(self.h, fm.h if fm is not None else None,
+                                                 C.c_void_p(sink_ptr) if sink_ptr else None, C.c_size_t(sink_stride),
+                                                 C.c_size_t(sink_capacity)))
+        self._fir_matrix = fm  # (kept alive while attached)
+
+    def fir_matrix_position(self):
+        """samples fed to the attached FirMatrix since the attach = where its next row samples go in the sink"""
+        v = C.c_size_t(0)
+        check(load().earhip_render_firmix_position(self.h, C.byref(v)))
+        return v.value
+
     def close(self):
         if self.h:
             load().earhip_render_destroy(self.h)
@@ -1106,4 +1121,54 @@ class Loudness:
     def close(self):
         if self.h:
             load().earhip_loudness_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+# (M) FIR filter matrix
+
+class _FirmixConfig(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("block_size", C.c_int), ("n_taps", C.c_int), ("taps", C.c_void_p),
+                ("max_blocks", C.c_int)]
+
+
+class FirMatrix:
+    """(M) taps [K][C][J] float32: K outputs from C inputs through one J-tap FIR per pair, partitioned at block_size; pairs whose
+    taps are all zero cost nothing and their input channels are never read."""
+
+    def __init__(self, ctx, taps, block_size, max_blocks=1):
+        taps = _f32(taps)
+        if taps.ndim != 3:
+            raise InvalidArgument(INVALID_ARGUMENT, "taps must be [n_out][n_in][n_taps]")
+        self.ctx = ctx
+        self.K, self.C, self.J = (int(v) for v in taps.shape)
+        self.B = int(block_size)
+        cfg = _FirmixConfig(self.C, self.K, self.B, self.J, taps.ctypes.data if taps.size else None, int(max_blocks))
+        self.h = C.c_void_p()
+        check(load().earhip_firmix_create(ctx.h, C.byref(cfg), C.byref(self.h)))
+
+    def process(self, x):
+        """x [C][nblocks * B] host array -> [K][nblocks * B]"""
+        x = _f32(x).reshape(self.C, -1)
+        nblocks = x.shape[1] // self.B
+        assert nblocks * self.B == x.shape[1], "whole blocks"
+        out = np.empty((self.K, x.shape[1]), np.float32)
+        check(load().earhip_firmix_process(self.h, C.c_size_t(nblocks), _chan_ptrs(x), _chan_ptrs(out)))
+        return out
+
+    def process_device(self, nblocks, in_ptr, in_stride, out_ptr, out_stride):
+        """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); enqueues on the context's stream"""
+        check(load().earhip_firmix_process_device(self.h, C.c_size_t(nblocks), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                                  C.c_void_p(out_ptr), C.c_size_t(out_stride)))
+
+    def info(self):
+        out = (C.c_int * 5)()
+        check(load().earhip_firmix_info(self.h, out))
+        return {"n_in": out[0], "n_out": out[1], "block_size": out[2], "partitions": out[3], "pairs": out[4]}
+
+    def reset(self):
+        check(load().earhip_firmix_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_firmix_destroy(self.h)
             self.h = C.c_void_p()

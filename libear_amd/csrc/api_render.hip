@@ -466,11 +466,27 @@ struct earhip_render {
   void check_meter(size_t nblocks) const {
     if (meter) loudness_check_room(meter, nblocks * (size_t)B);
   }
+  // An attached FIR matrix (earhip_render_attach_firmix) reads the same rows at the same place and writes its own rows to the
+  // caller's sink at fm_pos, a host counter: the feeds are enqueued in order.
+  earhip_firmix *fm = nullptr;
+  float *fm_sink = nullptr;
+  size_t fm_sink_stride = 0, fm_sink_cap = 0, fm_pos = 0;
+  void check_firmix(size_t nblocks) const {
+    if (!fm) return;
+    firmix_check_room(fm, nblocks);
+    if (fm_pos + nblocks * (size_t)B > fm_sink_cap)
+      fail_invalid("the call would pass the FIR matrix's sink_capacity (nothing was rendered)");
+  }
   void process_device(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
-    if (!meter) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
-    loudness_check_room(meter, nblocks * (size_t)B);
+    if (!meter && !fm) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
+    if (meter) loudness_check_room(meter, nblocks * (size_t)B);
+    check_firmix(nblocks);
     render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
-    loudness_feed(meter, nblocks * (size_t)B, out_dev, out_stride);
+    if (meter) loudness_feed(meter, nblocks * (size_t)B, out_dev, out_stride);
+    if (fm) {
+      firmix_feed(fm, nblocks, out_dev, out_stride, fm_sink + fm_pos, fm_sink_stride);
+      fm_pos += nblocks * (size_t)B;
+    }
   }
   void render_spans(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
     MixLaunch whole;  // the plan of the uncut call, made once (process_span takes it as it is)
@@ -806,6 +822,31 @@ int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m) {
   });
 }
 
+int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
+  return guarded([&] {
+    require(r != nullptr, "render must not be NULL");
+    if (fm) {
+      require(firmix_ctx(fm) == r->ctx, "the FIR matrix must belong to the renderer's context");
+      require(firmix_inputs(fm) == r->N, "the FIR matrix must have n_in = the renderer's n_out");
+      require(firmix_block(fm) == r->B, "the FIR matrix must have the renderer's block size");
+      require(sink_dev != nullptr, "sink_dev must not be NULL");
+      require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
+    }
+    r->fm = fm;
+    r->fm_sink = fm ? sink_dev : nullptr;
+    r->fm_sink_stride = fm ? sink_stride : 0;
+    r->fm_sink_cap = fm ? sink_capacity : 0;
+    r->fm_pos = 0;
+  });
+}
+
+int earhip_render_firmix_position(earhip_render *r, size_t *samples) {
+  return guarded([&] {
+    require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
+    *samples = r->fm_pos;
+  });
+}
+
 int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *in_dev,
                                  size_t in_stride, float *out_dev, size_t out_stride) {
   return guarded([&] {
@@ -813,6 +854,7 @@ int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *
     require(in_dev != nullptr && out_dev != nullptr, "device pointers must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
     r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
+    r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
     require(in_stride >= nblocks * r->B && out_stride >= nblocks * r->B, "stride too small");
     if (nblocks == 0) return;
     r->ctx->use();
@@ -827,6 +869,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     require(in != nullptr && out != nullptr, "in and out must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
     r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
+    r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
     if (nblocks == 0) return;
     earhip_ctx *ctx = r->ctx;
     ctx->use();
@@ -995,6 +1038,7 @@ static void check_frames_args(const earhip_render *r, size_t nblocks, const void
   require((int64_t)first_channel + r->M <= (int64_t)frame_channels, "first_channel + n_objects exceeds frame_channels");
   require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
   r->check_meter(nblocks);
+  r->check_firmix(nblocks);
   require(fmt == EARHIP_PCM_S24 || reinterpret_cast<uintptr_t>(frames) % (uintptr_t)S == 0, "frames not aligned to the sample size");
 }
 

@@ -209,3 +209,15 @@ void loudness_feed(earhip_loudness *m, size_t nsamples, const float *rows, size_
 const earhip_ctx *loudness_ctx(const earhip_loudness *m);
 int loudness_channels(const earhip_loudness *m);
 }  // namespace earhip
+
+struct earhip_firmix;
+namespace earhip {
+// the FIR filter matrix (api_firmix.hip) as the renderer's tap sees it (earhip_render_attach_firmix): does a call of nblocks fit
+// its scratch (throws EARHIP_INVALID_ARGUMENT), and its two passes over planar device rows on the context's stream
+void firmix_check_room(const earhip_firmix *fm, size_t nblocks);
+void firmix_feed(earhip_firmix *fm, size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride);
+const earhip_ctx *firmix_ctx(const earhip_firmix *fm);
+int firmix_inputs(const earhip_firmix *fm);
+int firmix_outputs(const earhip_firmix *fm);
+int firmix_block(const earhip_firmix *fm);
+}  // namespace earhip

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <vector>
 #include "../hip.hpp"
+#include "../hip_firmix.hpp"
 #include "../hip_loudness.hpp"
 
 namespace ear {
@@ -171,6 +172,21 @@ namespace ear {
       /// the attachment.  reset() leaves the meter alone.
       void attach_loudness(hip::LoudnessMeter &meter) { hip::check(earhip_render_attach_loudness(h_, meter.get())); }
       void detach_loudness() { hip::check(earhip_render_attach_loudness(h_, nullptr)); }
+      /// From now on every process call of every form also feeds its float32 output rows to `matrix` on the device; the matrix's
+      /// rows go to sink[k * sink_stride + position], position = the samples fed since the attach (fir_matrix_position()).  The
+      /// sink is the caller's: device memory, or hip::Context::alloc_host memory read after synchronize().  The matrix must have
+      /// n_out inputs, this renderer's block size and context, and outlive the attachment.  A call that would pass
+      /// sink_capacity or the matrix's max_blocks throws ear::invalid_argument before anything is rendered.  reset() leaves the
+      /// matrix alone.
+      void attach_fir_matrix(hip::FirMatrix &matrix, float *sink, size_t sink_stride, size_t sink_capacity) {
+        hip::check(earhip_render_attach_firmix(h_, matrix.get(), sink, sink_stride, sink_capacity));
+      }
+      void detach_fir_matrix() { hip::check(earhip_render_attach_firmix(h_, nullptr, nullptr, 0, 0)); }
+      size_t fir_matrix_position() const {
+        size_t n = 0;
+        hip::check(earhip_render_firmix_position(h_, &n));
+        return n;
+      }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
       size_t block_size() const { return block_size_; }
 
