@@ -960,8 +960,35 @@ int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m);
  * [channels read][max_blocks + P - 1][B] complex, one block of input per channel (double-buffered: the workgroups of a call's
  * last block rewrite it), and rows for max_blocks of the host form.  A process call allocates nothing and synchronises nothing.
  *
- * Out of scope: block sizes that are not powers of two (480, 960, ...), replacing or crossfading filters while running (head
- * tracking), HRIR data sets and SOFA files, interleaved PCM of the matrix's output, K-weighting of the monitor output (run a
+ * FILTER SETS (earhip_firmix_create_sets): a matrix may be made with room for n_sets filter sets of one shape (n_out, n_in,
+ * n_taps, B), of which one is CURRENT at any time, and switched or crossfaded between them while it runs: a binaural monitor
+ * that follows the listener's head, an EQ that is retuned.  The ring of input spectra does not depend on the filters, so
+ * another set is applied to the SAME history: no restart, no cut-off tail, no second forward transform.  Exactly:
+ *   - with y_s = h_s * x the formula above under set s over the WHOLE input history since create / reset,
+ *     earhip_firmix_select(fm, set, F) makes the output, from the next block fed, go from the current set (`from`) to `set`
+ *     (`to`) over F blocks:
+ *         fade block q in [0, F), sample n in [0, B):  a = (float)(q B + n) / (float)(F B),
+ *                                                      y = (1 - a) y_from + a y_to   in float32, each operation rounded
+ *         every block after the fade:                  y = y_to
+ *     F = 0 is a hard switch at the block boundary.  The ramp starts at 0 and never reaches 1 inside the fade, as libear's
+ *     fade_down_and_up.
+ *   - DIFFERENCE FROM libear's BlockConvolver::crossfade_filter: libear fades on the INPUT side — an input block is faded
+ *     between the two filters and its tail rings out under the filter it arrived under.  Here the fade is on the OUTPUT side
+ *     and both filters see the whole history: after the fade the output is exactly that of a matrix that had the new set
+ *     from the start.
+ *   - a fade's progress is a host integer: it runs on across calls, across the chunks of a render call that runs as a
+ *     pipeline and across the two spans of a cut call.  The steady blocks of a call run through the same kernels, on the
+ *     same ring and clock and in the same order of summation as a plain matrix: before a select and after a fade the output
+ *     has the bits of earhip_firmix_create matrices of those sets fed the same calls.
+ *   - an output with no non-zero pair in the set(s) applied to a block contributes exactly +0.0 there.
+ *   - AGAINST earhip_firmix_create: the set selected next is not known at create, so every input channel has a ring row:
+ *     every in[c] of the host form is looked at (none may be NULL) and every channel is read.  A NaN in a channel reaches no
+ *     output WHILE NO SET IN USE (current, or being faded from) has a non-zero pair on it.  Everything any later call needs is
+ *     made at create: spectra for every set at full width [n_sets][n_out n_in][P][B] complex, per-set pair lists, a pinned
+ *     staging buffer for one set of taps.  earhip_firmix_create itself is what it was.
+ *
+ * Out of scope: block sizes that are not powers of two (480, 960, ...), interpolating HRIRs between measured directions, HRIR
+ * data sets and SOFA files, interleaved PCM of the matrix's output, K-weighting of the monitor output (run a
  * second earhip_loudness over the sink), a multi-GPU matrix (after the exchange a rank owns whole channels and the matrix needs
  * all of them: run it on the gathering rank).
  * ---------------------------------------------------------------------- */
@@ -978,8 +1005,9 @@ typedef struct earhip_firmix_config {
 int earhip_firmix_create(earhip_ctx *ctx, const earhip_firmix_config *config, earhip_firmix **out);
 /* (detach it from its renderers first: earhip_render_attach_firmix(r, NULL, NULL, 0, 0)) */
 int earhip_firmix_destroy(earhip_firmix *fm);
-int earhip_firmix_reset(earhip_firmix *fm); /* state and clock to zero */
-/* info = n_in, n_out, B, partitions, non-zero pairs */
+/* state and clock to zero; a fade ends at once (its target is current); loaded sets stay loaded */
+int earhip_firmix_reset(earhip_firmix *fm);
+/* info = n_in, n_out, B, partitions, non-zero pairs (of the current set) */
 int earhip_firmix_info(const earhip_firmix *fm, int info[5]);
 /* planar float32 rows in device memory: input channel c at in_dev + c * in_stride, output k at out_dev + k * out_stride,
  * nblocks * B samples each, nblocks <= max_blocks (else EARHIP_INVALID_ARGUMENT, and nothing is consumed); enqueues on the
@@ -989,6 +1017,26 @@ int earhip_firmix_process_device(earhip_firmix *fm, size_t nblocks, const float 
 /* host rows in[n_in], out[n_out] (the pointer of an input channel that is never read is not looked at); H2D + the above +
  * D2H; synchronises */
 int earhip_firmix_process(earhip_firmix *fm, size_t nblocks, const float *const *in, float *const *out);
+/* Filter sets (FILTER SETS above).  n_sets in [1, 4096]; config->taps becomes set 0, which is current; the other sets are
+ * unloaded.  Limits as earhip_firmix_create. */
+int earhip_firmix_create_sets(earhip_ctx *ctx, const earhip_firmix_config *config, int n_sets, earhip_firmix **out);
+/* taps: host [n_out][n_in][n_taps], every one finite.  The set's all-zero pairs are dropped as at create.  Stages the taps and
+ * enqueues their forward transforms on the context's stream, behind every call enqueued so far; may wait for an earlier load's
+ * staging copy: not a call for the audio thread.  EARHIP_INVALID_ARGUMENT, and nothing changed: a set that is current or being
+ * faded from, a set index out of range, a non-finite tap, a matrix made by earhip_firmix_create. */
+int earhip_firmix_load_set(earhip_firmix *fm, int set, const float *taps);
+/* the same with the taps in device memory (interpolated there, say): no pair is dropped, the host never sees the taps, and
+ * finiteness is the caller's duty.  Neither allocates nor synchronises; taps_dev is read on the stream. */
+int earhip_firmix_load_set_device(earhip_firmix *fm, int set, const float *taps_dev);
+/* fade_blocks F in [0, 64].  Host bookkeeping only: no allocation, no synchronisation, no launch.  EARHIP_INVALID_ARGUMENT, and
+ * nothing changed: an unloaded set, a set index out of range, F out of range, a select while a fade has started and not
+ * finished (state[2] in [1, F)).  A select before any block of the previous select was fed replaces it (`from` stays).
+ * Selecting the current set while no fade runs is a no-op.  While a fade is pending or running its target is `current`. */
+int earhip_firmix_select(earhip_firmix *fm, int set, int fade_blocks);
+/* state = current set, set being faded from (-1: none), fade blocks done, fade blocks in all */
+int earhip_firmix_state(const earhip_firmix *fm, int state[4]);
+/* info = loaded (0 / 1), non-zero pairs */
+int earhip_firmix_set_info(const earhip_firmix *fm, int set, int info[2]);
 /* From now on every process call of r, of EVERY form, feeds its float32 output rows to fm on the device, behind its kernels on
  * the context's stream and where an attached loudness meter is fed: the samples earhip_render_process_frames would hand back,
  * before any PCM conversion or dither.  fm's n_out rows go to sink_dev[k * sink_stride + position], position = the samples fed
@@ -998,7 +1046,8 @@ int earhip_firmix_process(earhip_firmix *fm, size_t nblocks, const float *const 
  * EARHIP_INVALID_ARGUMENT).  A call that would pass sink_capacity, or fm's max_blocks, fails with EARHIP_INVALID_ARGUMENT
  * before anything is rendered.  A call that runs as two spans or as a pipeline of chunks is fed once per sample.
  * fm == NULL detaches (the other arguments are ignored); attaching again rewinds the position to 0.  A meter and a matrix may
- * be attached together.  earhip_render_reset does not touch fm; earhip_firmix_reset does.  Without a matrix the render paths
+ * be attached together.  earhip_render_reset does not touch fm; earhip_firmix_reset does.  earhip_firmix_select and
+ * earhip_firmix_load_set between render calls act on the next block fed.  Without a matrix the render paths
  * are what they were. */
 int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink_dev, size_t sink_stride,
                                 size_t sink_capacity);

@@ -1133,18 +1133,54 @@ class _FirmixConfig(C.Structure):
 
 class FirMatrix:
     """(M) taps [K][C][J] float32: K outputs from C inputs through one J-tap FIR per pair, partitioned at block_size; pairs whose
-    taps are all zero cost nothing and their input channels are never read."""
+    taps are all zero cost nothing and their input channels are never read.  n_sets: room for that many filter sets of this shape
+    (earhip_firmix_create_sets: `taps` is set 0 and current; load_set / select switch and crossfade while it runs); None: a plain
+    matrix (earhip_firmix_create)."""
 
-    def __init__(self, ctx, taps, block_size, max_blocks=1):
+    def __init__(self, ctx, taps, block_size, max_blocks=1, n_sets=None):
         taps = _f32(taps)
         if taps.ndim != 3:
             raise InvalidArgument(INVALID_ARGUMENT, "taps must be [n_out][n_in][n_taps]")
+        if n_sets is not None and (isinstance(n_sets, bool) or not isinstance(n_sets, (int, np.integer))):
+            raise InvalidArgument(INVALID_ARGUMENT, "n_sets must be an integer or None")
         self.ctx = ctx
         self.K, self.C, self.J = (int(v) for v in taps.shape)
         self.B = int(block_size)
         cfg = _FirmixConfig(self.C, self.K, self.B, self.J, taps.ctypes.data if taps.size else None, int(max_blocks))
         self.h = C.c_void_p()
-        check(load().earhip_firmix_create(ctx.h, C.byref(cfg), C.byref(self.h)))
+        self.n_sets = None if n_sets is None else int(n_sets)
+        if n_sets is None:
+            check(load().earhip_firmix_create(ctx.h, C.byref(cfg), C.byref(self.h)))
+        else:
+            check(load().earhip_firmix_create_sets(ctx.h, C.byref(cfg), C.c_int(self.n_sets), C.byref(self.h)))
+
+    def load_set(self, index, taps):
+        """host taps [K][C][J] become set `index` (not the current set, nor one being faded from); enqueues the transforms"""
+        taps = _f32(taps)
+        if taps.shape != (self.K, self.C, self.J):
+            raise InvalidArgument(INVALID_ARGUMENT, "taps must have the shape the matrix was made with")
+        check(load().earhip_firmix_load_set(self.h, C.c_int(int(index)), C.c_void_p(taps.ctypes.data)))
+
+    def load_set_device(self, index, taps_ptr):
+        """the same from float32 [K][C][J] in device memory (e.g. a torch tensor's data_ptr()): no pair is dropped, nothing is
+        allocated or synchronised"""
+        if not taps_ptr:
+            raise InvalidArgument(INVALID_ARGUMENT, "taps_ptr must not be NULL")
+        check(load().earhip_firmix_load_set_device(self.h, C.c_int(int(index)), C.c_void_p(taps_ptr)))
+
+    def select(self, index, fade_blocks=0):
+        """from the next block fed, go to set `index` over fade_blocks blocks (0: a hard switch): host bookkeeping only"""
+        check(load().earhip_firmix_select(self.h, C.c_int(int(index)), C.c_int(int(fade_blocks))))
+
+    def state(self):
+        out = (C.c_int * 4)()
+        check(load().earhip_firmix_state(self.h, out))
+        return {"current": out[0], "from": out[1], "done": out[2], "total": out[3]}
+
+    def set_info(self, index):
+        out = (C.c_int * 2)()
+        check(load().earhip_firmix_set_info(self.h, C.c_int(int(index)), out))
+        return {"loaded": bool(out[0]), "pairs": out[1]}
 
     def process(self, x):
         """x [C][nblocks * B] host array -> [K][nblocks * B]"""

@@ -124,4 +124,99 @@ inline FirmixPlan firmix_make_plan(int n_in, int n_out, int block, int n_taps, i
   return p;
 }
 
+// ---- filter sets (earhip_firmix_create_sets) ------------------------------------------------------------------------------
+// A matrix with room for n_sets filter sets of one shape.  Which set comes next is not known at create, so every input channel
+// has a ring row (row = channel) and every set has spectra at full width: pair (k, c) of a set is block k n_in + c of the
+// set's slice [n_out n_in][P][B], whether it is in the set's lists or not.  The lists are per set, with room for a dense set.
+constexpr int kFirmixMaxSets = 4096, kFirmixMaxFade = 64;
+
+struct FirmixSetLists {
+  int n_pairs = 0;
+  std::vector<int> group_start;      // [groups + 1] into entries
+  std::vector<FirmixEntry> entries;  // per group, ascending channel; row = channel, h = k n_in + c
+};
+inline size_t firmix_set_entries_room(int n_in, int n_out) { return (size_t)((n_out + 1) / 2) * (size_t)n_in; }
+
+// taps [n_out][n_in][n_taps]: all-zero pairs are dropped as in firmix_make_plan; taps == nullptr (the taps are in device
+// memory, the host never sees them): no pair is dropped
+inline FirmixSetLists firmix_make_set_lists(int n_in, int n_out, int n_taps, const float *taps) {
+  FirmixSetLists s;
+  const int groups = (n_out + 1) / 2;
+  auto nonzero = [&](int k, int c) {
+    if (k >= n_out) return false;
+    if (!taps) return true;
+    const float *h = taps + ((size_t)k * (size_t)n_in + (size_t)c) * (size_t)n_taps;
+    for (int j = 0; j < n_taps; j++)
+      if (h[j] != 0.0f) return true;
+    return false;
+  };
+  for (int g = 0; g < groups; g++) {
+    s.group_start.push_back((int)s.entries.size());
+    for (int c = 0; c < n_in; c++) {
+      const bool z0 = nonzero(2 * g, c), z1 = nonzero(2 * g + 1, c);
+      FirmixEntry e;
+      e.row = c;
+      e.h0 = z0 ? (2 * g) * n_in + c : -1;
+      e.h1 = z1 ? (2 * g + 1) * n_in + c : -1;
+      s.n_pairs += (z0 ? 1 : 0) + (z1 ? 1 : 0);
+      if (z0 || z1) s.entries.push_back(e);
+    }
+  }
+  s.group_start.push_back((int)s.entries.size());
+  return s;
+}
+
+// One step of the walk over the merged ascending channel lists of two sets (the fade kernel reads each X[c] once for both):
+// the next channel that either list has, with the spectra of its up to four pairs (-1: none), and both cursors moved on.
+struct FirmixMerged {
+  int row, a0, a1, b0, b1;
+};
+EARHIP_FIRMIX_HD inline FirmixMerged firmix_merge_step(const FirmixEntry *ea, int &ia, int ea_end, const FirmixEntry *eb, int &ib,
+                                                       int eb_end) {
+  const int ra = ia < ea_end ? ea[ia].row : 0x7fffffff, rb = ib < eb_end ? eb[ib].row : 0x7fffffff;
+  FirmixMerged m;
+  m.row = ra < rb ? ra : rb;
+  m.a0 = m.a1 = m.b0 = m.b1 = -1;
+  if (ra == m.row) m.a0 = ea[ia].h0, m.a1 = ea[ia].h1, ia++;
+  if (rb == m.row) m.b0 = eb[ib].h0, m.b1 = eb[ib].h1, ib++;
+  return m;
+}
+
+// The fade schedule: host integers, advanced by every feed (a process call, a chunk of a pipelined render call, a span).
+//   select(set, F): from the next block fed, `total` = F blocks go from the set that was current to `set`; afterwards `set`
+//   alone.  While a fade is pending or running `current` is its target and `from` the set it leaves.
+struct FirmixFade {
+  int current = 0, from = -1, done = 0, total = 0;
+};
+// nullptr when select(set, F) is accepted, else why not (EARHIP_INVALID_ARGUMENT, nothing changed); loaded: [n_sets]
+inline const char *firmix_select_check(const FirmixFade &f, int n_sets, const char *loaded, int set, int F) {
+  if (set < 0 || set >= n_sets) return "set index out of range";
+  if (F < 0 || F > kFirmixMaxFade) return "fade_blocks must be in [0, 64]";
+  if (!loaded[set]) return "the set is not loaded";
+  if (f.from >= 0 && f.done > 0) return "a fade has started and not finished";
+  return nullptr;
+}
+// an accepted select.  A select before any block of the previous one was fed replaces it: `from` stays.
+inline void firmix_select_apply(FirmixFade &f, int set, int F) {
+  const int from = f.from >= 0 ? f.from : f.current;
+  f.current = set;
+  f.done = 0;
+  if (F == 0 || set == from) f.from = -1, f.total = 0;  // a hard switch at the block boundary / nothing to fade between
+  else f.from = from, f.total = F;
+}
+// how many of the next n blocks are fade blocks: always the first ones of a feed
+EARHIP_FIRMIX_HD inline int firmix_fade_blocks(int from, int done, int total, int n) {
+  if (from < 0) return 0;
+  return n < total - done ? n : total - done;
+}
+inline void firmix_fade_advance(FirmixFade &f, int nfade) {
+  f.done += nfade;
+  if (f.from >= 0 && f.done >= f.total) f.from = -1, f.done = 0, f.total = 0;
+}
+inline void firmix_fade_end(FirmixFade &f) { f.from = -1, f.done = 0, f.total = 0; }  // reset: the target is current
+// a set that may not be loaded now: the current one (a fade's target included) and the one being faded from
+inline bool firmix_set_in_use(const FirmixFade &f, int set) { return set == f.current || set == f.from; }
+// the weight of the target at sample n of fade block q of F blocks of B: starts at 0, never reaches 1 (q B + n < 2^24: exact)
+EARHIP_FIRMIX_HD inline float firmix_fade_gain(int q, int n, int F, int B) { return (float)(q * B + n) / (float)(F * B); }
+
 }  // namespace earhip
