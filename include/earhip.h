@@ -1053,6 +1053,97 @@ int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink
                                 size_t sink_capacity);
 int earhip_render_firmix_position(earhip_render *r, size_t *samples);
 
+/* ------------------------------------------------------------------------
+ * (N) Look-ahead true-peak limiter — the last stage of a delivery chain, on the device.  libear has no counterpart.  The meter
+ * of group L and the levels of group F can tell that a render passes -1 dBTP or clips an s16 file; this stage brings the bus
+ * under a ceiling while it is still in device memory, with ONE gain for all channels, so that the spatial image is kept.
+ *
+ * The operation, exactly (a caller can reproduce it).  C channels, one object clock n since create / reset, x zero before the
+ * clock starts.  All arithmetic is float32, each operation rounded once; nothing is contracted beyond the interpolator's
+ * explicit fused multiply-adds (the library is built with -ffp-contract=off).  c is the ceiling, L the look-ahead, H the hold.
+ *   1. DETECTOR.  detect = 1 (true peak): y_c[phases n + p] is the interpolator of group L bit for bit (the same table rules,
+ *      the same order of taps), D = taps / 2 in integer division (6 for the annex 2 table), and
+ *          e[n] = max over c of max(|x_c[n - D]|, max over p of |y_c[phases n + p]|).
+ *      The interleaved 48-tap filter delays by 5.875 samples: y[4n .. 4n + 3] lies between x[n - 6] and x[n - 5], and D lines
+ *      the two up.  detect = 0 (sample peak only): D = 0 and e[n] = max over c of |x_c[n]|.  The max ignores NaN, as the
+ *      meter's does.
+ *   2. REQUIRED GAIN.  r[n] = min(1, c / e[n]), the division one correctly rounded float32 division; e = 0 gives r = 1.
+ *   3. SLIDING MINIMUM.  m[n] = min over i in [0, M) of r[n - i], M = L + 2 + H; r = 1 before the clock starts.  (The + 2 where
+ *      + 1 would cover the look-ahead lets the window of output sample x[j] include the r of the inter-sample interval on BOTH
+ *      its sides.)  min is exact: any algorithm gives the same bits.
+ *   4. SMOOTHING.  s[n] = m[n] + m[n - 1] + .. + m[n - L]: K = L + 1 terms, added in that order starting from +0.0f with
+ *      plain float32 adds;  g[n] = min(s[n] / (float)K, r[n - L]).  The outer min is a mathematical no-op (every m[n - k],
+ *      k <= L, has r[n - L] in its window); it makes the guarantee below hold in float32 without a K 2^-24 slack.
+ *   5. OUTPUT.  out_c[n] = x_c[n - D - L] g[n].  The latency is D + L samples (earhip_limiter_latency).  There is no flush call:
+ *      a caller that wants the tail feeds D + L zeros.
+ * GUARANTEE: for finite input |out_c[n]| <= c (1 + 2^-22) for every sample: g[n] <= r[n - L] <= fl(c / e[n - L]) and
+ * |x_c[n - D - L]| <= e[n - L].  The TRUE peak of the output is not bounded exactly by any gain-riding limiter (modulating the
+ * gain moves inter-sample peaks); for this design it is a measured property: at most 1.0021 c for L >= 64 on the tests'
+ * signals, 1.0001 c for L = 240.
+ * CUTS: any nsamples >= 0 per call, no block size.  Not one bit of out or g depends on how the stream is cut into calls,
+ * launches, tiles or pipeline chunks (the fixed order of summation and the exact min).  The history — max(D + L, taps - 1)
+ * samples per channel and M - 1 + L values of r, double-buffered — is carried exactly and made at create.
+ * NON-FINITE INPUT: a NaN is ignored by the detector and passes through as NaN in its own channel only; +-infinity gives
+ * r = 0 (the infinite sample itself comes out as inf x 0 = NaN).  Neither is guarded by extra passes.
+ * STATISTICS: min_gain is the smallest g so far (1 if there was none below 1), limited_samples the number of n with g[n] < 1;
+ * positive floats order like their bit patterns and the count is an integer, so both are independent of order and cuts.
+ *
+ * Out of scope: per-channel (unlinked) gains, exponential or programme-dependent release, oversampled gain application,
+ * loudness normalisation, a multi-GPU limiter (the linked gain needs every channel: run it on the gathering rank), PCM from
+ * the attached form (call earhip_limiter_process_pcm_device on rows instead).
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_limiter earhip_limiter;
+typedef struct earhip_limiter_config {
+  int n_channels;              /* [1, 64] */
+  int sample_rate;             /* > 0; with detect = 1 and no table of the caller's: 44100 or 48000 only, as the meter */
+  float ceiling;               /* c: finite, > 0 (0.8913 = -1 dBTP) */
+  int lookahead;               /* L in [8, 1024] samples */
+  int hold;                    /* H in [0, 8192] samples */
+  int detect;                  /* 0 sample peak | 1 true peak */
+  const earhip_true_peak *tp;  /* detect = 1: NULL (or coeffs == NULL) = annex 2; else as earhip_loudness_create_tp */
+  size_t max_samples;          /* >= 1: the longest process call */
+} earhip_limiter_config;
+/* Everything is made here: a process call allocates nothing and synchronises nothing.  Anything outside the limits above is
+ * EARHIP_INVALID_ARGUMENT. */
+int earhip_limiter_create(earhip_ctx *ctx, const earhip_limiter_config *config, earhip_limiter **out);
+/* (detach it from its renderers first: earhip_render_attach_limiter(r, NULL, NULL, 0, 0)) */
+int earhip_limiter_destroy(earhip_limiter *lim);
+int earhip_limiter_reset(earhip_limiter *lim); /* history, clock, stats and levels to zero */
+int earhip_limiter_latency(const earhip_limiter *lim, int *samples); /* D + L */
+/* planar float32 rows in device memory: channel c at in_dev + c * in_stride and out_dev + c * out_stride, nsamples each; the
+ * rows of in and out must not overlap.  gain_dev: [nsamples] g, or NULL.  nsamples > max_samples is EARHIP_INVALID_ARGUMENT
+ * and nothing is consumed.  Enqueues on the context's stream, does not synchronise. */
+int earhip_limiter_process_device(earhip_limiter *lim, size_t nsamples, const float *in_dev, size_t in_stride,
+                                  float *out_dev, size_t out_stride, float *gain_dev);
+/* host rows in[n_channels], out[n_channels], gain [nsamples] or NULL: H2D + the above + D2H; synchronises */
+int earhip_limiter_process(earhip_limiter *lim, size_t nsamples, const float *const *in, float *const *out,
+                           float *gain);
+/* The limited rows as interleaved PCM frames in device memory: the conversion rules, argument checks and dither of group F
+ * (earhip_render_process_frames_pcm_device), with n_channels in the place of n_out, through rows made at create.  The dither's
+ * t is the limiter's own output clock.  The levels are the limiter's own (earhip_limiter_output_levels): with c < 1, clipped
+ * stays 0 for s24 / s32 and for s16 without dither. */
+int earhip_limiter_process_pcm_device(earhip_limiter *lim, size_t nsamples, const float *in_dev, size_t in_stride,
+                                      void *out_dev, size_t out_frame_bytes, size_t out_first_byte,
+                                      const earhip_pcm_out *out);
+/* as earhip_render_output_levels, of the PCM form above: peak, clipped [n_channels]; synchronises */
+int earhip_limiter_output_levels(earhip_limiter *lim, float *peak, uint64_t *clipped, int reset);
+/* STATISTICS above; synchronises */
+int earhip_limiter_stats(earhip_limiter *lim, float *min_gain, uint64_t *limited_samples, int reset);
+/* From now on every process call of r, of EVERY form, feeds its float32 output rows to lim on the device, behind its kernels on
+ * the context's stream and behind an attached loudness meter and FIR matrix, which both keep seeing the UNLIMITED bus: the
+ * samples earhip_render_process_frames would hand back, before any PCM conversion or dither.  lim's n_channels rows go to
+ * sink_dev[c * sink_stride + position], position = the samples fed since the attach (a host counter: the feeds are enqueued in
+ * order).  The sink is the caller's: device memory, or earhip_host_alloc memory that a host caller reads after
+ * earhip_ctx_synchronize without a copy call.  lim must have the renderer's context and n_channels = the renderer's n_out;
+ * sink_stride >= sink_capacity (else EARHIP_INVALID_ARGUMENT).  There is no block-size condition: a feed is nblocks * B
+ * samples.  A call that would pass sink_capacity, or lim's max_samples, fails with EARHIP_INVALID_ARGUMENT before anything is
+ * rendered.  A call that runs as two spans or as a pipeline of chunks is fed once per sample.  lim == NULL detaches (the
+ * other arguments are ignored); attaching again rewinds the position to 0.  earhip_render_reset does not touch lim;
+ * earhip_limiter_reset does.  Without a limiter the render paths are what they were. */
+int earhip_render_attach_limiter(earhip_render *r, earhip_limiter *lim, float *sink_dev, size_t sink_stride,
+                                 size_t sink_capacity);
+int earhip_render_limiter_position(earhip_render *r, size_t *samples);
+
 #ifdef __cplusplus
 }
 #endif

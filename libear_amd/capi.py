@@ -990,6 +990,21 @@ class Renderer:
         check(load().earhip_render_firmix_position(self.h, C.byref(v)))
         return v.value
 
+    def attach_limiter(self, lim, sink_ptr=None, sink_stride=0, sink_capacity=0):
+        """every process call of every form feeds its float32 output rows to `lim` (a Limiter of n_out channels on this context)
+        on the device, behind an attached meter and FIR matrix, which keep seeing the unlimited bus; the limited rows go to
+        sink_ptr[c * sink_stride + position]; None detaches (include/earhip.h: earhip_render_attach_limiter)"""
+        check(load().earhip_render_attach_limiter(self.h, lim.h if lim is not None else None,
+                                                  C.c_void_p(sink_ptr) if sink_ptr else None, C.c_size_t(sink_stride),
+                                                  C.c_size_t(sink_capacity)))
+        self._limiter = lim  # (kept alive while attached)
+
+    def limiter_position(self):
+        """samples fed to the attached Limiter since the attach = where its next row samples go in the sink"""
+        v = C.c_size_t(0)
+        check(load().earhip_render_limiter_position(self.h, C.byref(v)))
+        return v.value
+
     def close(self):
         if self.h:
             load().earhip_render_destroy(self.h)
@@ -1207,4 +1222,94 @@ class FirMatrix:
     def close(self):
         if self.h:
             load().earhip_firmix_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+# (N) look-ahead true-peak limiter
+
+class _LimiterConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("sample_rate", C.c_int), ("ceiling", C.c_float), ("lookahead", C.c_int),
+                ("hold", C.c_int), ("detect", C.c_int), ("tp", C.c_void_p), ("max_samples", C.c_size_t)]
+
+
+class Limiter:
+    """(N) one gain for all channels that keeps every output sample under `ceiling`, looking `lookahead` samples ahead and
+    holding `hold` samples; true_peak=True detects on BS.1770-4's 4 x 12 interpolator (44100 and 48000 Hz), (phases, taps,
+    coeffs [phases][taps]) brings another table, False detects sample peaks only.  The output is delayed by latency() samples."""
+
+    def __init__(self, ctx, n_channels, ceiling, lookahead=64, hold=480, sample_rate=48000, true_peak=True, max_samples=48000):
+        for name, v in (("n_channels", n_channels), ("lookahead", lookahead), ("hold", hold), ("sample_rate", sample_rate),
+                        ("max_samples", max_samples)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise InvalidArgument(INVALID_ARGUMENT, f"{name} must be an integer")
+        if int(max_samples) < 0:
+            raise InvalidArgument(INVALID_ARGUMENT, "max_samples must be >= 1")
+        self.ctx, self.C = ctx, int(n_channels)
+        self.max_samples = int(max_samples)
+        tp = None
+        if true_peak is not True and true_peak is not False and true_peak is not None:
+            phases, taps, table = true_peak
+            table = _f64(table).reshape(-1)
+            if table.size != max(int(phases), 0) * max(int(taps), 0):
+                raise InvalidArgument(INVALID_ARGUMENT, "the true-peak table must be [phases][taps]")
+            if table.size == 0:
+                table = np.zeros(1)  # (a table, not the default: the library refuses its shape)
+            self._table = table
+            tp = _TruePeak(int(phases), int(taps), table.ctypes.data)
+        cfg = _LimiterConfig(self.C, int(sample_rate), float(ceiling), int(lookahead), int(hold), 1 if true_peak else 0,
+                             C.cast(C.pointer(tp), C.c_void_p) if tp is not None else None, self.max_samples)
+        self.h = C.c_void_p()
+        check(load().earhip_limiter_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(self.h)))
+
+    def latency(self):
+        v = C.c_int(0)
+        check(load().earhip_limiter_latency(self.h, C.byref(v)))
+        return v.value
+
+    def process(self, x, with_gain=False):
+        """x [channels][n] host array, any n -> the limited rows [channels][n] (and the gain row [n])"""
+        x = _f32(x)
+        if x.ndim != 2 or x.shape[0] != self.C:
+            raise InvalidArgument(INVALID_ARGUMENT, "x must be [channels][n]")
+        n = x.shape[1]
+        out = np.empty((self.C, n), np.float32)
+        g = np.empty(n, np.float32) if with_gain else None
+        check(load().earhip_limiter_process(self.h, C.c_size_t(n), _chan_ptrs(x), _chan_ptrs(out), _ptr(g) if with_gain else None))
+        return (out, g) if with_gain else out
+
+    def process_device(self, nsamples, in_ptr, in_stride, out_ptr, out_stride, gain_ptr=None):
+        """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); gain_ptr: [nsamples] or None; enqueues on the
+        context's stream"""
+        check(load().earhip_limiter_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                                   C.c_void_p(out_ptr), C.c_size_t(out_stride),
+                                                   C.c_void_p(gain_ptr) if gain_ptr else None))
+
+    def process_pcm_device(self, nsamples, in_ptr, in_stride, out_ptr, out_frame_bytes, out_first_byte=0, out_fmt="s16",
+                           dither=False, seed=0):
+        """the limited rows as PCM frames: bytes [out_first_byte, + channels * sample size) of each output frame of
+        out_frame_bytes in device memory, every other byte is left alone; enqueues on the context's stream"""
+        ocode = pcm_format(out_fmt)[0] if isinstance(out_fmt, str) else int(out_fmt)
+        spec = PcmOut(ocode, int(dither), int(seed) & 0xFFFFFFFF)
+        check(load().earhip_limiter_process_pcm_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                                       C.c_void_p(out_ptr), C.c_size_t(out_frame_bytes),
+                                                       C.c_size_t(out_first_byte), C.byref(spec)))
+
+    def output_levels(self, reset=False):
+        """(peak float32 [channels], clipped uint64 [channels]) of the samples that went through process_pcm_device"""
+        peak, clipped = np.zeros(self.C, np.float32), np.zeros(self.C, np.uint64)
+        check(load().earhip_limiter_output_levels(self.h, _ptr(peak), C.c_void_p(clipped.ctypes.data), int(bool(reset))))
+        return peak, clipped
+
+    def stats(self, reset=False):
+        """(the smallest gain so far as numpy float32, the number of samples with a gain below 1)"""
+        g, n = C.c_float(1.0), C.c_uint64(0)
+        check(load().earhip_limiter_stats(self.h, C.byref(g), C.byref(n), int(bool(reset))))
+        return np.float32(g.value), n.value
+
+    def reset(self):
+        check(load().earhip_limiter_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_limiter_destroy(self.h)
             self.h = C.c_void_p()

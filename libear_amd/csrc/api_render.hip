@@ -477,15 +477,31 @@ struct earhip_render {
     if (fm_pos + nblocks * (size_t)B > fm_sink_cap)
       fail_invalid("the call would pass the FIR matrix's sink_capacity (nothing was rendered)");
   }
+  // An attached limiter (earhip_render_attach_limiter) reads the same rows behind the meter and the matrix, which both see the
+  // unlimited bus, and writes the limited rows to its own sink at lim_pos.
+  earhip_limiter *lim = nullptr;
+  float *lim_sink = nullptr;
+  size_t lim_sink_stride = 0, lim_sink_cap = 0, lim_pos = 0;
+  void check_limiter(size_t nblocks) const {
+    if (!lim) return;
+    limiter_check_room(lim, nblocks * (size_t)B);
+    if (lim_pos + nblocks * (size_t)B > lim_sink_cap)
+      fail_invalid("the call would pass the limiter's sink_capacity (nothing was rendered)");
+  }
   void process_device(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
-    if (!meter && !fm) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
+    if (!meter && !fm && !lim) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
     if (meter) loudness_check_room(meter, nblocks * (size_t)B);
     check_firmix(nblocks);
+    check_limiter(nblocks);
     render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
     if (meter) loudness_feed(meter, nblocks * (size_t)B, out_dev, out_stride);
     if (fm) {
       firmix_feed(fm, nblocks, out_dev, out_stride, fm_sink + fm_pos, fm_sink_stride);
       fm_pos += nblocks * (size_t)B;
+    }
+    if (lim) {
+      limiter_feed(lim, nblocks * (size_t)B, out_dev, out_stride, lim_sink + lim_pos, lim_sink_stride);
+      lim_pos += nblocks * (size_t)B;
     }
   }
   void render_spans(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
@@ -847,6 +863,30 @@ int earhip_render_firmix_position(earhip_render *r, size_t *samples) {
   });
 }
 
+int earhip_render_attach_limiter(earhip_render *r, earhip_limiter *lim, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
+  return guarded([&] {
+    require(r != nullptr, "render must not be NULL");
+    if (lim) {
+      require(limiter_ctx(lim) == r->ctx, "the limiter must belong to the renderer's context");
+      require(limiter_channels(lim) == r->N, "the limiter must have n_channels = the renderer's n_out");
+      require(sink_dev != nullptr, "sink_dev must not be NULL");
+      require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
+    }
+    r->lim = lim;
+    r->lim_sink = lim ? sink_dev : nullptr;
+    r->lim_sink_stride = lim ? sink_stride : 0;
+    r->lim_sink_cap = lim ? sink_capacity : 0;
+    r->lim_pos = 0;
+  });
+}
+
+int earhip_render_limiter_position(earhip_render *r, size_t *samples) {
+  return guarded([&] {
+    require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
+    *samples = r->lim_pos;
+  });
+}
+
 int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *in_dev,
                                  size_t in_stride, float *out_dev, size_t out_stride) {
   return guarded([&] {
@@ -855,6 +895,7 @@ int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
     r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
     r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
+    r->check_limiter(nblocks);  // (and for an attached limiter and its sink)
     require(in_stride >= nblocks * r->B && out_stride >= nblocks * r->B, "stride too small");
     if (nblocks == 0) return;
     r->ctx->use();
@@ -870,6 +911,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
     r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
     r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
+    r->check_limiter(nblocks);  // (and for an attached limiter and its sink)
     if (nblocks == 0) return;
     earhip_ctx *ctx = r->ctx;
     ctx->use();
@@ -1039,6 +1081,7 @@ static void check_frames_args(const earhip_render *r, size_t nblocks, const void
   require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
   r->check_meter(nblocks);
   r->check_firmix(nblocks);
+  r->check_limiter(nblocks);
   require(fmt == EARHIP_PCM_S24 || reinterpret_cast<uintptr_t>(frames) % (uintptr_t)S == 0, "frames not aligned to the sample size");
 }
 
@@ -1484,3 +1527,13 @@ int earhip_render_last_plan(const earhip_render *r, int out[4]) {
 }
 
 }  // extern "C"
+
+// group F's PCM conversion for the limiter's PCM form (common.h)
+namespace earhip {
+size_t pcm_out_check(const earhip_pcm_out *out) { return check_pcm_out(out); }
+int pcm_level_slots() { return kLevelSlots; }
+void pcm_out_rows(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out, size_t frame_bytes,
+                  size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s) {
+  launch_rows_to_pcm(o, in, in_stride, N, len, out, frame_bytes, first_byte, peak, clipped, t0, s);
+}
+}  // namespace earhip

@@ -221,3 +221,20 @@ int firmix_inputs(const earhip_firmix *fm);
 int firmix_outputs(const earhip_firmix *fm);
 int firmix_block(const earhip_firmix *fm);
 }  // namespace earhip
+
+struct earhip_limiter;
+namespace earhip {
+// the look-ahead limiter (api_limiter.hip) as the renderer's tap sees it (earhip_render_attach_limiter): does a call of nsamples
+// fit its scratch (throws EARHIP_INVALID_ARGUMENT), and its two passes over planar device rows on the context's stream
+void limiter_check_room(const earhip_limiter *lim, size_t nsamples);
+void limiter_feed(earhip_limiter *lim, size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride);
+const earhip_ctx *limiter_ctx(const earhip_limiter *lim);
+int limiter_channels(const earhip_limiter *lim);
+// group F's PCM conversion (api_render.hip) as the limiter's PCM form uses it: what every PCM-out form refuses (returns the
+// output sample size), the number of copies of the levels k_rows_to_pcm keeps ([slots][N] each), and the launch itself: planar
+// rows [N][in_stride] (samples [0, len), the first at sample clock t0) -> bytes [first_byte, + N * sample size) of each frame
+size_t pcm_out_check(const earhip_pcm_out *out);
+int pcm_level_slots();
+void pcm_out_rows(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out, size_t frame_bytes,
+                  size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s);
+}  // namespace earhip

@@ -85,6 +85,9 @@ __device__ inline void tp_keep_history(const TpArgs &a, const float *row, const 
   }
 }
 
+// (the limiter's kernels, limiter_kernels.h, share everything above this line and define EARHIP_TP_HELPERS_ONLY: the meter's
+// kernels exist once, in api_loudness.hip)
+#ifndef EARHIP_TP_HELPERS_ONLY
 __global__ __launch_bounds__(64 * kTpWaves) void k_true_peak_4x12(TpArgs a) {
   __shared__ float tile[kTpWaves][kTpLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ch = blockIdx.y;
@@ -217,5 +220,6 @@ __global__ __launch_bounds__(256) void k_true_peak_totals(const unsigned *tp, co
   __syncthreads();
   if (tid == 0) out[(size_t)which * C + ch] = max(max(part[0], part[1]), max(part[2], part[3]));
 }
+#endif  // EARHIP_TP_HELPERS_ONLY
 
 }  // namespace earhip

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../hip.hpp"
 #include "../hip_firmix.hpp"
+#include "../hip_limiter.hpp"
 #include "../hip_loudness.hpp"
 
 namespace ear {
@@ -185,6 +186,20 @@ namespace ear {
       size_t fir_matrix_position() const {
         size_t n = 0;
         hip::check(earhip_render_firmix_position(h_, &n));
+        return n;
+      }
+      /// From now on every process call of every form also feeds its float32 output rows to `limiter` on the device, behind an
+      /// attached meter and FIR matrix, which keep seeing the unlimited bus; the limited rows go to
+      /// sink[c * sink_stride + position], position = the samples fed since the attach (limiter_position()).  The limiter must
+      /// have n_out channels and this renderer's context, and outlive the attachment.  A call that would pass sink_capacity or
+      /// the limiter's max_samples throws ear::invalid_argument before anything is rendered.  reset() leaves the limiter alone.
+      void attach_limiter(hip::Limiter &limiter, float *sink, size_t sink_stride, size_t sink_capacity) {
+        hip::check(earhip_render_attach_limiter(h_, limiter.get(), sink, sink_stride, sink_capacity));
+      }
+      void detach_limiter() { hip::check(earhip_render_attach_limiter(h_, nullptr, nullptr, 0, 0)); }
+      size_t limiter_position() const {
+        size_t n = 0;
+        hip::check(earhip_render_limiter_position(h_, &n));
         return n;
       }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
