@@ -387,11 +387,9 @@ int earhip_firmix_process(earhip_firmix *fm, size_t nblocks, const float *const 
     earhip_ctx *ctx = fm->ctx;
     ctx->use();
     const size_t n = nblocks * (size_t)fm->B;
-    for (int c : fm->plan.used)  // (a channel without a pair is not read here either)
-      EARHIP_HIP(hipMemcpyAsync(fm->d_in.p + (size_t)c * n, in[c], sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+    rows_to_device(fm->d_in.p, in, fm->C, n, ctx->stream, &fm->plan.used);  // (a channel without a pair is not read here either)
     fm->feed(nblocks, fm->d_in.p, n, fm->d_out.p, n);
-    for (int k = 0; k < fm->K; k++)
-      EARHIP_HIP(hipMemcpyAsync(out[k], fm->d_out.p + (size_t)k * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    rows_from_device(out, fm->d_out.p, fm->K, n, ctx->stream);
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
   });
 }

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "limiter_kernels.h"
+#include "pcm_frames.h"
 
 using namespace earhip;
 
@@ -23,8 +24,7 @@ struct earhip_limiter {
   DevBuf<unsigned> stat_min;                   // [kLimSlots]
   DevBuf<unsigned long long> stat_count;       // [kLimSlots]
   DevBuf<float> d_in, d_out, d_gain;           // the host form's rows and the PCM form's: [C][max_samples] each, [max_samples]
-  DevBuf<unsigned> d_peak;                     // [kLevelSlots][C]: k_rows_to_pcm's levels
-  DevBuf<unsigned long long> d_clip;
+  PcmLevels levels;                            // the PCM form's
 
   // a launch's sample indices are ints
   static constexpr size_t kMaxLaunch = (size_t)1 << 24;
@@ -33,17 +33,13 @@ struct earhip_limiter {
     EARHIP_HIP(hipMemsetAsync(stat_min.p, 0, sizeof(unsigned) * stat_min.n, ctx->stream));
     EARHIP_HIP(hipMemsetAsync(stat_count.p, 0, sizeof(unsigned long long) * stat_count.n, ctx->stream));
   }
-  void zero_levels() {
-    EARHIP_HIP(hipMemsetAsync(d_peak.p, 0, sizeof(unsigned) * d_peak.n, ctx->stream));
-    EARHIP_HIP(hipMemsetAsync(d_clip.p, 0, sizeof(unsigned long long) * d_clip.n, ctx->stream));
-  }
   void zero() {
     EARHIP_HIP(hipMemsetAsync(xhist.p, 0, sizeof(float) * xhist.n, ctx->stream));
     for (int b = 0; b < 2; b++)  // r = 1 before the clock starts
       EARHIP_HIP(hipMemcpyAsync(rhist.p + (size_t)b * (size_t)sh.r_hist(), ones.p, sizeof(float) * (size_t)sh.r_hist(),
                                 hipMemcpyDeviceToDevice, ctx->stream));
     zero_stats();
-    zero_levels();
+    levels.zero(ctx->stream);
     clock = 0;
     par = 0;
   }
@@ -108,40 +104,19 @@ int earhip_limiter_create(earhip_ctx *ctx, const earhip_limiter_config *cfg, ear
                                                cfg->max_samples))
       fail_invalid(why);
     require(ctx != nullptr && out != nullptr, "ctx and out must not be NULL");
-    std::vector<float> table;
-    int phases = 0, taps = 0;
-    if (cfg->detect) {
-      const earhip_true_peak *tp = cfg->tp;
-      if (tp && tp->coeffs) {  // (the rules of earhip_loudness_create_tp)
-        phases = tp->phases, taps = tp->taps;
-        require(phases >= 1 && phases <= kTpMaxPhases, "true peak: phases must be in [1, 8]");
-        require(taps >= 1 && taps <= kTpMaxTaps, "true peak: taps must be in [1, 64]");
-        table.resize((size_t)phases * (size_t)taps);
-        for (size_t i = 0; i < table.size(); i++) {
-          require(std::isfinite(tp->coeffs[i]) && std::isfinite((float)tp->coeffs[i]), "true peak: coefficients must be finite");
-          table[i] = (float)tp->coeffs[i];
-        }
-      } else {
-        require(cfg->sample_rate == 44100 || cfg->sample_rate == 48000,
-                "the built-in true-peak table is 4x oversampling for 44100 and 48000 Hz: another rate must bring its own");
-        double h[4][12];
-        true_peak_default_table(h);
-        phases = 4, taps = 12;
-        table.resize(48);
-        for (int i = 0; i < 48; i++) table[(size_t)i] = (float)h[i / 12][i % 12];
-      }
-    }
+    TpTable table;  // (detect = 0: none)
+    if (cfg->detect)
+      if (const char *why = tp_table_make(cfg->tp, cfg->sample_rate, &table)) fail_invalid(why);
     ctx->use();
     std::unique_ptr<earhip_limiter> lim(new earhip_limiter);
     lim->ctx = ctx;
     lim->C = cfg->n_channels, lim->c = cfg->ceiling, lim->detect = cfg->detect;
-    lim->sh = limiter_shape(cfg->lookahead, cfg->hold, cfg->detect, phases, taps);
+    lim->sh = limiter_shape(cfg->lookahead, cfg->hold, cfg->detect, table.phases, table.taps);
     lim->max_samples = cfg->max_samples;
-    if (phases == 4 && taps == 12) std::memcpy(lim->h, table.data(), sizeof(lim->h));
-    else std::memset(lim->h, 0, sizeof(lim->h));
+    std::memcpy(lim->h, table.h, sizeof(lim->h));
     const size_t C = (size_t)cfg->n_channels, HR = (size_t)lim->sh.r_hist();
-    lim->table.alloc(table.size());
-    if (!table.empty()) EARHIP_HIP(hipMemcpy(lim->table.p, table.data(), sizeof(float) * table.size(), hipMemcpyHostToDevice));
+    lim->table.alloc(table.v.size());
+    if (!table.v.empty()) EARHIP_HIP(hipMemcpy(lim->table.p, table.v.data(), sizeof(float) * table.v.size(), hipMemcpyHostToDevice));
     lim->xhist.alloc(2 * C * (size_t)lim->sh.x_hist());
     lim->rhist.alloc(2 * HR);
     lim->ones.alloc(HR);
@@ -153,8 +128,7 @@ int earhip_limiter_create(earhip_ctx *ctx, const earhip_limiter_config *cfg, ear
     lim->d_in.alloc(C * cfg->max_samples);
     lim->d_out.alloc(C * cfg->max_samples);
     lim->d_gain.alloc(cfg->max_samples);
-    lim->d_peak.alloc((size_t)pcm_level_slots() * C);
-    lim->d_clip.alloc((size_t)pcm_level_slots() * C);
+    lim->levels.reserve(cfg->n_channels, ctx->stream);
     lim->zero();
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
     *out = lim.release();
@@ -208,11 +182,9 @@ int earhip_limiter_process(earhip_limiter *lim, size_t nsamples, const float *co
     earhip_ctx *ctx = lim->ctx;
     ctx->use();
     const size_t n = nsamples;
-    for (int c = 0; c < lim->C; c++)
-      EARHIP_HIP(hipMemcpyAsync(lim->d_in.p + (size_t)c * n, in[c], sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+    rows_to_device(lim->d_in.p, in, lim->C, n, ctx->stream);
     lim->feed(n, lim->d_in.p, n, lim->d_out.p, n, gain ? lim->d_gain.p : nullptr);
-    for (int c = 0; c < lim->C; c++)
-      EARHIP_HIP(hipMemcpyAsync(out[c], lim->d_out.p + (size_t)c * n, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
+    rows_from_device(out, lim->d_out.p, lim->C, n, ctx->stream);
     if (gain) EARHIP_HIP(hipMemcpyAsync(gain, lim->d_gain.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
   });
@@ -222,13 +194,7 @@ int earhip_limiter_process_pcm_device(earhip_limiter *lim, size_t nsamples, cons
                                       size_t out_frame_bytes, size_t out_first_byte, const earhip_pcm_out *out) {
   return guarded([&] {
     require(lim != nullptr, "limiter must not be NULL");
-    const size_t So = pcm_out_check(out);
-    require(out_dev != nullptr, "out_dev must not be NULL");
-    require(So == 3 || reinterpret_cast<uintptr_t>(out_dev) % So == 0, "out_dev not aligned to the sample size");
-    require(out_frame_bytes >= (size_t)lim->C * So, "out_frame_bytes smaller than n_channels samples");
-    require(out_first_byte <= out_frame_bytes - (size_t)lim->C * So, "out_first_byte + n_channels samples exceed out_frame_bytes");
-    require(So == 3 || (out_frame_bytes % So == 0 && out_first_byte % So == 0),
-            "out_frame_bytes / out_first_byte not multiples of the sample size");
+    check_pcm_out_frame(lim->C, check_pcm_out(out), out_dev, out_frame_bytes, out_first_byte, "n_channels");
     lim->check_room(nsamples);
     if (nsamples == 0) return;
     require(in_dev != nullptr, "in_dev must not be NULL");
@@ -237,8 +203,8 @@ int earhip_limiter_process_pcm_device(earhip_limiter *lim, size_t nsamples, cons
     ctx->use();
     const int64_t t0 = (int64_t)lim->clock;
     lim->feed(nsamples, in_dev, in_stride, lim->d_out.p, nsamples, nullptr);
-    pcm_out_rows(*out, lim->d_out.p, nsamples, lim->C, nsamples, static_cast<unsigned char *>(out_dev), out_frame_bytes, out_first_byte,
-                 lim->d_peak.p, lim->d_clip.p, t0, ctx->stream);
+    launch_rows_to_pcm(*out, lim->d_out.p, nsamples, lim->C, nsamples, static_cast<unsigned char *>(out_dev), out_frame_bytes,
+                       out_first_byte, lim->levels.peak.p, lim->levels.clip.p, t0, ctx->stream);
   });
 }
 
@@ -249,20 +215,8 @@ int earhip_limiter_output_levels(earhip_limiter *lim, float *peak, uint64_t *cli
     earhip_ctx *ctx = lim->ctx;
     ctx->use();
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    // (the kernel keeps several copies: the maximum / the sum over them; bits of non-negative floats order as integers)
-    const size_t slots = (size_t)pcm_level_slots(), cnt = slots * (size_t)lim->C;
-    std::vector<unsigned> pk(cnt);
-    std::vector<unsigned long long> cl(cnt);
-    EARHIP_HIP(hipMemcpy(pk.data(), lim->d_peak.p, sizeof(unsigned) * cnt, hipMemcpyDeviceToHost));
-    EARHIP_HIP(hipMemcpy(cl.data(), lim->d_clip.p, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost));
-    for (int c = 0; c < lim->C; c++) {
-      unsigned m = 0;
-      uint64_t sum = 0;
-      for (size_t k = 0; k < slots; k++) m = std::max(m, pk[k * (size_t)lim->C + c]), sum += cl[k * (size_t)lim->C + c];
-      std::memcpy(&peak[c], &m, sizeof(float));
-      clipped[c] = sum;
-    }
-    if (reset) lim->zero_levels();
+    lim->levels.read(lim->C, peak, clipped);
+    if (reset) lim->levels.zero(ctx->stream);
   });
 }
 

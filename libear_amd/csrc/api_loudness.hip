@@ -143,27 +143,9 @@ int earhip_loudness_create_tp(earhip_ctx *ctx, int n_channels, int sample_rate, 
     require(coeffs != nullptr || sample_rate == 48000,
             "the built-in K-weighting coefficients are those of 48000 Hz: another rate must bring its own");
     require(max_steps >= 1 && max_steps <= ((size_t)1 << 32) / (size_t)n_channels, "max_steps out of range");
-    std::vector<float> table;
-    int phases = 4, taps = 12;
-    if (tp) {
-      if (tp->coeffs) {
-        phases = tp->phases, taps = tp->taps;
-        require(phases >= 1 && phases <= kTpMaxPhases, "true peak: phases must be in [1, 8]");
-        require(taps >= 1 && taps <= kTpMaxTaps, "true peak: taps must be in [1, 64]");
-        table.resize((size_t)phases * (size_t)taps);
-        for (size_t i = 0; i < table.size(); i++) {
-          require(std::isfinite(tp->coeffs[i]) && std::isfinite((float)tp->coeffs[i]), "true peak: coefficients must be finite");
-          table[i] = (float)tp->coeffs[i];
-        }
-      } else {
-        require(sample_rate == 44100 || sample_rate == 48000,
-                "the built-in true-peak table is 4x oversampling for 44100 and 48000 Hz: another rate must bring its own");
-        double h[4][12];
-        true_peak_default_table(h);
-        table.resize(48);
-        for (int i = 0; i < 48; i++) table[(size_t)i] = (float)h[i / 12][i % 12];
-      }
-    }
+    TpTable table;
+    if (tp)
+      if (const char *why = tp_table_make(tp, sample_rate, &table)) fail_invalid(why);
     ctx->use();
     std::unique_ptr<earhip_loudness> m(new earhip_loudness);
     m->ctx = ctx;
@@ -195,11 +177,10 @@ int earhip_loudness_create_tp(earhip_ctx *ctx, int n_channels, int sample_rate, 
     EARHIP_HIP(hipMemcpy(m->Q.p, Q.data(), sizeof(double) * Q.size(), hipMemcpyHostToDevice));
     if (tp) {
       m->tp_on = true;
-      m->tp_phases = phases, m->tp_taps = taps;
-      if (phases == 4 && taps == 12) std::memcpy(m->tp_h, table.data(), sizeof(m->tp_h));
-      else std::memset(m->tp_h, 0, sizeof(m->tp_h));
-      m->tp_table.alloc(table.size());
-      EARHIP_HIP(hipMemcpy(m->tp_table.p, table.data(), sizeof(float) * table.size(), hipMemcpyHostToDevice));
+      m->tp_phases = table.phases, m->tp_taps = table.taps;
+      std::memcpy(m->tp_h, table.h, sizeof(m->tp_h));
+      m->tp_table.alloc(table.v.size());
+      EARHIP_HIP(hipMemcpy(m->tp_table.p, table.v.data(), sizeof(float) * table.v.size(), hipMemcpyHostToDevice));
       m->tp_hist.alloc(2 * C * kTpHist);
       m->tp_steps.alloc((max_steps + 1) * C);
       m->sp_steps.alloc((max_steps + 1) * C);

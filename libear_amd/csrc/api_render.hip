@@ -1,22 +1,18 @@
 // api_render.hip — (F) the composed Objects render block of include/earhip.h:
 // K0 segment prep -> K1 gain_mix (direct + diffuse buses) -> K2
 // decorrelate_delay_mix, `nblocks` blocks per call, state resident in HBM.
+// Around it: the taps on its output bus (meter, FIR matrix, limiter), the host-pointer forms (long calls: the chunk pipeline of
+// host_pipeline.h) and the forms that take and make interleaved PCM frames (their conversions: api_frames.hip, pcm_frames.h).
 #include <cmath>
 #include <cstdlib>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <vector>
-
 
 #include "common.h"
 #include "curves.h"
-#include "host_gather.h"
-#include "pcm_kernels.h"
-#include "pcm_out_kernels.h"
+#include "host_pipeline.h"
+#include "pcm_frames.h"
 #include "fft_kernels.h"
 #include "render_kernels.h"
 
@@ -113,163 +109,6 @@ static int wave_run_len(int T, int N, int num_cus) {
   return best;
 }
 
-// Staging threads of the host-pointer entry point, started at the first long call and kept: a call
-// neither creates threads nor allocates.  A long call is cut into TIME chunks (a few blocks each: ~8 MB of inputs); a job =
-// gather every channel's samples of chunk g into the pinned buffer, chunk-major ([chunk][channel][samples of the chunk]: a
-// chunk is one linear transfer), thread t taking every nthreads-th channel; done[g] counts the threads that have finished
-// chunk g (the caller starts that chunk's transfer then, while the threads gather the next one).  The contiguous-range job
-// (submit_range: interleaved PCM frames, earhip_render_process_frames) copies chunk g's byte range of the caller's buffer to the
-// same offset of the pinned buffer instead, thread t taking its slice of the range (range_slice).
-struct GatherPool {
-  static constexpr int kMaxGroups = HostChunkPlan::kMaxChunks;
-  NumaMap numa;
-  bool streaming = true;              // (option HOST_NT, read when a job is submitted)
-  int job_node = -1;                  // the node this job's rows live on (-1: run anywhere)
-  const cpu_set_t *job_cpus = nullptr;
-  std::vector<std::thread> threads;
-  std::mutex mu;
-  std::condition_variable go, finished_cv;
-  uint64_t generation = 0;
-  int finished = 0;
-  bool quit = false;
-  // the job
-  const float *const *in = nullptr;
-  float *dst = nullptr;
-  size_t n = 0;                      // samples per channel in the call
-  size_t cstart[kMaxGroups + 1] = {0};  // chunk g = samples [cstart[g], cstart[g + 1]) of every channel
-  int M = 0, groups = 0;
-  const unsigned char *src_bytes = nullptr;  // contiguous-range job: source and destination of chunk g = bytes
-  unsigned char *dst_bytes = nullptr;        // [cstart[g] * unit, cstart[g + 1] * unit) (src_bytes NULL: a row job)
-  size_t unit = 0;
-  std::atomic<int> done[kMaxGroups];
-  int nthreads() const { return (int)threads.size(); }
-  size_t group_len(int g) const { return cstart[g + 1] - cstart[g]; }
-  void start(int count) {
-    for (int t = 0; t < count; t++)
-      threads.emplace_back([this, t] {
-        uint64_t seen = 0;
-        int my_node = -1;  // the node this thread is bound to (-1: not bound)
-        for (;;) {
-          int want_node;
-          const cpu_set_t *want_cpus;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            go.wait(lk, [&] { return quit || generation != seen; });
-            if (quit) return;
-            seen = generation;
-            want_node = job_node, want_cpus = job_cpus;
-          }
-          if (want_node != my_node) {  // (a failure leaves the thread where it is: placement is an optimisation)
-            if (want_node >= 0 && want_cpus) {
-              if (sched_setaffinity(0, sizeof(cpu_set_t), want_cpus) == 0) my_node = want_node;
-            } else if (numa.ok && sched_setaffinity(0, sizeof(cpu_set_t), &numa.allowed) == 0) {
-              my_node = -1;
-            }
-          }
-          const int nt = nthreads();
-          for (int g = 0; g < groups; g++) {
-            const size_t len = group_len(g), at = cstart[g];
-            float *base = dst + (size_t)M * at;
-            if (src_bytes) {
-              size_t lo, hi;
-              range_slice(len * unit, t, nt, &lo, &hi);
-              const size_t o = at * unit + lo;
-              if (hi > lo) {
-                if (streaming) stream_copy_bytes(dst_bytes + o, src_bytes + o, hi - lo);
-                else std::memcpy(dst_bytes + o, src_bytes + o, hi - lo);
-              }
-#if defined(__x86_64__)
-              if (streaming) _mm_sfence();
-#endif
-            } else if (streaming) {
-              for (int m = t; m < M; m += nt) stream_copy(base + (size_t)m * len, in[m] + at, len);
-#if defined(__x86_64__)
-              _mm_sfence();  // (streaming stores are weakly ordered: globally visible before the chunk counts as gathered)
-#endif
-            } else {
-              for (int m = t; m < M; m += nt) std::memcpy(base + (size_t)m * len, in[m] + at, sizeof(float) * len);
-            }
-            done[g].fetch_add(1, std::memory_order_release);
-          }
-          std::lock_guard<std::mutex> lk(mu);
-          if (++finished == nt) finished_cv.notify_one();
-        }
-      });
-  }
-  void submit(const float *const *in_, float *dst_, size_t n_, const size_t *starts, int nchunks, int M_, bool bind, bool nt) {
-    const int node = bind && numa.ok ? NumaMap::rows_node(in_, M_, n_) : -1;
-    std::lock_guard<std::mutex> lk(mu);
-    in = in_, dst = dst_, n = n_, M = M_;
-    src_bytes = nullptr;
-    for (int g = 0; g <= nchunks; g++) cstart[g] = starts[g];
-    streaming = nt;
-    job_cpus = numa.cpus_of(node);
-    job_node = job_cpus ? node : -1;
-    groups = nchunks;
-    for (auto &d : done) d.store(0);
-    finished = 0;
-    generation++;
-    go.notify_all();
-  }
-  void submit_range(const void *src, void *dst_, size_t unit_, const size_t *starts, int nchunks, bool bind, bool nt) {
-    const int node = bind && numa.ok ? NumaMap::range_node(src, starts[nchunks] * unit_) : -1;
-    std::lock_guard<std::mutex> lk(mu);
-    src_bytes = static_cast<const unsigned char *>(src), dst_bytes = static_cast<unsigned char *>(dst_), unit = unit_;
-    in = nullptr, dst = nullptr, n = starts[nchunks], M = 0;
-    for (int g = 0; g <= nchunks; g++) cstart[g] = starts[g];
-    streaming = nt;
-    job_cpus = numa.cpus_of(node);
-    job_node = job_cpus ? node : -1;
-    groups = nchunks;
-    for (auto &d : done) d.store(0);
-    finished = 0;
-    generation++;
-    go.notify_all();
-  }
-  void wait_all() {
-    std::unique_lock<std::mutex> lk(mu);
-    finished_cv.wait(lk, [&] { return finished == nthreads(); });
-  }
-  ~GatherPool() {
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      quit = true;
-    }
-    go.notify_all();
-    for (auto &th : threads) th.join();
-  }
-};
-
-// Copy streams and events of long host-pointer calls (made at the first such call and kept): the chunks of a call go
-// H2D on `in`, through the kernels on the context's stream, and D2H on `out`, each stage ordered behind the one
-// before it by the chunk's events — chunk c's kernels and the transfer of its outputs run beside the transfer of c + 1.
-struct StreamPipe {
-  hipStream_t in = nullptr, out = nullptr;
-  hipEvent_t ev_in[GatherPool::kMaxGroups], ev_k[GatherPool::kMaxGroups], ev_out[GatherPool::kMaxGroups];
-  bool made = false;
-  void make() {
-    if (made) return;
-    EARHIP_HIP(hipStreamCreateWithFlags(&in, hipStreamNonBlocking));
-    EARHIP_HIP(hipStreamCreateWithFlags(&out, hipStreamNonBlocking));
-    for (int i = 0; i < GatherPool::kMaxGroups; i++) {
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_in[i], hipEventDisableTiming));
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_k[i], hipEventDisableTiming));
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_out[i], hipEventDisableTiming));
-    }
-    made = true;
-  }
-  ~StreamPipe() {
-    if (!made) return;
-    for (int i = 0; i < GatherPool::kMaxGroups; i++) {
-      (void)hipEventDestroy(ev_in[i]);
-      (void)hipEventDestroy(ev_k[i]);
-      (void)hipEventDestroy(ev_out[i]);
-    }
-    (void)hipStreamDestroy(in);
-    (void)hipStreamDestroy(out);
-  }
-};
-
 struct earhip_render {
   earhip_ctx *ctx = nullptr;
   int M = 0, N = 0, B = 0, K = 1, D = 0, T = 0;
@@ -321,11 +160,10 @@ struct earhip_render {
   DevBuf<float> d_ilv, d_rows, d_rows_out;
   // PCM frames out (earhip_render_process_frames_pcm): the packed output frames of a call on the device and pinned (pageable
   // out_frames only), sized at the first call of that form for max_blocks frames of its format (grown by a call of a wider
-  // format); the levels the conversion kernel keeps, [kLevelSlots][N] each, made (zeroed) with them
+  // format); the levels the conversion kernel keeps, made (zeroed) with them
   DevBuf<unsigned char> d_pcm;
   PinBuf<unsigned char> p_pcm;
-  DevBuf<unsigned> d_peak;
-  DevBuf<unsigned long long> d_clip;
+  PcmLevels levels;
   // timing
   bool timing = false;
   bool last_timed = false;
@@ -344,6 +182,17 @@ struct earhip_render {
       for (auto e : p.e)
         if (e) (void)hipEventDestroy(e);
     for (auto e : pool) (void)hipEventDestroy(e);
+  }
+
+  // the copy of the context's mode word the last call's gain kernel left in this renderer's slot, valid until this renderer's next
+  // call (synchronises the stream)
+  unsigned mode_word() {
+    ctx->use();
+    unsigned word = 0;
+    EARHIP_HIP(hipMemcpyAsync(&word, rec.p, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    if (!(word & kModeRecorded)) fail_internal("no gain kernel recorded the call's mode word");
+    return word;
   }
 
   hipEvent_t get_event() {
@@ -390,19 +239,21 @@ struct earhip_render {
     return ctx->host_reachable(ch[0], step * (count - 1) + sizeof(float) * n) ? (size_t)(step / sizeof(float)) : 0;
   }
 
-  void reserve_levels() {
-    if (d_peak.p) return;
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    d_peak.alloc_zero((size_t)kLevelSlots * N, ctx->stream);
-    d_clip.alloc_zero((size_t)kLevelSlots * N, ctx->stream);
-  }
-  void zero_levels() {
-    if (!d_peak.p) return;
-    EARHIP_HIP(hipMemsetAsync(d_peak.p, 0, sizeof(unsigned) * kLevelSlots * N, ctx->stream));
-    EARHIP_HIP(hipMemsetAsync(d_clip.p, 0, sizeof(unsigned long long) * kLevelSlots * N, ctx->stream));
+  // the device frames forms' first step: the call's frames converted into d_rows, rows of the n samples returned (with_out:
+  // the form renders into d_rows_out, for interleaved outputs)
+  size_t frames_to_device_rows(size_t nblocks, const void *frames_dev, int fmt, int frame_channels, int first_channel, bool with_out) {
+    ctx->use();
+    const size_t S = (size_t)pcm_sample_bytes(fmt), n = nblocks * (size_t)B, cap = (size_t)T * B;
+    if (d_rows.n < cap * M || (with_out && d_rows_out.n < cap * N)) {
+      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (first use: nothing of this renderer may still read them)
+      d_rows.reserve(cap * M);
+      if (with_out) d_rows_out.reserve(cap * N);
+    }
+    launch_pcm_to_rows(fmt, frames_dev, (size_t)frame_channels * S, (size_t)first_channel * S, M, n, d_rows.p, n, ctx->stream);
+    return n;
   }
   void reserve_pcm_out(size_t bytes, bool pinned) {
-    reserve_levels();
+    levels.reserve(N, ctx->stream);
     d_pcm.reserve(bytes);
     if (pinned) p_pcm.reserve(bytes);
   }
@@ -410,6 +261,38 @@ struct earhip_render {
   // the chunk plan of a call from host memory (earhip_render_process and _process_frames alike)
   HostChunkPlan host_plan(size_t nblocks, bool direct) const {
     return plan_host_chunks(nblocks, B, M, direct, ctx->has(OPT_HOST_CHUNK_MB), ctx->get(OPT_HOST_CHUNK_MB), ctx->get(OPT_HOST_FIRST, 0));
+  }
+  // A chunk's planar outputs — samples [at, at + len) of every row, chunk-major in d_out and p_out — on their way back: on pipe.out
+  // by strided DMA into the caller's device-reachable rows (out_st: their stride) or into p_out, and from there to the caller's rows.
+  hipError_t chunk_rows_d2h(float *out0, size_t out_st, size_t at, size_t len) {
+    const float *dout = d_out.p + (size_t)N * at;
+    if (out_st)
+      return hipMemcpy2DAsync(out0 + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, N, hipMemcpyDeviceToHost, pipe.out);
+    return hipMemcpyAsync(p_out.p + (size_t)N * at, dout, sizeof(float) * len * N, hipMemcpyDeviceToHost, pipe.out);
+  }
+  void chunk_rows_scatter(float *const *out, size_t at, size_t len) const {
+    for (int ch = 0; ch < N; ch++) std::memcpy(out[ch] + at, p_out.p + (size_t)N * at + (size_t)ch * len, sizeof(float) * len);
+  }
+  // Short calls, planar outputs, from d_in: K2 writes the few output rows straight into host memory (the caller's own rows when they
+  // are reachable, else the pinned staging buffer: no D2H copy to start and wait for, 126 -> 119 us per
+  // 512-sample call at the headline shape).  The other direction does not pay — kernels that read their 2 MB
+  // of inputs over PCIe themselves are slower than the copy engine plus kernels (129 us) — and neither does
+  // spinning on a completion word behind one more launch.
+  // (FIRs of several partitions accumulate into the output: that stays in device memory, and out_st is 0 then)
+  void process_short_call(size_t nblocks, float *out0, size_t out_st) {
+    const size_t n = nblocks * (size_t)B;
+    const bool direct_out = NP <= 1;
+    process_device(nblocks, d_in.p, n, out_st ? out0 : direct_out ? p_out.p : d_out.p, out_st ? out_st : n);
+    if (!out_st && !direct_out) EARHIP_HIP(hipMemcpyAsync(p_out.p, d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  // the staging threads of long calls from pageable memory, started at the first such call (option HOST_THREADS: how many)
+  GatherPool &staging_threads() {
+    if (!gather) {
+      gather.reset(new GatherPool);
+      const int want = ctx->get(OPT_HOST_THREADS, 0);
+      gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
+    }
+    return *gather;
   }
 
   // the launch plan of a call of nblocks blocks at the current sample clock
@@ -459,50 +342,58 @@ struct earhip_render {
   // which the planner spreads over the chip by splitting the objects (as in block mode).  The cut costs a second K0, a
   // second K2 launch and the boundaries (~30 us): taken when the tail is at most a quarter of a round.  Results are those
   // of two consecutive calls (every call length is a valid call: the state carries over).
-  // The one place every form of process call passes.  An attached loudness meter (earhip_render_attach_loudness) reads the
-  // planar rows the call wrote — the caller's, d_out or d_rows_out — behind the call's kernels: after the tail cut, so a call
-  // that ran as two spans is metered once per sample.  Without a meter this is render_spans and nothing else.
+  // The one place every form of process call passes.  The taps on the output bus read the planar rows the call wrote — the
+  // caller's, d_out or d_rows_out — behind the call's kernels: after the tail cut, so a call that ran as two spans is seen once per
+  // sample.  An attached loudness meter (earhip_render_attach_loudness) only reads.  An attached FIR matrix
+  // (earhip_render_attach_firmix) writes its own rows to the caller's sink at the tap's pos, a host counter: the feeds are
+  // enqueued in order.  An attached limiter (earhip_render_attach_limiter) comes behind the meter and the matrix, which both see
+  // the unlimited bus, and writes the limited rows to its own sink.  Without a tap this is render_spans and nothing else.
+  struct BusTap {
+    float *sink = nullptr;
+    size_t stride = 0, cap = 0, pos = 0;
+    // a stage is attached (on: its sink is checked first) or detached; either way the tap starts at 0
+    void attach(bool on, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
+      if (on) {
+        require(sink_dev != nullptr, "sink_dev must not be NULL");
+        require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
+      }
+      *this = on ? BusTap{sink_dev, sink_stride, sink_capacity, 0} : BusTap{};
+    }
+  };
   earhip_loudness *meter = nullptr;
-  void check_meter(size_t nblocks) const {
-    if (meter) loudness_check_room(meter, nblocks * (size_t)B);
-  }
-  // An attached FIR matrix (earhip_render_attach_firmix) reads the same rows at the same place and writes its own rows to the
-  // caller's sink at fm_pos, a host counter: the feeds are enqueued in order.
   earhip_firmix *fm = nullptr;
-  float *fm_sink = nullptr;
-  size_t fm_sink_stride = 0, fm_sink_cap = 0, fm_pos = 0;
-  void check_firmix(size_t nblocks) const {
-    if (!fm) return;
-    firmix_check_room(fm, nblocks);
-    if (fm_pos + nblocks * (size_t)B > fm_sink_cap)
-      fail_invalid("the call would pass the FIR matrix's sink_capacity (nothing was rendered)");
-  }
-  // An attached limiter (earhip_render_attach_limiter) reads the same rows behind the meter and the matrix, which both see the
-  // unlimited bus, and writes the limited rows to its own sink at lim_pos.
   earhip_limiter *lim = nullptr;
-  float *lim_sink = nullptr;
-  size_t lim_sink_stride = 0, lim_sink_cap = 0, lim_pos = 0;
-  void check_limiter(size_t nblocks) const {
-    if (!lim) return;
-    limiter_check_room(lim, nblocks * (size_t)B);
-    if (lim_pos + nblocks * (size_t)B > lim_sink_cap)
-      fail_invalid("the call would pass the limiter's sink_capacity (nothing was rendered)");
+  BusTap fm_tap, lim_tap;
+  // a tap that has no room for the call refuses it before anything is rendered
+  void check_taps(size_t nblocks) const {
+    const size_t n = nblocks * (size_t)B;
+    if (meter) loudness_check_room(meter, n);
+    if (fm) {
+      firmix_check_room(fm, nblocks);
+      if (fm_tap.pos + n > fm_tap.cap) fail_invalid("the call would pass the FIR matrix's sink_capacity (nothing was rendered)");
+    }
+    if (lim) {
+      limiter_check_room(lim, n);
+      if (lim_tap.pos + n > lim_tap.cap) fail_invalid("the call would pass the limiter's sink_capacity (nothing was rendered)");
+    }
+  }
+  void feed_taps(size_t nblocks, const float *out_dev, size_t out_stride) {
+    const size_t n = nblocks * (size_t)B;
+    if (meter) loudness_feed(meter, n, out_dev, out_stride);
+    if (fm) {
+      firmix_feed(fm, nblocks, out_dev, out_stride, fm_tap.sink + fm_tap.pos, fm_tap.stride);
+      fm_tap.pos += n;
+    }
+    if (lim) {
+      limiter_feed(lim, n, out_dev, out_stride, lim_tap.sink + lim_tap.pos, lim_tap.stride);
+      lim_tap.pos += n;
+    }
   }
   void process_device(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
     if (!meter && !fm && !lim) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
-    if (meter) loudness_check_room(meter, nblocks * (size_t)B);
-    check_firmix(nblocks);
-    check_limiter(nblocks);
+    check_taps(nblocks);
     render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
-    if (meter) loudness_feed(meter, nblocks * (size_t)B, out_dev, out_stride);
-    if (fm) {
-      firmix_feed(fm, nblocks, out_dev, out_stride, fm_sink + fm_pos, fm_sink_stride);
-      fm_pos += nblocks * (size_t)B;
-    }
-    if (lim) {
-      limiter_feed(lim, nblocks * (size_t)B, out_dev, out_stride, lim_sink + lim_pos, lim_sink_stride);
-      lim_pos += nblocks * (size_t)B;
-    }
+    feed_taps(nblocks, out_dev, out_stride);
   }
   void render_spans(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
     MixLaunch whole;  // the plan of the uncut call, made once (process_span takes it as it is)
@@ -823,7 +714,7 @@ int earhip_render_reset(earhip_render *r, int64_t sample_time) {
     r->ctx->use();
     r->t = sample_time;
     r->fresh = true;  // the next call reads the all-zero state and rewrites its own pair completely
-    r->zero_levels();  // (only a renderer that has made PCM frames has any)
+    r->levels.zero(r->ctx->stream);  // (only a renderer that has made PCM frames has any)
   });
 }
 
@@ -845,21 +736,16 @@ int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink
       require(firmix_ctx(fm) == r->ctx, "the FIR matrix must belong to the renderer's context");
       require(firmix_inputs(fm) == r->N, "the FIR matrix must have n_in = the renderer's n_out");
       require(firmix_block(fm) == r->B, "the FIR matrix must have the renderer's block size");
-      require(sink_dev != nullptr, "sink_dev must not be NULL");
-      require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
     }
+    r->fm_tap.attach(fm != nullptr, sink_dev, sink_stride, sink_capacity);
     r->fm = fm;
-    r->fm_sink = fm ? sink_dev : nullptr;
-    r->fm_sink_stride = fm ? sink_stride : 0;
-    r->fm_sink_cap = fm ? sink_capacity : 0;
-    r->fm_pos = 0;
   });
 }
 
 int earhip_render_firmix_position(earhip_render *r, size_t *samples) {
   return guarded([&] {
     require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
-    *samples = r->fm_pos;
+    *samples = r->fm_tap.pos;
   });
 }
 
@@ -869,21 +755,16 @@ int earhip_render_attach_limiter(earhip_render *r, earhip_limiter *lim, float *s
     if (lim) {
       require(limiter_ctx(lim) == r->ctx, "the limiter must belong to the renderer's context");
       require(limiter_channels(lim) == r->N, "the limiter must have n_channels = the renderer's n_out");
-      require(sink_dev != nullptr, "sink_dev must not be NULL");
-      require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
     }
+    r->lim_tap.attach(lim != nullptr, sink_dev, sink_stride, sink_capacity);
     r->lim = lim;
-    r->lim_sink = lim ? sink_dev : nullptr;
-    r->lim_sink_stride = lim ? sink_stride : 0;
-    r->lim_sink_cap = lim ? sink_capacity : 0;
-    r->lim_pos = 0;
   });
 }
 
 int earhip_render_limiter_position(earhip_render *r, size_t *samples) {
   return guarded([&] {
     require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
-    *samples = r->lim_pos;
+    *samples = r->lim_tap.pos;
   });
 }
 
@@ -893,9 +774,7 @@ int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *
     require(r != nullptr, "render must not be NULL");
     require(in_dev != nullptr && out_dev != nullptr, "device pointers must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
-    r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
-    r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
-    r->check_limiter(nblocks);  // (and for an attached limiter and its sink)
+    r->check_taps(nblocks);  // (an attached meter, FIR matrix or limiter that has no room for the call: nothing is rendered)
     require(in_stride >= nblocks * r->B && out_stride >= nblocks * r->B, "stride too small");
     if (nblocks == 0) return;
     r->ctx->use();
@@ -909,9 +788,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     require(r != nullptr, "render must not be NULL");
     require(in != nullptr && out != nullptr, "in and out must not be NULL");
     require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
-    r->check_meter(nblocks);  // (an attached loudness meter that has no room for the call: nothing is rendered)
-    r->check_firmix(nblocks);  // (the same for an attached FIR matrix and its sink)
-    r->check_limiter(nblocks);  // (and for an attached limiter and its sink)
+    r->check_taps(nblocks);  // (an attached meter, FIR matrix or limiter that has no room for the call: nothing is rendered)
     if (nblocks == 0) return;
     earhip_ctx *ctx = r->ctx;
     ctx->use();
@@ -921,7 +798,6 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     r->p_out.reserve(cap * r->N);
     r->d_in.reserve(cap * r->M);
     r->d_out.reserve(cap * r->N);
-    const size_t in_bytes = sizeof(float) * n * r->M;
     const bool dbg = ctx->get(OPT_DEBUG_TIMING) != 0;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_a = dbg ? now() : 0.0;
@@ -930,88 +806,37 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     const size_t out_st = r->NP <= 1 || !short_call ? r->direct_stride(out, r->N, n) : 0;
     r->last_host_chunks = 0;
     if (!short_call) {
-      // Long calls (libear's calling convention for offline renders: host channel pointers, any length): the call is cut
-      // into TIME chunks of a few blocks (option HOST_CHUNK_MB: ~8 MB of inputs each, at most 64 chunks) and the chunks run
-      // through a three-stage pipeline on three streams: H2D of chunk c + 1 (its own copy stream) beside the kernels of
-      // chunk c (the context's stream: each chunk is an ordinary process call of its blocks, the DSP state carries over)
-      // beside the D2H of chunk c - 1 (a second copy stream).  The kernels are ~100 x faster than the bus, so the call
-      // takes what its inputs take over PCIe plus one chunk's kernels and output transfer.  From ordinary (pageable)
-      // pointers the staging threads gather chunk c + 1 into the pinned buffer (chunk-major: one linear transfer per
-      // chunk) while chunk c is on the bus, and the outputs of finished chunks are handed back to the caller's rows while
-      // later chunks are still in flight; from device-reachable rows (earhip_host_alloc / _register) neither copy exists.
+      // Long calls (libear's calling convention for offline renders: host channel pointers, any length) run as the pipeline of
+      // time chunks of host_pipeline.h, each chunk an ordinary process call of its blocks (the DSP state carries over): the
+      // kernels are ~100 x faster than the bus, so the call takes what its inputs take over PCIe plus one chunk's kernels and
+      // output transfer.  Pageable rows are gathered chunk-major into the pinned buffer by the staging threads, a chunk ahead;
+      // device-reachable rows (earhip_host_alloc / _register) go by strided DMA both ways, without either copy.
       // (the plan, the same for earhip_render_process_frames: host_gather.h, plan_host_chunks)
       const HostChunkPlan plan = r->host_plan(nblocks, in_st != 0);
-      const size_t cb = plan.cb;
-      const size_t *cstart = plan.cstart;
-      const int nch = plan.nch;
       r->pipe.make();
+      GatherPool *gp = nullptr;
       if (!in_st) {
-        if (!r->gather) {
-          r->gather.reset(new GatherPool);
-          const int want = ctx->get(OPT_HOST_THREADS, 0);
-          r->gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
-        }
-        r->gather->submit(in, r->p_in.p, n, cstart, nch, r->M, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
+        gp = &r->staging_threads();
+        gp->submit(in, r->p_in.p, n, plan.cstart, plan.nch, r->M, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
       }
-      hipError_t err = hipSuccess;
-      std::string fail;
-      int scattered = 0;
-      auto scatter_chunk = [&](int c) {
-        const size_t at = cstart[c], len = cstart[c + 1] - at;
-        const float *base = r->p_out.p + (size_t)r->N * at;
-        for (int ch = 0; ch < r->N; ch++) std::memcpy(out[ch] + at, base + (size_t)ch * len, sizeof(float) * len);
-      };
-      for (int c = 0; c < nch; c++) {
-        const size_t at = cstart[c], len = cstart[c + 1] - at;
-        float *din = r->d_in.p + (size_t)r->M * at, *dout = r->d_out.p + (size_t)r->N * at;
-        if (!in_st) {
-          GatherPool &gp = *r->gather;
-          while (gp.done[c].load(std::memory_order_acquire) < gp.nthreads()) {
-            // (meanwhile: outputs of chunks whose transfer has landed go back to the caller's rows)
-            if (!out_st && scattered < c && err == hipSuccess && hipEventQuery(r->pipe.ev_out[scattered]) == hipSuccess) scatter_chunk(scattered++);
-            else std::this_thread::yield();
-          }
-        }
-        if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
-        if (in_st)
-          err = hipMemcpy2DAsync(din, sizeof(float) * len, in[0] + at, sizeof(float) * in_st, sizeof(float) * len, r->M,
-                                 hipMemcpyHostToDevice, r->pipe.in);
-        else
-          err = hipMemcpyAsync(din, r->p_in.p + (size_t)r->M * at, sizeof(float) * len * r->M, hipMemcpyHostToDevice, r->pipe.in);
-        if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_in[c], r->pipe.in);
-        if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream, r->pipe.ev_in[c], 0);
-        if (err != hipSuccess) continue;
-        try {
-          r->process_device(len / r->B, din, len, dout, len);
-        } catch (const Error &e) {
-          fail = e.msg;
-          continue;
-        }
-        err = hipEventRecord(r->pipe.ev_k[c], ctx->stream);
-        if (err == hipSuccess) err = hipStreamWaitEvent(r->pipe.out, r->pipe.ev_k[c], 0);
-        if (err != hipSuccess) continue;
-        if (out_st)
-          err = hipMemcpy2DAsync(out[0] + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, r->N,
-                                 hipMemcpyDeviceToHost, r->pipe.out);
-        else
-          err = hipMemcpyAsync(r->p_out.p + (size_t)r->N * at, dout, sizeof(float) * len * r->N, hipMemcpyDeviceToHost, r->pipe.out);
-        if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_out[c], r->pipe.out);
-      }
-      if (!in_st) r->gather->wait_all();
-      const double t_c = dbg ? now() : 0.0;
-      // (everything queued is waited for whatever happened above: nothing of this call is in flight when it returns)
-      (void)hipStreamSynchronize(r->pipe.in);
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipStreamSynchronize(r->pipe.out);
-      EARHIP_HIP(err);
-      if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
-      const double t_d = dbg ? now() : 0.0;
-      if (!out_st)
-        for (; scattered < nch; scattered++) scatter_chunk(scattered);
-      r->last_host_chunks = nch;
+      const HostChunkTimes tm = run_host_chunks(
+          r->pipe, gp, plan, ctx->stream, !out_st, &r->last_host_chunks,
+          [&](size_t at, size_t len) {
+            float *din = r->d_in.p + (size_t)r->M * at;
+            if (in_st)
+              return hipMemcpy2DAsync(din, sizeof(float) * len, in[0] + at, sizeof(float) * in_st, sizeof(float) * len, r->M,
+                                      hipMemcpyHostToDevice, r->pipe.in);
+            return hipMemcpyAsync(din, r->p_in.p + (size_t)r->M * at, sizeof(float) * len * r->M, hipMemcpyHostToDevice, r->pipe.in);
+          },
+          [&](size_t at, size_t len) {
+            r->process_device(len / r->B, r->d_in.p + (size_t)r->M * at, len, r->d_out.p + (size_t)r->N * at, len);
+          },
+          [&](size_t at, size_t len) { return r->chunk_rows_d2h(out[0], out_st, at, len); },
+          [&](size_t at, size_t len) { r->chunk_rows_scatter(out, at, len); },
+          [&] { return dbg ? now() : 0.0; });
       if (dbg)
-        fprintf(stderr, "render_process: %d chunks of %zu blocks%s: enqueue incl. gather %.1f us, drain %.1f us, scatter of the rest %.1f us\n", nch,
-                cb, in_st ? " (device-reachable rows)" : "", t_c - t_a, t_d - t_c, now() - t_d);
+        fprintf(stderr, "render_process: %d chunks of %zu blocks%s: enqueue incl. gather %.1f us, drain %.1f us, scatter of the rest %.1f us\n",
+                plan.nch, plan.cb, in_st ? " (device-reachable rows)" : "", tm.enqueued - t_a, tm.drained - tm.enqueued, now() - tm.drained);
       return;
     }
     if (in_st) {
@@ -1028,7 +853,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
       // too and loses: 0.146 / 0.125 / 0.138: the launch is host time in front of the gather, and the probe it
       // leaves behind the transfer is one more kernel in the chain)
       const int groups_env = ctx->get(OPT_BLOCK_GROUPS);
-      const int groups = groups_env >= 1 && groups_env <= 8 ? groups_env : (in_bytes >= ((size_t)1 << 20) ? 2 : 1);
+      const int groups = groups_env >= 1 && groups_env <= 8 ? groups_env : (sizeof(float) * n * r->M >= ((size_t)1 << 20) ? 2 : 1);
       for (int g = 0; g < groups; g++) {
         const int m0 = (int)((int64_t)r->M * g / groups), m1 = (int)((int64_t)r->M * (g + 1) / groups);
         for (int m = m0; m < m1; m++) std::memcpy(r->p_in.p + (size_t)m * n, in[m], sizeof(float) * n);
@@ -1038,22 +863,11 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
       }
     }
     const double t_b = dbg ? now() : 0.0;
-    // Short calls: K2 writes the few output rows straight into host memory (the caller's own rows when they
-    // are reachable, else the pinned staging buffer: no D2H copy to start and wait for, 126 -> 119 us per
-    // 512-sample call at the headline shape).  The other direction does not pay — kernels that read their 2 MB
-    // of inputs over PCIe themselves are slower than the copy engine plus kernels (129 us) — and neither does
-    // spinning on a completion word behind one more launch.
-    // (FIRs of several partitions accumulate into the output: that stays in device memory)
-    const bool direct_out = r->NP <= 1;
-    float *dst = out_st ? out[0] : direct_out ? r->p_out.p : r->d_out.p;
-    r->process_device(nblocks, r->d_in.p, n, dst, out_st ? out_st : n);
-    if (!direct_out)
-      EARHIP_HIP(hipMemcpyAsync(r->p_out.p, r->d_out.p, sizeof(float) * n * r->N, hipMemcpyDeviceToHost, ctx->stream));
+    r->process_short_call(nblocks, out[0], out_st);
     const double t_c = dbg ? now() : 0.0;
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
     const double t_d = dbg ? now() : 0.0;
-    if (!out_st)
-      for (int c = 0; c < r->N; c++) std::memcpy(out[c], r->p_out.p + c * n, sizeof(float) * n);
+    if (!out_st) r->chunk_rows_scatter(out, 0, n);
     if (dbg)
       fprintf(stderr, "render_process: gather+H2D enqueue %.1f us, launches %.1f us, wait %.1f us, scatter %.1f us\n", t_b - t_a,
               t_c - t_b, t_d - t_c, now() - t_d);
@@ -1061,15 +875,6 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
 }
 
 // ---- interleaved PCM frames (include/earhip.h, group F: earhip_render_process_frames) --------------------------------------
-static int pcm_sample_bytes(int fmt) {
-  switch (fmt) {
-    case EARHIP_PCM_S16: return 2;
-    case EARHIP_PCM_S24: return 3;
-    case EARHIP_PCM_S32: case EARHIP_PCM_F32: return 4;
-    default: return 0;
-  }
-}
-
 // what both forms refuse before they touch anything
 static void check_frames_args(const earhip_render *r, size_t nblocks, const void *frames, int fmt, int frame_channels, int first_channel) {
   require(r != nullptr, "render must not be NULL");
@@ -1079,61 +884,8 @@ static void check_frames_args(const earhip_render *r, size_t nblocks, const void
   require(first_channel >= 0, "first_channel must be >= 0");
   require((int64_t)first_channel + r->M <= (int64_t)frame_channels, "first_channel + n_objects exceeds frame_channels");
   require(nblocks <= (size_t)r->T, "nblocks exceeds max_blocks");
-  r->check_meter(nblocks);
-  r->check_firmix(nblocks);
-  r->check_limiter(nblocks);
+  r->check_taps(nblocks);
   require(fmt == EARHIP_PCM_S24 || reinterpret_cast<uintptr_t>(frames) % (uintptr_t)S == 0, "frames not aligned to the sample size");
-}
-
-// frames -> planar rows out [M][row_stride] (samples [0, len)), on stream s
-static void launch_pcm_to_rows(int fmt, const void *frames, size_t frame_bytes, size_t first_byte, int M, size_t len, float *out,
-                               size_t row_stride, hipStream_t s) {
-  const dim3 grid((unsigned)((len + kPcmFrames - 1) / kPcmFrames), (unsigned)((M + kPcmChans - 1) / kPcmChans));
-  const unsigned char *f = static_cast<const unsigned char *>(frames);
-  switch (fmt) {
-    case EARHIP_PCM_S16: hipLaunchKernelGGL((k_pcm_to_rows<2, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
-    case EARHIP_PCM_S24: hipLaunchKernelGGL((k_pcm_to_rows<3, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
-    case EARHIP_PCM_S32: hipLaunchKernelGGL((k_pcm_to_rows<4, false>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
-    default: hipLaunchKernelGGL((k_pcm_to_rows<4, true>), grid, dim3(kPcmThreads), 0, s, f, frame_bytes, first_byte, M, len, out, row_stride); break;
-  }
-  EARHIP_HIP(hipGetLastError());
-}
-
-// planar rows [N][in_stride] -> frames [len][out_stride], on stream s
-static void launch_rows_to_frames(const float *in, size_t in_stride, int N, size_t len, float *out, size_t out_stride, hipStream_t s) {
-  const dim3 grid((unsigned)((len + kIlvFrames - 1) / kIlvFrames), (unsigned)((N + kIlvChans - 1) / kIlvChans));
-  hipLaunchKernelGGL(k_rows_to_frames, grid, dim3(256), 0, s, in, in_stride, N, len, out, out_stride);
-  EARHIP_HIP(hipGetLastError());
-}
-
-// what the PCM-out forms refuse on top of check_frames_args; returns the output sample size
-static size_t check_pcm_out(const earhip_pcm_out *out) {
-  require(out != nullptr, "out (earhip_pcm_out) must not be NULL");
-  const int So = pcm_sample_bytes(out->format);
-  require(So != 0, "unknown PCM output format");
-  require(out->dither == 0 || out->dither == 1, "dither must be 0 or 1");
-  require(out->dither == 0 || out->format == EARHIP_PCM_S16, "dither is defined for EARHIP_PCM_S16 only");
-  return (size_t)So;
-}
-
-// planar rows [N][in_stride] (samples [0, len), the first at sample clock t0) -> PCM frames: bytes [first_byte, + N * sample size) of
-// each frame of frame_bytes at `out`; levels into peak / clipped [N]; on stream s
-static void launch_rows_to_pcm(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out,
-                               size_t frame_bytes, size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s) {
-  const dim3 grid((unsigned)((len + kOutFrames - 1) / kOutFrames), (unsigned)((N + kOutChans - 1) / kOutChans));
-  PcmOutArgs a;
-  a.in = in; a.in_stride = in_stride; a.N = N; a.len = len; a.out = out; a.frame_bytes = frame_bytes; a.first_byte = first_byte;
-  a.peak = peak; a.clipped = clipped; a.seed = o.seed; a.t0 = (long long)t0;
-  switch (o.format) {
-    case EARHIP_PCM_S16:
-      if (o.dither) hipLaunchKernelGGL((k_rows_to_pcm<kPcmS16, true>), grid, dim3(kOutThreads), 0, s, a);
-      else hipLaunchKernelGGL((k_rows_to_pcm<kPcmS16, false>), grid, dim3(kOutThreads), 0, s, a);
-      break;
-    case EARHIP_PCM_S24: hipLaunchKernelGGL((k_rows_to_pcm<kPcmS24, false>), grid, dim3(kOutThreads), 0, s, a); break;
-    case EARHIP_PCM_S32: hipLaunchKernelGGL((k_rows_to_pcm<kPcmS32, false>), grid, dim3(kOutThreads), 0, s, a); break;
-    default: hipLaunchKernelGGL((k_rows_to_pcm<kPcmF32, false>), grid, dim3(kOutThreads), 0, s, a); break;
-  }
-  EARHIP_HIP(hipGetLastError());
 }
 
 // The host form of both frames calls (arguments checked by the caller).  po == nullptr: earhip_render_process_frames, float outputs
@@ -1169,7 +921,7 @@ static void process_frames_host(earhip_render *r, size_t nblocks, const void *fr
   // planar rows [N][stride] of `len` frames at sample clock t0 -> the interleaved frames at ilv_dev + at * ofb
   auto launch_interleave = [&](const float *rows, size_t stride, size_t len, size_t at, int64_t t0) {
     if (po)
-      launch_rows_to_pcm(*po, rows, stride, N, len, ilv_dev + at * ofb, ofb, 0, r->d_peak.p, r->d_clip.p, t0, ctx->stream);
+      launch_rows_to_pcm(*po, rows, stride, N, len, ilv_dev + at * ofb, ofb, 0, r->levels.peak.p, r->levels.clip.p, t0, ctx->stream);
     else
       launch_rows_to_frames(rows, stride, N, len, reinterpret_cast<float *>(ilv_dev + at * ofb), N, ctx->stream);
   };
@@ -1190,98 +942,44 @@ static void process_frames_host(earhip_render *r, size_t nblocks, const void *fr
       launch_interleave(r->d_out.p, n, n, 0, t0);
       EARHIP_HIP(hipMemcpyAsync(out_direct ? ilv_host : ilv_pin, ilv_dev, n * ofb, hipMemcpyDeviceToHost, ctx->stream));
     } else {
-      // (as earhip_render_process: a single-partition render writes its outputs straight into host memory)
-      const bool direct_out = r->NP <= 1;
-      float *dst = out_st ? out0 : direct_out ? r->p_out.p : r->d_out.p;
-      r->process_device(nblocks, r->d_in.p, n, dst, out_st ? out_st : n);
-      if (!out_st && !direct_out)
-        EARHIP_HIP(hipMemcpyAsync(r->p_out.p, r->d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
+      r->process_short_call(nblocks, out0, out_st);
     }
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
     if (out_interleaved && !out_direct) std::memcpy(ilv_host, ilv_pin, n * ofb);
-    if (!out_interleaved && !out_st)
-      for (int c = 0; c < N; c++) std::memcpy(out[c], r->p_out.p + (size_t)c * n, sizeof(float) * n);
+    if (!out_interleaved && !out_st) r->chunk_rows_scatter(out, 0, n);
     return;
   }
-  // Long calls: the pipeline of earhip_render_process, on the packed bytes.  Chunk c is one contiguous byte range of the caller's
-  // buffer: staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all (device-reachable
-  // frames); H2D on the copy stream; on the context's stream the conversion into the chunk's rows of d_in, then the chunk's
-  // render as an ordinary process call; D2H of its outputs on the second copy stream.
-  const size_t *cstart = plan.cstart;
-  const int nch = plan.nch;
+  // Long calls: the pipeline of earhip_render_process, on the packed bytes.  A chunk is one contiguous byte range of the caller's
+  // buffer, staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all; its kernels
+  // are the conversion into the chunk's rows of d_in, then the chunk's render as an ordinary process call.
   r->pipe.make();
+  GatherPool *gp = nullptr;
   if (!direct) {
-    if (!r->gather) {
-      r->gather.reset(new GatherPool);
-      const int want = ctx->get(OPT_HOST_THREADS, 0);
-      r->gather->start(want >= 1 && want <= 64 ? want : default_staging_threads());
-    }
-    r->gather->submit_range(frames, r->p_bytes.p, fb, cstart, nch, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
+    gp = &r->staging_threads();
+    gp->submit_range(frames, r->p_bytes.p, fb, plan.cstart, plan.nch, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
     src = r->p_bytes.p;
   }
-  hipError_t err = hipSuccess;
-  std::string fail;
-  int recorded = 0;   // chunks whose output transfer THIS call has queued (ev_out[c] recorded)
-  int scattered = 0;  // ... whose outputs have been handed to the caller (only from pinned staging)
-  auto scatter_chunk = [&](int c) {
-    const size_t at = cstart[c], len = cstart[c + 1] - at;
-    if (out_interleaved) {
-      std::memcpy(ilv_host + at * ofb, ilv_pin + at * ofb, len * ofb);
-    } else {
-      const float *base = r->p_out.p + (size_t)N * at;
-      for (int ch = 0; ch < N; ch++) std::memcpy(out[ch] + at, base + (size_t)ch * len, sizeof(float) * len);
-    }
-  };
-  for (int c = 0; c < nch; c++) {
-    const size_t at = cstart[c], len = cstart[c + 1] - at;
-    float *din = r->d_in.p + (size_t)M * at, *dout = r->d_out.p + (size_t)N * at;
-    if (!direct) {
-      GatherPool &gp = *r->gather;
-      while (gp.done[c].load(std::memory_order_acquire) < gp.nthreads()) {
-        // (meanwhile: outputs of chunks whose transfer this call queued and that have landed go back to the caller)
-        if (!out_direct && scattered < recorded && err == hipSuccess && fail.empty() &&
-            hipEventQuery(r->pipe.ev_out[scattered]) == hipSuccess)
-          scatter_chunk(scattered++);
-        else
-          std::this_thread::yield();
-      }
-    }
-    if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
-    err = hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
-    if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_in[c], r->pipe.in);
-    if (err == hipSuccess) err = hipStreamWaitEvent(ctx->stream, r->pipe.ev_in[c], 0);
-    if (err != hipSuccess) continue;
-    try {
-      launch_pcm_to_rows(fmt, r->d_bytes.p + at * fb, fb, first_byte, M, len, din, len, ctx->stream);
-      const int64_t t0 = r->t;
-      r->process_device(len / r->B, din, len, dout, len);
-      if (out_interleaved) launch_interleave(dout, len, len, at, t0);
-    } catch (const Error &e) {
-      fail = e.msg;
-      continue;
-    }
-    err = hipEventRecord(r->pipe.ev_k[c], ctx->stream);
-    if (err == hipSuccess) err = hipStreamWaitEvent(r->pipe.out, r->pipe.ev_k[c], 0);
-    if (err != hipSuccess) continue;
-    if (out_interleaved)
-      err = hipMemcpyAsync((out_direct ? ilv_host : ilv_pin) + at * ofb, ilv_dev + at * ofb, len * ofb, hipMemcpyDeviceToHost, r->pipe.out);
-    else if (out_st)
-      err = hipMemcpy2DAsync(out0 + at, sizeof(float) * out_st, dout, sizeof(float) * len, sizeof(float) * len, N, hipMemcpyDeviceToHost,
-                             r->pipe.out);
-    else
-      err = hipMemcpyAsync(r->p_out.p + (size_t)N * at, dout, sizeof(float) * len * N, hipMemcpyDeviceToHost, r->pipe.out);
-    if (err == hipSuccess) err = hipEventRecord(r->pipe.ev_out[c], r->pipe.out);
-    if (err == hipSuccess) recorded = c + 1;
-  }
-  if (!direct) r->gather->wait_all();
-  (void)hipStreamSynchronize(r->pipe.in);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipStreamSynchronize(r->pipe.out);
-  EARHIP_HIP(err);
-  if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
-  if (!out_direct)
-    for (; scattered < nch; scattered++) scatter_chunk(scattered);
-  r->last_host_chunks = nch;
+  run_host_chunks(
+      r->pipe, gp, plan, ctx->stream, !out_direct, &r->last_host_chunks,
+      [&](size_t at, size_t len) {
+        return hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
+      },
+      [&](size_t at, size_t len) {
+        float *din = r->d_in.p + (size_t)M * at, *dout = r->d_out.p + (size_t)N * at;
+        launch_pcm_to_rows(fmt, r->d_bytes.p + at * fb, fb, first_byte, M, len, din, len, ctx->stream);
+        const int64_t t0 = r->t;
+        r->process_device(len / r->B, din, len, dout, len);
+        if (out_interleaved) launch_interleave(dout, len, len, at, t0);
+      },
+      [&](size_t at, size_t len) {
+        if (!out_interleaved) return r->chunk_rows_d2h(out0, out_st, at, len);
+        return hipMemcpyAsync((out_direct ? ilv_host : ilv_pin) + at * ofb, ilv_dev + at * ofb, len * ofb, hipMemcpyDeviceToHost, r->pipe.out);
+      },
+      [&](size_t at, size_t len) {
+        if (out_interleaved) std::memcpy(ilv_host + at * ofb, ilv_pin + at * ofb, len * ofb);
+        else r->chunk_rows_scatter(out, at, len);
+      },
+      [] { return 0.0; });
 }
 
 int earhip_render_process_frames(earhip_render *r, size_t nblocks, const void *frames, earhip_pcm_format fmt, int frame_channels,
@@ -1302,19 +1000,10 @@ int earhip_render_process_frames_device(earhip_render *r, size_t nblocks, const 
     require(out_dev != nullptr, "out_dev must not be NULL");
     require(out_interleaved ? out_stride >= (size_t)r->N : out_stride >= nblocks * r->B, "stride too small");
     if (nblocks == 0) return;
-    earhip_ctx *ctx = r->ctx;
-    ctx->use();
-    const size_t S = (size_t)pcm_sample_bytes(fmt);
-    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
-    if (r->d_rows.n < cap * r->M || (out_interleaved && r->d_rows_out.n < cap * r->N)) {
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (first use: nothing of this renderer may still read them)
-      r->d_rows.reserve(cap * r->M);
-      if (out_interleaved) r->d_rows_out.reserve(cap * r->N);
-    }
-    launch_pcm_to_rows(fmt, frames_dev, (size_t)frame_channels * S, (size_t)first_channel * S, r->M, n, r->d_rows.p, n, ctx->stream);
+    const size_t n = r->frames_to_device_rows(nblocks, frames_dev, fmt, frame_channels, first_channel, out_interleaved != 0);
     if (out_interleaved) {
       r->process_device(nblocks, r->d_rows.p, n, r->d_rows_out.p, n);
-      launch_rows_to_frames(r->d_rows_out.p, n, r->N, n, out_dev, out_stride, ctx->stream);
+      launch_rows_to_frames(r->d_rows_out.p, n, r->N, n, out_dev, out_stride, r->ctx->stream);
     } else {
       r->process_device(nblocks, r->d_rows.p, n, out_dev, out_stride);
     }
@@ -1338,28 +1027,16 @@ int earhip_render_process_frames_pcm_device(earhip_render *r, size_t nblocks, co
                                             size_t out_first_byte, const earhip_pcm_out *out) {
   return guarded([&] {
     check_frames_args(r, nblocks, frames_dev, fmt, frame_channels, first_channel);
-    const size_t So = check_pcm_out(out);
-    require(out_dev != nullptr, "out_dev must not be NULL");
-    require(So == 3 || reinterpret_cast<uintptr_t>(out_dev) % So == 0, "out_dev not aligned to the sample size");
-    require(out_frame_bytes >= (size_t)r->N * So, "out_frame_bytes smaller than n_out samples");
-    require(out_first_byte <= out_frame_bytes - (size_t)r->N * So, "out_first_byte + n_out samples exceed out_frame_bytes");
-    require(So == 3 || (out_frame_bytes % So == 0 && out_first_byte % So == 0), "out_frame_bytes / out_first_byte not multiples of the sample size");
+    check_pcm_out_frame(r->N, check_pcm_out(out), out_dev, out_frame_bytes, out_first_byte, "n_out");
     if (nblocks == 0) return;
     earhip_ctx *ctx = r->ctx;
     ctx->use();
-    const size_t S = (size_t)pcm_sample_bytes(fmt);
-    const size_t n = nblocks * r->B, cap = (size_t)r->T * r->B;
-    if (r->d_rows.n < cap * r->M || r->d_rows_out.n < cap * r->N) {
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (first use: nothing of this renderer may still read them)
-      r->d_rows.reserve(cap * r->M);
-      r->d_rows_out.reserve(cap * r->N);
-    }
-    r->reserve_levels();
-    launch_pcm_to_rows(fmt, frames_dev, (size_t)frame_channels * S, (size_t)first_channel * S, r->M, n, r->d_rows.p, n, ctx->stream);
+    r->levels.reserve(r->N, ctx->stream);
+    const size_t n = r->frames_to_device_rows(nblocks, frames_dev, fmt, frame_channels, first_channel, true);
     const int64_t t0 = r->t;
     r->process_device(nblocks, r->d_rows.p, n, r->d_rows_out.p, n);
     launch_rows_to_pcm(*out, r->d_rows_out.p, n, r->N, n, static_cast<unsigned char *>(out_dev), out_frame_bytes, out_first_byte,
-                       r->d_peak.p, r->d_clip.p, t0, ctx->stream);
+                       r->levels.peak.p, r->levels.clip.p, t0, ctx->stream);
   });
 }
 
@@ -1370,24 +1047,8 @@ int earhip_render_output_levels(earhip_render *r, float *peak, uint64_t *clipped
     earhip_ctx *ctx = r->ctx;
     ctx->use();
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    if (!r->d_peak.p) {  // (no PCM-out call yet)
-      for (int c = 0; c < r->N; c++) peak[c] = 0.f, clipped[c] = 0;
-      return;
-    }
-    // (the kernel keeps kLevelSlots copies: the maximum / the sum over them; bits of non-negative floats order as integers)
-    const size_t cnt = (size_t)kLevelSlots * r->N;
-    std::vector<unsigned> pk(cnt);
-    std::vector<unsigned long long> cl(cnt);
-    EARHIP_HIP(hipMemcpy(pk.data(), r->d_peak.p, sizeof(unsigned) * cnt, hipMemcpyDeviceToHost));
-    EARHIP_HIP(hipMemcpy(cl.data(), r->d_clip.p, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost));
-    for (int c = 0; c < r->N; c++) {
-      unsigned m = 0;
-      uint64_t sum = 0;
-      for (int k = 0; k < kLevelSlots; k++) m = std::max(m, pk[(size_t)k * r->N + c]), sum += cl[(size_t)k * r->N + c];
-      std::memcpy(&peak[c], &m, sizeof(float));
-      clipped[c] = sum;
-    }
-    if (reset) r->zero_levels();
+    r->levels.read(r->N, peak, clipped);  // (zeros before the first PCM-out call)
+    if (reset) r->levels.zero(ctx->stream);
   });
 }
 
@@ -1440,15 +1101,8 @@ int earhip_render_hinge_standby(earhip_render *r, int *standby) {
   return guarded([&] {
     require(r != nullptr && standby != nullptr, "NULL argument");
     *standby = 0;
-    earhip_ctx *ctx = r->ctx;
-    // (the copy of the mode word the call's own gain kernel left in this renderer's slot: valid until this renderer's next call)
     if (r->last_kind != 5 || !r->last_gated || r->last_hg_robust) return;  // (robust form allowed: nobody stands by)
-    ctx->use();
-    unsigned word = 0;
-    EARHIP_HIP(hipMemcpyAsync(&word, r->rec.p, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    if (!(word & kModeRecorded)) fail_internal("no gain kernel recorded the call's mode word");
-    *standby = (word & kGateHingeUnsafe) ? 1 : 0;
+    *standby = (r->mode_word() & kGateHingeUnsafe) ? 1 : 0;
   });
 }
 
@@ -1456,14 +1110,8 @@ int earhip_render_hinge_robust(earhip_render *r, int *robust) {
   return guarded([&] {
     require(r != nullptr && robust != nullptr, "NULL argument");
     *robust = 0;
-    earhip_ctx *ctx = r->ctx;
     if (r->last_kind != 5 || !r->last_hg_robust) return;
-    ctx->use();
-    unsigned word = 0;
-    EARHIP_HIP(hipMemcpyAsync(&word, r->rec.p, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    if (!(word & kModeRecorded)) fail_internal("no gain kernel recorded the call's mode word");
-    *robust = hinge_span_exceeded(word, r->M) ? 1 : 0;
+    *robust = hinge_span_exceeded(r->mode_word(), r->M) ? 1 : 0;
   });
 }
 
@@ -1471,15 +1119,9 @@ int earhip_render_wide_form(earhip_render *r, int *wide) {
   return guarded([&] {
     require(r != nullptr && wide != nullptr, "NULL argument");
     *wide = 1;
-    earhip_ctx *ctx = r->ctx;
     if (r->last_kind < 3) *wide = -1;  // (no split operands at all)
     if (r->last_kind < 3 || !r->last_device_form) return;
-    ctx->use();
-    unsigned word = 0;
-    EARHIP_HIP(hipMemcpyAsync(&word, r->rec.p, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    if (!(word & kModeRecorded)) fail_internal("no gain kernel recorded the call's mode word");
-    *wide = (word & 1u) ? 1 : 0;
+    *wide = (r->mode_word() & 1u) ? 1 : 0;
   });
 }
 
@@ -1527,13 +1169,3 @@ int earhip_render_last_plan(const earhip_render *r, int out[4]) {
 }
 
 }  // extern "C"
-
-// group F's PCM conversion for the limiter's PCM form (common.h)
-namespace earhip {
-size_t pcm_out_check(const earhip_pcm_out *out) { return check_pcm_out(out); }
-int pcm_level_slots() { return kLevelSlots; }
-void pcm_out_rows(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out, size_t frame_bytes,
-                  size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s) {
-  launch_rows_to_pcm(o, in, in_stride, N, len, out, frame_bytes, first_byte, peak, clipped, t0, s);
-}
-}  // namespace earhip

@@ -110,6 +110,18 @@ struct PinBuf {
   }
 };
 
+// The small host forms' rows: C pageable rows of n samples to or from a device buffer [C][n], enqueued on a stream (`only`: just
+// the rows listed there — the others' pointers are not looked at).
+inline void rows_to_device(float *dev, const float *const *rows, int C, size_t n, hipStream_t s, const std::vector<int> *only = nullptr) {
+  for (int i = 0; i < (only ? (int)only->size() : C); i++) {
+    const int c = only ? (*only)[(size_t)i] : i;
+    EARHIP_HIP(hipMemcpyAsync(dev + (size_t)c * n, rows[c], sizeof(float) * n, hipMemcpyHostToDevice, s));
+  }
+}
+inline void rows_from_device(float *const *rows, const float *dev, int C, size_t n, hipStream_t s) {
+  for (int c = 0; c < C; c++) EARHIP_HIP(hipMemcpyAsync(rows[c], dev + (size_t)c * n, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+}
+
 }  // namespace earhip
 
 struct earhip_vbs;
@@ -230,11 +242,4 @@ void limiter_check_room(const earhip_limiter *lim, size_t nsamples);
 void limiter_feed(earhip_limiter *lim, size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride);
 const earhip_ctx *limiter_ctx(const earhip_limiter *lim);
 int limiter_channels(const earhip_limiter *lim);
-// group F's PCM conversion (api_render.hip) as the limiter's PCM form uses it: what every PCM-out form refuses (returns the
-// output sample size), the number of copies of the levels k_rows_to_pcm keeps ([slots][N] each), and the launch itself: planar
-// rows [N][in_stride] (samples [0, len), the first at sample clock t0) -> bytes [first_byte, + N * sample size) of each frame
-size_t pcm_out_check(const earhip_pcm_out *out);
-int pcm_level_slots();
-void pcm_out_rows(const earhip_pcm_out &o, const float *in, size_t in_stride, int N, size_t len, unsigned char *out, size_t frame_bytes,
-                  size_t first_byte, unsigned *peak, unsigned long long *clipped, int64_t t0, hipStream_t s);
 }  // namespace earhip

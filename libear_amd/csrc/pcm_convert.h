@@ -1,6 +1,7 @@
 // pcm_convert.h — the float -> PCM conversion include/earhip.h defines for earhip_render_process_frames_pcm (group F), as one
 // function the device kernel (pcm_out_kernels.h) and a plain C++ program on the CPU (tests/cpp/test_pcm_convert.cpp) both compile:
-// what is tested against the numpy model on the CPU is the code the kernel runs.  No HIP header is needed to include it.
+// what is tested against the numpy model on the CPU is the code the kernel runs — and the host fold of the levels that kernel
+// keeps (pcm_levels_fold).  No HIP header is needed to include it.
 //
 // Every floating-point step is ONE float32 operation rounded once.  What keeps the dither add apart from the multiply before it
 // is the build's -ffp-contract=off (csrc/Makefile; the host test passes it too): __fadd_rn is a plain add to this compiler.
@@ -8,7 +9,9 @@
 // overflow saturates either way — but the definition is the two-step one.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define EARHIP_PCM_HD __host__ __device__
@@ -78,6 +81,23 @@ EARHIP_PCM_HD inline int32_t pcm_from_float(float x, float d, bool *clipped) {
   }
   *clipped = false;
   return (int32_t)r;  // (exact: r is an integer inside the range of int32)
+}
+
+// The levels of the kernel that converts (pcm_out_kernels.h keeps `slots` copies [slots][C] of each, so that its waves do not all
+// meet on C addresses) folded on the host: per channel the largest of the peaks' bit patterns — bits of non-negative floats order
+// as integers — and the sum of the clip counts.
+inline void pcm_levels_fold(int slots, int C, const unsigned *peak_bits, const unsigned long long *clip_counts, float *peak,
+                            uint64_t *clipped) {
+  for (int c = 0; c < C; c++) {
+    unsigned m = 0;
+    uint64_t sum = 0;
+    for (size_t at = (size_t)c; at < (size_t)slots * (size_t)C; at += (size_t)C) {
+      if (peak_bits[at] > m) m = peak_bits[at];
+      sum += clip_counts[at];
+    }
+    std::memcpy(&peak[c], &m, sizeof(float));
+    clipped[c] = sum;
+  }
 }
 
 }  // namespace earhip

@@ -8,11 +8,15 @@
 //     takes the same one of the two as the device does for its table's shape.  Every y is a fixed function of `taps` input
 //     samples, so how a stream is cut into calls cannot change a bit of it;
 //   - the two maxima (|y| and |x|) ignore NaN and are exact, so neither their order nor their grouping matters;
-//   - a one-channel meter on the CPU that carries taps - 1 samples of history and the peaks of the open 100 ms step.
+//   - a one-channel meter on the CPU that carries taps - 1 samples of history and the peaks of the open 100 ms step;
+//   - the table a meter or a limiter is made with (TpTable): the caller's earhip_true_peak checked, or annex 2's.
 #pragma once
 #include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <vector>
+
+#include "../../include/earhip.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define EARHIP_TP_HD __host__ __device__
@@ -39,6 +43,36 @@ inline void true_peak_default_table(double h[4][12]) {
     h[2][k] = kTruePeakTable8192[1][11 - k] / 8192.0;
     h[3][k] = kTruePeakTable8192[0][11 - k] / 8192.0;
   }
+}
+
+// The table as the kernels take it: v [phases][taps] in float32 for the device, and h, the same numbers where the shape is 4 x 12
+// (the kernels of that shape take them as an argument), else zero.
+struct TpTable { int phases = 0, taps = 0; std::vector<float> v; float h[4][12] = {}; };
+
+// The caller's table (tp->coeffs) or, without one (tp or tp->coeffs NULL), annex 2's for the rates it was designed for.
+// Returns why the table is refused, or nullptr.
+inline const char *tp_table_make(const earhip_true_peak *tp, int sample_rate, TpTable *t) {
+  if (tp && tp->coeffs) {
+    if (!(tp->phases >= 1 && tp->phases <= kTpMaxPhases)) return "true peak: phases must be in [1, 8]";
+    if (!(tp->taps >= 1 && tp->taps <= kTpMaxTaps)) return "true peak: taps must be in [1, 64]";
+    t->phases = tp->phases, t->taps = tp->taps;
+    t->v.resize((size_t)t->phases * (size_t)t->taps);
+    for (size_t i = 0; i < t->v.size(); i++) {
+      if (!(std::isfinite(tp->coeffs[i]) && std::isfinite((float)tp->coeffs[i]))) return "true peak: coefficients must be finite";
+      t->v[i] = (float)tp->coeffs[i];
+    }
+  } else {
+    if (sample_rate != 44100 && sample_rate != 48000)
+      return "the built-in true-peak table is 4x oversampling for 44100 and 48000 Hz: another rate must bring its own";
+    double h[4][12];
+    true_peak_default_table(h);
+    t->phases = 4, t->taps = 12;
+    t->v.resize(48);
+    for (int i = 0; i < 48; i++) t->v[(size_t)i] = (float)h[i / 12][i % 12];
+  }
+  if (t->phases == 4 && t->taps == 12) std::memcpy(t->h, t->v.data(), sizeof(t->h));
+  else std::memset(t->h, 0, sizeof(t->h));
+  return nullptr;
 }
 
 // one output of one phase: x(k) = x[n - k]

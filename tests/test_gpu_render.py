@@ -1196,3 +1196,70 @@ def test_curves_updated_object_by_object_between_block_mode_calls(force):
         assert kernel == 5, kernel
     assert np.array_equal(got, got_full)
     assert scenes.rel_rms_per_channel(got, want) <= 1e-6
+
+
+def test_every_tap_refuses_through_every_entry_point_and_changes_nothing():
+    """A meter, a 2 x 2 FIR matrix and a limiter on one renderer's bus (4 objects, 0+2+0, blocks of 64, at most 4 per call).  Each
+    tap in turn is the one without room — the meter's max_steps reached, the matrix's sink full, the limiter's sink full — and
+    the call is made through each of the six process entry points: invalid argument with that tap's message, the output buffer
+    keeps its sentinel, no tap moves; the call that fits afterwards renders the bits of a renderer that saw no refused call."""
+    import torch
+    import loudness_model as lm
+    from libear_amd import capi
+    names = LAYOUTS["0+2+0"]
+    M, N, B, T = 4, len(names), 64, 4
+    rate = 1280  # (a 100 ms step of 128 samples = two blocks: a few blocks reach a small meter's max_steps)
+    c = ctx()
+    dec = decorrelators("0+2+0")
+    curves = scenes.ragged_curves(M, N, 8 * B, seed=91)
+    x = scenes.audio(M, 5 * B, seed=92)
+    first, again, fits = x[:, :2 * B], np.ascontiguousarray(x[:, 2 * B:4 * B]), x[:, 4 * B:]
+    frames = np.ascontiguousarray(again.T)  # [2 B][M] float32 frames
+    x_dev, frames_dev = torch.from_numpy(again).cuda(), torch.from_numpy(frames).cuda()
+    taps = np.random.default_rng(93).uniform(-0.5, 0.5, (2, N, 40)).astype(np.float32)
+    r, never = (capi.Renderer(c, M, N, B, dec, 0, max_blocks=T) for _ in range(2))
+    for v in (r, never):
+        set_renderer_curves(v, curves)
+    fm = capi.FirMatrix(c, taps, B, max_blocks=T)
+    lim = capi.Limiter(c, N, 0.05, 16, 32, max_samples=T * B)
+    meters = {True: capi.Loudness(c, N, rate, max_steps=1, coeffs=lm.COEFFS), False: capi.Loudness(c, N, rate, max_steps=64, coeffs=lm.COEFFS)}
+    fsink = torch.zeros((2, 8 * B), dtype=torch.float32, device="cuda")
+    lsink = torch.zeros((N, 8 * B), dtype=torch.float32, device="cuda")
+    tight, roomy = 3 * B, 8 * B  # (room for the first call and one block more / for everything)
+    want = [never.process(first), never.process(fits)]
+    messages = {"meter": "the call would pass the loudness meter's max_steps", "matrix": "the call would pass the FIR matrix's sink_capacity",
+                "limiter": "the call would pass the limiter's sink_capacity"}
+
+    def refused(call, out, sentinel):
+        with pytest.raises(capi.InvalidArgument) as e:
+            call()
+        assert e.value.code == capi.INVALID_ARGUMENT and messages[tap] in str(e.value), str(e.value)
+        c.synchronize()
+        assert bool((out == sentinel).all()), "a refused call wrote to its output buffer"
+        assert (r.fir_matrix_position(), r.limiter_position(), meter.num_steps()) == (2 * B, 2 * B, 1)
+
+    try:
+        for tap in ("meter", "matrix", "limiter"):
+            meter = meters[tap == "meter"]
+            r.reset(0), meter.reset(), fm.reset(), lim.reset()
+            r.attach_loudness(meter)
+            r.attach_fir_matrix(fm, fsink.data_ptr(), 8 * B, tight if tap == "matrix" else roomy)
+            r.attach_limiter(lim, lsink.data_ptr(), 8 * B, tight if tap == "limiter" else roomy)
+            assert np.array_equal(r.process(first).view(np.uint32), want[0].view(np.uint32))
+            o_dev = torch.full((N, 2 * B), -3.0, dtype=torch.float32, device="cuda")
+            refused(lambda: r.process_device(2, x_dev.data_ptr(), 2 * B, o_dev.data_ptr(), 2 * B), o_dev, -3.0)
+            o = np.full((N, 2 * B), -3.0, np.float32)
+            refused(lambda: r.process_into(again, o), o, -3.0)
+            refused(lambda: r.process_frames_into(frames, o, "f32"), o, -3.0)
+            refused(lambda: r.process_frames_device(2, frames_dev.data_ptr(), "f32", M, 0, o_dev.data_ptr(), 2 * B), o_dev, -3.0)
+            q = np.full((2 * B, N), 0x5A5A, np.int16)
+            refused(lambda: r.process_frames_pcm_into(frames, q, "f32", out_fmt="s16"), q, 0x5A5A)
+            q_dev = torch.full((2 * B, N), 0x5A5A, dtype=torch.int16, device="cuda")
+            refused(lambda: r.process_frames_pcm_device(2, frames_dev.data_ptr(), "f32", M, 0, q_dev.data_ptr(), 2 * N), q_dev, 0x5A5A)
+            got = r.process(fits)  # one block: it fits every tap
+            assert np.array_equal(got.view(np.uint32), want[1].view(np.uint32)), f"a call refused by the {tap} changed the render state"
+            assert (r.fir_matrix_position(), r.limiter_position(), meter.num_steps()) == (3 * B, 3 * B, 1)
+    finally:
+        r.attach_loudness(None), r.attach_fir_matrix(None), r.attach_limiter(None)
+        for v in (r, never, fm, lim, *meters.values()):
+            v.close()

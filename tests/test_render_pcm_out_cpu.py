@@ -131,6 +131,20 @@ def edge_values():
     return np.concatenate([x, np.nextafter(x, np.float32(np.inf)), np.nextafter(x, np.float32(-np.inf))])
 
 
+def test_level_fold_on_the_host(tmp_path):
+    """pcm_convert.h, pcm_levels_fold (what both output_levels calls return): 64 slots x 3 channels of chosen bit patterns and
+    counts — the largest pattern per channel, the sum of the counts (one above 2^32), an all-zero channel — under ASan + UBSan"""
+    exe = tmp_path / "test_pcm_levels"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "libear_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "test_pcm_levels.cpp"), "-o", str(exe)],
+                   check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+    print(res.stdout)
+    assert res.returncode == 0, res.stdout
+
+
 def test_shared_conversion_header_on_the_host_equals_the_model(tmp_path):
     """pcm_convert.h, the function k_rows_to_pcm calls, built with the host compiler: every edge value and a few thousand random
     ones, all formats, with and without dither, bit for bit the model's samples, clip flags and hash values (the samples laid

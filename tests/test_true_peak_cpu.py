@@ -121,6 +121,20 @@ def test_nan_and_infinity_in_the_header_and_the_model():
     assert tm.worst_ratio(tp[:1], want["step_tp"][:1, 0], None, 0.5) <= 1.0
 
 
+def test_table_setup_shared_by_the_meter_and_the_limiter_on_cpu(tmp_path):
+    """libear_amd/csrc/true_peak.h, tp_table_make (what earhip_loudness_create_tp and earhip_limiter_create are made with): the
+    built-in table, callers' tables of the extreme shapes, h for 4 x 12 alone, every refusal's message — under ASan + UBSan"""
+    exe = tmp_path / "test_tp_table"
+    src = os.path.join(ROOT, "tests", "cpp", "test_tp_table.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "libear_amd", "csrc"), src, "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+    print(res.stdout)
+    assert res.returncode == 0, res.stdout
+
+
 # ---- loudness range ---------------------------------------------------------------------------------------------------------------
 def programme(levels, seconds=20.0):
     t = np.arange(int(round(RATE * seconds))) / RATE

@@ -1,6 +1,6 @@
 """Register / scratch / LDS use of the kernels of one translation unit, as the compiler reports them:
     python tools/kernel_resources.py libear_amd/csrc/api_render.hip [filter] [-DNAME=VALUE ...]
-(hipcc --save-temps into a temporary directory; reads the .amdgpu_metadata of the gfx950 assembly)"""
+(the PCM conversion kernels: libear_amd/csrc/api_frames.hip; hipcc --save-temps into a temporary directory; reads the .amdgpu_metadata of the gfx950 assembly)"""
 import os, re, subprocess, sys, tempfile
 src = os.path.abspath(sys.argv[1])
 filt = next((a for a in sys.argv[2:] if not a.startswith("-")), "")
