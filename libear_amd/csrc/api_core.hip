@@ -7,6 +7,7 @@
 #include <string>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
 #include "curves.h"
@@ -25,392 +26,451 @@ static_assert(kSplitTile == 256, "MixLaunch::tile() and tiles_aligned(256, ...) 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &msg) { g_last_error = msg; }
 
-size_t mix_lds_bytes(const ColumnPlan &cp, const MixLaunch &ml) {
-  if (ml.wsplit <= 1 || ml.split || ml.pieces || ml.hinge) return 0;
-  if (ml.mfma) return (size_t)cp.mgroups * ml.tpw * cp.nct * 16 * ml.tile() * sizeof(float);
-  return (size_t)cp.ngroups * cp.nout * ml.tile() * sizeof(float);
+// One of a fixed list of values as a compile-time constant: f(Int<V>{}) for the V that v equals.  Every launcher below turns its
+// runtime shape (column tiles, waves, tiles per workgroup) into the template arguments of its kernel this way; the lists are
+// the instantiations the library holds.
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <int... Vs, typename F>
+static void dispatch(int v, F &&f) {
+  if (!((v == Vs ? (f(Int<Vs>{}), true) : false) || ...)) fail_internal("no gain kernel instantiation for this launch plan");
+}
+template <int... Vs, typename F>
+static void for_each(F &&f) {
+  (f(Int<Vs>{}), ...);
 }
 
-template <int NCT, int NRT>
-static void launch_mfma_t(const GainMixParams &P, dim3 grid, dim3 block, size_t lds,
-                          hipStream_t s) {
-  hipLaunchKernelGGL((k_gain_mix_mfma<NCT, NRT>), grid, block, lds, s, P);
+// every instantiation of k_hinge_build, f(tiles per workgroup, waves of the gain kernel): its launch picks one, and
+// hinge_build_allow_lds raises the LDS limit of each
+template <typename F>
+static void for_each_hinge_build(F &&f) {
+  for_each<1, 2, 4, 8>([&](auto T) { f(T, Int<4>{}), f(T, Int<8>{}); });
 }
 
-template <int NOUT, int SPL, bool STRICT>
-static void launch_mix_t(const GainMixParams &P, dim3 grid, dim3 block, size_t lds,
-                         hipStream_t s) {
-  hipLaunchKernelGGL((k_gain_mix<NOUT, SPL, STRICT>), grid, block, lds, s, P);
-}
-
-void launch_gain_mix(earhip_ctx *ctx, const CurveSet &cs, const MixLaunch &ml, bool strict,
-                     int64_t t_call, int nsamples, const float *in_dev, size_t in_stride,
-                     float *out_dev, size_t out_stride, size_t part_stride, SegDesc *desc,
-                     hipEvent_t *ev) {
-  const ColumnPlan &cp = cs.plan();
-  const PointStore ps = cs.device();
-  const int M = cs.M();
-  const bool slots = ml.mfma && !ml.split && !ml.pieces && !ml.hinge && !ml.f32grid;
-  if (slots && M > kMaxSlotObjects) fail_internal("slot lists address objects with 16 bits");
-  if (ev) EARHIP_HIP(hipEventRecord(ev[0], ctx->stream));
-  // K0: segment descriptors; for the f32 MFMA kernel K0s then turns them into the
-  // tiles' slot lists, which live behind the descriptors in the same buffer (desc_units())
-  // short curves (static or nearly static gains, <= 8 points per object on average): K0s finds
-  // the segments itself and the descriptor pass is skipped; with long curves the 16-lanes-per-
-  // object search of k_seg_prep is the faster one (measured both ways)
-  const bool fused_prep = slots && (size_t)ps.npoints <= (size_t)8 * M;
-  // split-operand kernels: K0 starts with the level probe of the call's inputs (k_level_probe: 64 instants per object; rows
-  // must allow 16-byte loads).  The two level words alternate between calls: this call's probe raises word `li` (zero since
-  // the last such call cleared it), its K1 reads it and clears the other.
-  LevelProbe probe;
+// The context's words of one call of a split-operand kernel.  The two level words alternate between calls: this call's probe
+// raises `level_cur` (zero since the last such call cleared it), its K1 reads it and clears `level_next`; the mode words (bit 0:
+// the grid kernel's wide mode, bit 1: "not the hinge kernel") and the grid kernel's per-tile "some object needs the exact path
+// here" words (gain_h2.h) alternate the same way.  Null: the call has no such word.
+struct CallWords {
   unsigned *level_cur = nullptr, *level_next = nullptr;
-  unsigned *wide_cur = nullptr, *wide_next = nullptr;  // f16x2 kernel: "run this call in wide mode" (gain_h2.h)
-  unsigned *gate = nullptr;                            // hinge kernel: "this call is the piece lists'" (k_hinge_gate)
-  ctx->last_gate_idx = -1;
-  ctx->last_wide_idx = -1;
-  unsigned *const record = ctx->record_slot;  // (the renderer's slot for this call's mode word; consumed here)
-  ctx->record_slot = nullptr;
-  // hinge kernel: what a call whose levels spread beyond the packed-f16 kink products' span gets — the kernel's robust form
-  // (default) or, option HG_ROBUST = 0, the piece lists standing by behind it (rounds 4-5)
-  const bool hg_robust = ml.hinge && ctx->get(OPT_HG_ROBUST, 1) != 0;
-  if ((ml.split || ml.pieces || ml.hinge) && ctx->x_scale_auto && in_stride % 4 == 0 && ((uintptr_t)in_dev & 15) == 0) {
-    // (the words, the per-object levels and the per-tile words below are made where a renderer is created —
-    // reserve_call_words —; a gain stage that comes here first, or a call larger than any renderer of the context announced,
-    // grows them here behind a synchronisation: counted in ctx->lazy_allocs, which a renderer reports with its regrows)
-    if (!ctx->level.p) ctx->level.alloc_zero(4, ctx->stream), ctx->lazy_allocs++;  // [0..1] level words, [2..3] wide-mode words
-    level_cur = ctx->level.p + ctx->level_idx;
-    level_next = ctx->level.p + (ctx->level_idx ^ 1);
-    // a short call (less than two rounds of workgroups: block mode) runs the wide form only: its latency does not
-    // depend on the form, and the second launch — the form that returns at once — is 4-5 us of it
-    // (every call clears the word the NEXT call decides with, whether it decides itself or not)
-    if ((size_t)ml.ntiles * ml.gsplit >= 2 * (size_t)ctx->num_cus) wide_cur = ctx->level.p + 2 + ctx->level_idx;
-    wide_next = ctx->level.p + 2 + (ctx->level_idx ^ 1);
-    gate = ctx->level.p + 2 + ctx->level_idx;  // (the same word: bit 0 the grid kernel's wide mode, bit 1 "not the hinge kernel")
-    ctx->last_gate_idx = ml.hinge ? ctx->level_idx : -1;
-    ctx->last_hinge_robust = hg_robust;
-    ctx->last_wide_idx = wide_cur ? ctx->level_idx : -1;
-    ctx->level_idx ^= 1;
-    // per-object levels (k_level_probe, gain_kernels.h): grown with the largest M this context has seen — contexts are
-    // shared by gain stages of different sizes
-    if (ctx->obj_level_cap < M) {
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-      ctx->obj_level_cap = M + M / 2 + 64;
-      ctx->obj_level.alloc_zero(2 * (size_t)ctx->obj_level_cap, ctx->stream);
-      ctx->lazy_allocs++;
-    }
-    probe.obj_level = ctx->obj_level.p;
-    probe.level = level_cur;
-    const int probe_runs = [&] {  // tuning knob: runs of consecutive samples per object (1 .. 64)
-      const int v = ctx->get(OPT_PROBE_RUNS);
-      return v >= 1 && v <= 64 && (v & (v - 1)) == 0 ? v : 16;
-    }();
-    hipLaunchKernelGGL(k_level_probe, dim3((M + kProbeObjects - 1) / kProbeObjects), dim3(64 * kProbeObjects), 0, ctx->stream, in_dev,
-                       in_stride, nsamples, M, level_cur, ctx->obj_level.p, ctx->obj_level_cap, probe_runs);
-  }
-  // (piece lists: K0 also counts every object's ramps per tile, into the list builder's count words)
-  PieceLists pl;
-  pl.pieces = reinterpret_cast<Piece *>(desc);  // (the list builders need no descriptors)
-  pl.M = M;
-  pl.paired = ml.paired ? 1 : 0;
-  // (the piece lists that stand by behind the hinge kernel have their own tiles: 64 pw samples, whatever the hinge kernel's)
-  const int ptile = ml.hinge ? 64 * ml.pw : ml.tile();
-  const int pnt = ml.hinge ? (nsamples + ptile - 1) / ptile : ml.ntiles;
-  pl.slots = cs.piece_cap(ptile, ml.paired);
-  pl.count = reinterpret_cast<int *>(pl.pieces + (size_t)pl.cap() * pnt);
-  pl.ovf = pl.count + (size_t)8 * pnt;
-  // f16x2 gain kernel: a word per tile, "some object needs the exact path here" (see gain_h2.h)
+  unsigned *wide_cur = nullptr, *wide_next = nullptr;  // "run this call in wide mode"; wide_cur null: the wide form, not decided on the device
+  unsigned *gate = nullptr;                            // the call's mode word (the same word as wide_cur's)
   unsigned *slow_cur = nullptr, *slow_next = nullptr;
-  if (ml.split) {
-    if (ctx->tile_slow_cap < (size_t)ml.ntiles) {
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-      ctx->tile_slow_cap = std::max<size_t>(2 * (size_t)ml.ntiles, 1024);
-      ctx->tile_slow.alloc_zero(2 * ctx->tile_slow_cap, ctx->stream);
-      ctx->lazy_allocs++;
-    }
-    slow_cur = ctx->tile_slow.p + (size_t)ctx->tile_slow_idx * ctx->tile_slow_cap;
-    slow_next = ctx->tile_slow.p + (size_t)(ctx->tile_slow_idx ^ 1) * ctx->tile_slow_cap;
+  unsigned *obj_level = nullptr;  // per-object levels of the probe (k_level_probe); null: no probe ran
+  bool grew = false;
+};
+
+// The one place that makes or grows the context's words: level and mode words, the probe's per-object levels for M objects, the
+// grid kernel's per-tile words for `ntiles` tiles (0: not needed; grown to tile_cap).  Returns how many buffers it made, behind
+// a synchronisation (calls of other stages may be using the old ones).
+static int grow_call_words(earhip_ctx *ctx, int M, size_t ntiles, size_t tile_cap) {
+  int made = 0;
+  if (M > 0 && !ctx->level.p) ctx->level.alloc_zero(4, ctx->stream), made++;  // [0..1] level words, [2..3] mode words
+  const bool grow_obj = ctx->obj_level_cap < M, grow_tiles = ctx->tile_slow_cap < ntiles;
+  if (grow_obj || grow_tiles) EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+  if (grow_obj) {  // (grown with the largest M this context has seen: contexts are shared by gain stages of different sizes)
+    ctx->obj_level_cap = M + M / 2 + 64;
+    ctx->obj_level.alloc_zero(2 * (size_t)ctx->obj_level_cap, ctx->stream);
+    made++;
+  }
+  if (grow_tiles) {
+    ctx->tile_slow_cap = std::max<size_t>(tile_cap, 1024);
+    ctx->tile_slow.alloc_zero(2 * ctx->tile_slow_cap, ctx->stream);
+    ctx->tile_slow_idx = 0;
+    made++;
+  }
+  return made;
+}
+
+// What the split-operand kernels of a call of up to `max_samples` samples on M objects keep PER CONTEXT (tiles of 256 samples at
+// the smallest), made where a renderer is created, so that no process call allocates or synchronises for them.
+void reserve_call_words(earhip_ctx *ctx, int M, size_t max_samples) {
+  const size_t ntiles = (max_samples + 255) / 256;
+  grow_call_words(ctx, M, ntiles, ntiles + ntiles / 4);
+}
+
+// This call's turn of the words, and the level probe of its inputs in front of everything else (k_level_probe: 64 instants per
+// object; rows must allow 16-byte loads; not with a fixed input scale, option XSCALE).  A gain stage that comes here before any
+// renderer was created, or a call larger than any renderer of the context announced, grows the words here: counted in
+// ctx->lazy_allocs and reported as `grew`.
+static CallWords acquire_call_words(earhip_ctx *ctx, const MixLaunch &ml, int M, const float *in_dev, size_t in_stride, int nsamples) {
+  CallWords w;
+  if (!ml.split_operands()) return w;
+  const bool probe = ctx->x_scale_auto && in_stride % 4 == 0 && ((uintptr_t)in_dev & 15) == 0;
+  const size_t slow_tiles = ml.kind == GainKernel::Grid ? (size_t)ml.ntiles : 0;
+  if (!probe && !slow_tiles) return w;
+  if ((probe && (!ctx->level.p || ctx->obj_level_cap < M)) || ctx->tile_slow_cap < slow_tiles) {  // (not on a call a renderer announced)
+    ctx->lazy_allocs += grow_call_words(ctx, probe ? M : 0, slow_tiles, 2 * slow_tiles);
+    w.grew = true;
+  }
+  if (slow_tiles) {
+    w.slow_cur = ctx->tile_slow.p + (size_t)ctx->tile_slow_idx * ctx->tile_slow_cap;
+    w.slow_next = ctx->tile_slow.p + (size_t)(ctx->tile_slow_idx ^ 1) * ctx->tile_slow_cap;
     ctx->tile_slow_idx ^= 1;
   }
-  // hinge kernel: its own list builder (k_hinge_build, gain_hg.h) behind the same probe launch
-  HingeLists hl = hinge_lists(desc, M, ml.ntiles);
-  if (ml.hinge) {
-    if (M > kMaxHingeCached || (ml.tile() != 256 && ml.tile() != 512)) fail_internal("hinge lists: object count or tile out of range");
-    // (the kernel addresses input rows and gain rows with 32-bit byte offsets; plan_mix only picks it within these limits)
-    if (!ps.kink_row0) fail_internal("hinge kernel: the curve set has no kink rows");
-    if (!hinge_addressable(M, in_stride, nsamples, (size_t)ps.kink_row0 + ps.rows, ps.row)) fail_internal("hinge kernel: buffers beyond its 32-bit offsets");
-    unsigned *obj_lv = probe.obj_level;
-    // with a probe: does the hinge kernel's span of levels cover this call?  (decided on the device: k_hinge_gate)
-    if (gate) hipLaunchKernelGGL(k_hinge_gate, dim3((M + 255) / 256), dim3(256), 0, ctx->stream, obj_lv, ctx->obj_level_cap, M, level_cur, gate, wide_cur != nullptr, hg_robust);
-    int tpw = 1;
-    const size_t cached_max = std::min((size_t)kMaxHingeCached, ctx->hinge_build_lds / sizeof(HingeCached));  // (pairs a workgroup may keep)
-    if ((size_t)M > cached_max) fail_internal("hinge lists: more objects than the builder's LDS holds on this device");
-    while (tpw < 8 && ml.ntiles / (2 * tpw) >= ctx->num_cus && (size_t)M * (2 * tpw) <= cached_max) tpw *= 2;
-    if (ctx->has(OPT_HBUILD_TPW)) {  // tuning knob
-      const int v = ctx->get(OPT_HBUILD_TPW);
-      if ((v == 1 || v == 2 || v == 4 || v == 8) && (size_t)M * v <= cached_max) tpw = v;
-    }
-    // two kernels (option BUILD_2K = 1; NOT the default here): k_hinge_classify object-major into the staging matrix behind the
-    // lists, then the builder from its counting loop on, without the LDS its first pass kept its results in.  Measured: classify
-    // 21 us + the builder's second half 42 us against 58 us in one kernel — that half (ranking by ballots over 32 classes between
-    // three barriers per batch, two scattered 16-byte stores per pair) is what the builder is made of, and it does not get faster
-    // at two workgroups per CU.  The lists are the same bit for bit (tests run both).
-    const HingeCached *stage = nullptr;
-    if (ctx->get(OPT_BUILD_2K, 0) != 0) {
-      HingeCached *st = reinterpret_cast<HingeCached *>(desc) + hinge_units((size_t)M, (size_t)ml.ntiles);
-      stage = st;
-      const dim3 cgrid((ml.ntiles + 63) / 64, (M + kClassifyObjects - 1) / kClassifyObjects);
-      if (ml.tile() == 256)
-        hipLaunchKernelGGL((k_hinge_classify<4>), cgrid, dim3(64 * kClassifyObjects), 0, ctx->stream, ps, M, ml.ntiles, t_call, t_call + nsamples, st,
-                           obj_lv, level_cur, hg_robust ? nullptr : gate, hg_robust ? gate : nullptr);
-      else
-        hipLaunchKernelGGL((k_hinge_classify<8>), cgrid, dim3(64 * kClassifyObjects), 0, ctx->stream, ps, M, ml.ntiles, t_call, t_call + nsamples, st,
-                           obj_lv, level_cur, hg_robust ? nullptr : gate, hg_robust ? gate : nullptr);
-      if (!ctx->has(OPT_HBUILD_TPW)) {
-        tpw = 1;
-        while (tpw < 8 && ml.ntiles / (2 * tpw) >= 2 * ctx->num_cus) tpw *= 2;
-      }
-    }
-    const dim3 bgrid((ml.ntiles + tpw - 1) / tpw);
-    const size_t lds = stage ? 0 : sizeof(HingeCached) * (size_t)M * tpw;
-    // (more than 64 KB of dynamic LDS has to be asked for, per device and instantiation: earhip_ctx_create does, hinge_build_allow_lds)
-#define EARHIP_HBUILD_ONE(T_, NW_)                                                                                    \
-  hipLaunchKernelGGL((k_hinge_build<T_, NW_>), bgrid, dim3(kHingeBuildThreads), lds, ctx->stream, ps, M, ml.ntiles, t_call, \
-                     t_call + nsamples, hl, obj_lv, level_cur, hg_robust ? nullptr : gate, hg_robust ? gate : nullptr, stage);
-#define EARHIP_HBUILD_CASE(T_)                                                                                        \
-  if (tpw == T_) {                                                                                                    \
-    if (ml.tile() == 256) EARHIP_HBUILD_ONE(T_, 4)                                                                    \
-    else EARHIP_HBUILD_ONE(T_, 8)                                                                                     \
+  if (!probe) return w;
+  w.level_cur = ctx->level.p + ctx->level_idx;
+  w.level_next = ctx->level.p + (ctx->level_idx ^ 1);
+  // a short call (less than two rounds of workgroups: block mode) runs the wide form only: its latency does not
+  // depend on the form, and the second launch — the form that returns at once — is 4-5 us of it
+  // (every call clears the word the NEXT call decides with, whether it decides itself or not)
+  if ((size_t)ml.ntiles * ml.gsplit >= 2 * (size_t)ctx->num_cus) w.wide_cur = ctx->level.p + 2 + ctx->level_idx;
+  w.wide_next = ctx->level.p + 2 + (ctx->level_idx ^ 1);
+  w.gate = ctx->level.p + 2 + ctx->level_idx;
+  ctx->level_idx ^= 1;
+  w.obj_level = ctx->obj_level.p;
+  const int v = ctx->get(OPT_PROBE_RUNS);  // tuning knob: runs of consecutive samples per object (1 .. 64)
+  const int probe_runs = v >= 1 && v <= 64 && (v & (v - 1)) == 0 ? v : 16;
+  hipLaunchKernelGGL(k_level_probe, dim3((M + kProbeObjects - 1) / kProbeObjects), dim3(64 * kProbeObjects), 0, ctx->stream, in_dev,
+                     in_stride, nsamples, M, w.level_cur, ctx->obj_level.p, ctx->obj_level_cap, probe_runs);
+  return w;
+}
+
+// One call of the gain stage as its K0 and K1 functions see it.
+struct MixCall {
+  earhip_ctx *ctx;
+  const CurveSet &cs;
+  const MixLaunch &ml;
+  const ColumnPlan &cp;
+  PointStore ps;
+  int M, nsamples;
+  int64_t t_call;
+  const float *in_dev;
+  size_t in_stride;  // of the input rows
+  SegDesc *scratch;  // laid out by `lay`
+  ScratchLayout lay;
+  SlotLists sl;   // the views of the scratch buffer the kind has (else zero)
+  PieceLists pl;  // (Hinge: the lists standing by)
+  HingeLists hl;
+  CallWords w;
+  // hinge kernel: what a call whose levels spread beyond the packed-f16 kink products' span gets — the kernel's robust form
+  // (default) or, option HG_ROBUST = 0, the piece lists standing by behind it (rounds 4-5): built and launched behind the hinge
+  // kernel's, for the call it may not take
+  bool hg_robust = false, standby = false;
+  GainMixParams P;  // (K1)
+  hipStream_t stream() const { return ctx->stream; }
+  int64_t t_end() const { return t_call + nsamples; }
+  unsigned *gate_word(bool robust) const { return hg_robust == robust ? w.gate : nullptr; }  // (k_hinge_*: [..., gate, robust gate])
+  unsigned *standby_gate() const { return ml.kind == GainKernel::Hinge ? w.gate : nullptr; }
+  // (the piece lists have tiles of 64 pw samples — behind the hinge kernel whatever its own)
+  int piece_tile() const { return 64 * ml.pw; }
+  int piece_tiles() const { return lay.piece_tiles; }
+  float x_scale() const { return std::ldexp(1.0f, ctx->x_scale_log2); }
+  // workgroups of a split-operand kernel's grid, z: column groups
+  dim3 tile_grid(int x) const { return dim3(x, ml.gsplit, cp.mnz * cp.mgroups); }
+};
+
+// ---- K0
+
+// hinge kernel: the device's decision whose call this is (k_hinge_gate), then its own list builder (k_hinge_build, gain_hg.h)
+static void prep_hinge_lists(const MixCall &c) {
+  earhip_ctx *ctx = c.ctx;
+  const MixLaunch &ml = c.ml;
+  const int M = c.M, nw = ml.tile() / 64;
+  if (M > kMaxHingeCached || (nw != 4 && nw != 8)) fail_internal("hinge lists: object count or tile out of range");
+  // (the kernel addresses input rows and gain rows with 32-bit byte offsets; plan_mix only picks it within these limits)
+  if (!c.ps.kink_row0) fail_internal("hinge kernel: the curve set has no kink rows");
+  if (!hinge_addressable(M, c.in_stride, c.nsamples, (size_t)c.ps.kink_row0 + c.ps.rows, c.ps.row)) fail_internal("hinge kernel: buffers beyond its 32-bit offsets");
+  // with a probe: does the hinge kernel's span of levels cover this call?
+  if (c.w.gate)
+    hipLaunchKernelGGL(k_hinge_gate, dim3((M + 255) / 256), dim3(256), 0, c.stream(), c.w.obj_level, ctx->obj_level_cap, M, c.w.level_cur, c.w.gate,
+                       c.w.wide_cur != nullptr, c.hg_robust);
+  int tpw = 1;
+  const size_t cached_max = std::min((size_t)kMaxHingeCached, ctx->hinge_build_lds / sizeof(HingeCached));  // (pairs a workgroup may keep)
+  if ((size_t)M > cached_max) fail_internal("hinge lists: more objects than the builder's LDS holds on this device");
+  while (tpw < 8 && ml.ntiles / (2 * tpw) >= ctx->num_cus && (size_t)M * (2 * tpw) <= cached_max) tpw *= 2;
+  if (ctx->has(OPT_HBUILD_TPW)) {  // tuning knob
+    const int v = ctx->get(OPT_HBUILD_TPW);
+    if ((v == 1 || v == 2 || v == 4 || v == 8) && (size_t)M * v <= cached_max) tpw = v;
   }
-    EARHIP_HBUILD_CASE(1) EARHIP_HBUILD_CASE(2) EARHIP_HBUILD_CASE(4) EARHIP_HBUILD_CASE(8)
-#undef EARHIP_HBUILD_CASE
-#undef EARHIP_HBUILD_ONE
-  }
-  // piece-list kernel: ONE pass builds the lists (k_piece_build, gain_p2.h) behind a small probe launch
-  const bool one_pass = ml.pieces || ml.hinge;
-  if (ml.pieces || (ml.hinge && gate && !hg_robust)) {  // (behind the hinge kernel's builder: the lists of the call it may not take)
-    if (M > kMaxPieceObjects || ptile > kPieceMaxTile) fail_internal("piece lists: object index or tile out of range");
-    unsigned *obj_lv = probe.obj_level;
-    // tiles per workgroup: as many as leave one workgroup per CU (eight tiles = eight lanes per object reading
-    // neighbouring points beat four tiles and two workgroups per CU: 0.084 vs 0.096 ms on the ADM scene)
-    int tpw = 1;
-    while (tpw < 8 && pnt / (2 * tpw) >= ctx->num_cus) tpw *= 2;
-    if (ctx->has(OPT_BUILD_TPW)) {  // tuning knob
-      const int v = ctx->get(OPT_BUILD_TPW);
-      if (v == 1 || v == 2 || v == 4 || v == 8) tpw = v;
+  // two kernels (option BUILD_2K = 1; NOT the default here): k_hinge_classify object-major into the staging matrix behind the
+  // lists, then the builder from its counting loop on, without the LDS its first pass kept its results in.  Measured: classify
+  // 21 us + the builder's second half 42 us against 58 us in one kernel — that half (ranking by ballots over 32 classes between
+  // three barriers per batch, two scattered 16-byte stores per pair) is what the builder is made of, and it does not get faster
+  // at two workgroups per CU.  The lists are the same bit for bit (tests run both).
+  HingeCached *stage = nullptr;
+  if (ctx->get(OPT_BUILD_2K, 0) != 0) {
+    stage = c.lay.hinge_staging(c.scratch);
+    const dim3 cgrid((ml.ntiles + 63) / 64, (M + kClassifyObjects - 1) / kClassifyObjects);
+    dispatch<4, 8>(nw, [&](auto NW) {
+      hipLaunchKernelGGL((k_hinge_classify<decltype(NW)::value>), cgrid, dim3(64 * kClassifyObjects), 0, c.stream(), c.ps, M, ml.ntiles, c.t_call,
+                         c.t_end(), stage, c.w.obj_level, c.w.level_cur, c.gate_word(false), c.gate_word(true));
+    });
+    if (!ctx->has(OPT_HBUILD_TPW)) {
+      tpw = 1;
+      while (tpw < 8 && ml.ntiles / (2 * tpw) >= 2 * ctx->num_cus) tpw *= 2;
     }
-    const dim3 bgrid((pnt + tpw - 1) / tpw);
-    // two kernels (default; option BUILD_2K = 0: the one-pass builder): classify object-major into the staging matrix behind the
-    // lists (scratch_units holds room for it), then place tile-major
-    PairRec *stage = nullptr;
-    // (default: where the lists are PAIRED — curves that hold most of the time: at most one ramp per object and tile nearly
-    // everywhere, which the staged pair carries; always-ramping curves on packed lists have several per pair, the placing kernel
-    // would walk most pairs itself: 0.097 against 0.076 ms, measured)
-    if (ctx->has(OPT_BUILD_2K) ? ctx->get(OPT_BUILD_2K) != 0 : ml.paired) {
-      stage = reinterpret_cast<PairRec *>(desc) + piece_units((size_t)M, (size_t)pnt, (size_t)pl.slots);
-      hipLaunchKernelGGL(k_piece_classify, dim3((pnt + 63) / 64, (M + kClassifyObjects - 1) / kClassifyObjects), dim3(64 * kClassifyObjects), 0,
-                         ctx->stream, ps, M, pnt, ptile, t_call, t_call + nsamples, pl.paired, stage, obj_lv, level_cur,
-                         ml.hinge ? gate : nullptr);
-    }
-#define EARHIP_BUILD_CASE(T_)                                                                                          \
-  if (tpw == T_)                                                                                                       \
-    hipLaunchKernelGGL(k_piece_build<T_>, bgrid, dim3(kBuildThreads), 0, ctx->stream, ps, M, pnt, ptile, t_call, \
-                       t_call + nsamples, pl, obj_lv, level_cur, ml.hinge ? gate : nullptr, ctx->obj_level_cap, wide_cur, stage);
-    EARHIP_BUILD_CASE(1) EARHIP_BUILD_CASE(2) EARHIP_BUILD_CASE(4) EARHIP_BUILD_CASE(8)
-#undef EARHIP_BUILD_CASE
   }
-  if (!fused_prep && !one_pass) {
-    const dim3 ogrid((M + 15) / 16);
-    QuietMark qm;  // (what the probe found goes into the descriptors as they are made)
-    if (probe.obj_level) {
-      qm.obj_level = probe.obj_level, qm.cap = ctx->obj_level_cap, qm.level = level_cur;
-      qm.wide = ml.split ? wide_cur : nullptr;
-    }
-    if (ml.ntiles >= 2048)
-      hipLaunchKernelGGL(k_seg_prep<4>, dim3((ml.ntiles + 63) / 64, ogrid.x), dim3(256), 0, ctx->stream, ps, M,
-                         ml.ntiles, ml.tile(), t_call, t_call + nsamples, desc, qm, slow_cur);
-    else
-      hipLaunchKernelGGL(k_seg_prep<2>, dim3((ml.ntiles + 31) / 32, ogrid.x), dim3(256), 0, ctx->stream, ps, M,
-                         ml.ntiles, ml.tile(), t_call, t_call + nsamples, desc, qm, slow_cur);
+  const dim3 bgrid((ml.ntiles + tpw - 1) / tpw);
+  // (more than 64 KB of dynamic LDS has to be asked for, per device and instantiation: earhip_ctx_create does, hinge_build_allow_lds)
+  const size_t lds = stage ? 0 : sizeof(HingeCached) * (size_t)M * tpw;
+  for_each_hinge_build([&](auto T, auto NW) {
+    if (tpw == T && nw == NW)
+      hipLaunchKernelGGL((k_hinge_build<decltype(T)::value, decltype(NW)::value>), bgrid, dim3(kHingeBuildThreads), lds, c.stream(), c.ps, M, ml.ntiles,
+                         c.t_call, c.t_end(), c.hl, c.w.obj_level, c.w.level_cur, c.gate_word(false), c.gate_word(true), (const HingeCached *)stage);
+  });
+}
+
+// piece-list kernel: ONE pass builds the lists (k_piece_build, gain_p2.h) behind the probe launch — the call's own, or those
+// standing by behind the hinge kernel's
+static void prep_piece_lists(const MixCall &c) {
+  earhip_ctx *ctx = c.ctx;
+  const MixLaunch &ml = c.ml;
+  const int M = c.M, ptile = c.piece_tile(), pnt = c.piece_tiles();
+  if (M > kMaxPieceObjects || ptile > kPieceMaxTile) fail_internal("piece lists: object index or tile out of range");
+  // tiles per workgroup: as many as leave one workgroup per CU (eight tiles = eight lanes per object reading
+  // neighbouring points beat four tiles and two workgroups per CU: 0.084 vs 0.096 ms on the ADM scene)
+  int tpw = 1;
+  while (tpw < 8 && pnt / (2 * tpw) >= ctx->num_cus) tpw *= 2;
+  if (ctx->has(OPT_BUILD_TPW)) {  // tuning knob
+    const int v = ctx->get(OPT_BUILD_TPW);
+    if (v == 1 || v == 2 || v == 4 || v == 8) tpw = v;
   }
-  SlotLists sl;
-  sl.slots = reinterpret_cast<Slot *>(desc + (size_t)M * ml.ntiles);
-  sl.count = reinterpret_cast<int *>(sl.slots + (size_t)kTileSlots * M * ml.ntiles);
-  sl.ovf = sl.count + (size_t)4 * ml.ntiles;
-  sl.M = M;
-  if (slots)
-    hipLaunchKernelGGL(k_slot_list, dim3(ml.ntiles), dim3(256), 0, ctx->stream, ps, M, ml.tile(),
-                       t_call, t_call + nsamples, fused_prep ? nullptr : desc, sl);
-  if (ev) EARHIP_HIP(hipEventRecord(ev[1], ctx->stream));
+  const PieceLists &pl = c.pl;
+  // two kernels (option BUILD_2K; the one-pass builder otherwise): classify object-major into the staging matrix behind the
+  // lists, then place tile-major
+  // (default: where the lists are PAIRED — curves that hold most of the time: at most one ramp per object and tile nearly
+  // everywhere, which the staged pair carries; always-ramping curves on packed lists have several per pair, the placing kernel
+  // would walk most pairs itself: 0.097 against 0.076 ms, measured)
+  PairRec *stage = nullptr;
+  if (ctx->has(OPT_BUILD_2K) ? ctx->get(OPT_BUILD_2K) != 0 : ml.paired) {
+    stage = c.lay.piece_staging(c.scratch);
+    hipLaunchKernelGGL(k_piece_classify, dim3((pnt + 63) / 64, (M + kClassifyObjects - 1) / kClassifyObjects), dim3(64 * kClassifyObjects), 0,
+                       c.stream(), c.ps, M, pnt, ptile, c.t_call, c.t_end(), pl.paired, stage, c.w.obj_level, c.w.level_cur, c.standby_gate());
+  }
+  dispatch<1, 2, 4, 8>(tpw, [&](auto T) {
+    hipLaunchKernelGGL(k_piece_build<decltype(T)::value>, dim3((pnt + tpw - 1) / tpw), dim3(kBuildThreads), 0, c.stream(), c.ps, M, pnt, ptile, c.t_call,
+                       c.t_end(), pl, c.w.obj_level, c.w.level_cur, c.standby_gate(), ctx->obj_level_cap, c.w.wide_cur, stage);
+  });
+}
+
+// segment descriptors (k_seg_prep: 16 lanes per object search its curve), with what the probe found marked in them as they are made
+static void prep_descriptors(const MixCall &c) {
+  const MixLaunch &ml = c.ml;
+  const unsigned objs = (unsigned)(c.M + 15) / 16;
+  QuietMark qm;
+  if (c.w.obj_level) {
+    qm.obj_level = c.w.obj_level, qm.cap = c.ctx->obj_level_cap, qm.level = c.w.level_cur;
+    qm.wide = ml.kind == GainKernel::Grid ? c.w.wide_cur : nullptr;
+  }
+  if (ml.ntiles >= 2048)
+    hipLaunchKernelGGL(k_seg_prep<4>, dim3((ml.ntiles + 63) / 64, objs), dim3(256), 0, c.stream(), c.ps, c.M, ml.ntiles, ml.tile(), c.t_call,
+                       c.t_end(), c.scratch + c.lay.desc.at, qm, c.w.slow_cur);
+  else
+    hipLaunchKernelGGL(k_seg_prep<2>, dim3((ml.ntiles + 31) / 32, objs), dim3(256), 0, c.stream(), c.ps, c.M, ml.ntiles, ml.tile(), c.t_call,
+                       c.t_end(), c.scratch + c.lay.desc.at, qm, c.w.slow_cur);
+}
+
+// f32 MFMA kernel: K0s turns the descriptors into the tiles' slot lists; `own_search`: it finds the segments itself
+static void prep_slot_lists(const MixCall &c, bool own_search) {
+  hipLaunchKernelGGL(k_slot_list, dim3(c.ml.ntiles), dim3(256), 0, c.stream(), c.ps, c.M, c.ml.tile(), c.t_call, c.t_end(),
+                     own_search ? nullptr : c.scratch + c.lay.desc.at, c.sl);
+}
+
+// ---- K1
+
+static void launch_valu(const MixCall &c, bool strict) {
+  const ColumnPlan &cp = c.cp;
+  const dim3 grid(c.ml.ntiles, c.ml.gsplit, cp.nz), block(64 * cp.ngroups * c.ml.wsplit);
+  const size_t lds = c.ml.wsplit > 1 ? (size_t)cp.ngroups * cp.nout * c.ml.tile() * sizeof(float) : 0;  // (the object splits' sums)
+  dispatch<4, 2>(c.ml.spl, [&](auto SPL) {
+    dispatch<8, 16, 24>(cp.nout, [&](auto NOUT) {
+      constexpr int spl = decltype(SPL)::value, nout = decltype(NOUT)::value;
+      if (!strict) hipLaunchKernelGGL((k_gain_mix<nout, spl, false>), grid, block, lds, c.stream(), c.P);
+      else hipLaunchKernelGGL((k_gain_mix<nout, spl, true>), grid, block, lds, c.stream(), c.P);
+    });
+  });
+}
+
+static void launch_slots(const MixCall &c) {
+  const ColumnPlan &cp = c.cp;
+  const MixLaunch &ml = c.ml;
+  const dim3 grid((ml.ntiles + ml.tpw - 1) / ml.tpw, ml.gsplit, cp.mnz), block(64 * cp.mgroups * ml.tpw * ml.wsplit);
+  const size_t lds = ml.wsplit > 1 ? (size_t)cp.mgroups * ml.tpw * cp.nct * 16 * ml.tile() * sizeof(float) : 0;
+  dispatch<8, 4>(ml.nrt, [&](auto NRT) {
+    dispatch<1, 2, 3>(cp.nct, [&](auto NCT) {
+      hipLaunchKernelGGL((k_gain_mix_mfma<decltype(NCT)::value, decltype(NRT)::value>), grid, block, lds, c.stream(), c.P);
+    });
+  });
+}
+
+// exact f32 on the tile grid (gain_f32g.h): a workgroup per 512-sample tile, descriptors from k_seg_prep
+static void launch_f32grid(const MixCall &c) {
+  if (c.nsamples % kF32GridTile != 0) fail_internal("f32 grid kernel: the call is not whole tiles");
+  dispatch<1, 2, 3>(c.cp.nct, [&](auto NCT) {
+    hipLaunchKernelGGL((k_gain_mix_f32g<decltype(NCT)::value>), c.tile_grid(c.ml.ntiles), dim3(512), 0, c.stream(), c.P, c.ps.zero_row);
+  });
+}
+
+static void launch_grid(const MixCall &c) {
+  earhip_ctx *ctx = c.ctx;
+  const ColumnPlan &cp = c.cp;
+  const MixLaunch &ml = c.ml;
+  const CallWords &w = c.w;
+  // as many workgroups as are resident at once (a multiple of 8: a workgroup's tiles stay on its XCD), each working
+  // through its share of the tiles in one software pipeline (gain_h2.h)
+  const int per_cu = ml.tile() == 512 ? 1 : (cp.nct == 1 ? 3 : 2);  // (the 8-wave forms: 154-243 registers, one workgroup per CU)
+  int wgs = std::max(8, (ctx->num_cus * per_cu / std::max(1, ml.gsplit * cp.mnz * cp.mgroups)) & ~7);
+  if (ctx->has(OPT_H2_WGS)) wgs = std::max(1, ctx->get(OPT_H2_WGS));  // tuning knob
+  wgs = std::max(wgs, ((ml.ntiles + 63) / 64 + 7) & ~7);  // (at most 64 tiles per workgroup: its redo mask)
+  if (!h2_persistent(cp.nct, ml.tile() == 512 ? 8 : 4)) wgs = ml.ntiles;  // (a tile per workgroup)
+  GainMixParams P = c.P;
+  // a workgroup's tiles as one contiguous run (option H2_RUNS: 1 on, 0 off; default: the single-column-tile forms — config 2)
+  P.tile_runs = ctx->has(OPT_H2_RUNS) ? (ctx->get(OPT_H2_RUNS) != 0) : 0;
+  const dim3 grid = c.tile_grid(std::min(ml.ntiles, wgs));
+  const float xs = c.x_scale();
+  const float *gs = c.cs.column_scales();
+  // two forms of the kernel: the 8-wave kernel carries both and branches on the device-side mode word (round 6); the 4-wave
+  // kernels are launched as a pair, back to back: the form the word names runs, the other returns at once
+  // (gain_h2.h; the piece-list and hinge kernels carry both forms in one kernel — for this one the merged kernel measured
+  // slower: config 2 0.224 -> 0.259 ms, its 4-wave form loses a wave per SIMD to the larger of the two register counts);
+  // without a probe only the wide form
+  const bool two_launches = ctx->get(OPT_H2_PAIR, 0) != 0;  // (tuning knob: the 8-wave kernel as a pair of launches, as until round 6)
+  auto h2 = [&](auto NCT, auto NW, auto WIDE) {
+    hipLaunchKernelGGL((k_gain_mix_h2<decltype(NCT)::value, decltype(NW)::value, decltype(WIDE)::value>), grid, dim3(64 * decltype(NW)::value), 0,
+                       c.stream(), P, c.ps.zero_row, xs, gs, w.level_cur, w.level_next, w.slow_cur, w.slow_next, w.wide_cur, w.wide_next);
+  };
+  auto h2_t1 = [&](auto NCT, auto WIDE) {
+    hipLaunchKernelGGL((k_gain_mix_h2_t1<decltype(NCT)::value, 4, decltype(WIDE)::value>), grid, dim3(256), 0, c.stream(), P, c.ps.zero_row, xs, gs,
+                       w.level_cur, w.level_next, w.slow_cur, w.slow_next, w.wide_cur, w.wide_next);
+  };
+  // (the kernel's third argument: 0 the plain form, 1 the wide form, 2 both, picked on the device)
+  dispatch<1, 2, 3>(cp.nct, [&](auto NCT) {
+    if (ml.tile() == 512) {
+      if (w.wide_cur && !two_launches) return h2(NCT, Int<8>{}, Int<2>{});
+      if (w.wide_cur) h2(NCT, Int<8>{}, Int<0>{});
+      h2(NCT, Int<8>{}, Int<1>{});
+    } else if (NCT == 1) {
+      // (a plain `if`, as it has always been: k_gain_mix_h2_t1<1, 4, *> stays in the library though nothing launches it — the set
+      // of instantiated kernels is not this function's to change)
+      if (w.wide_cur) h2(Int<1>{}, Int<4>{}, Int<0>{});
+      h2(Int<1>{}, Int<4>{}, Int<1>{});
+    } else {
+      if (w.wide_cur) h2_t1(NCT, std::false_type{});
+      h2_t1(NCT, std::true_type{});
+    }
+  });
+}
+
+static void launch_pieces(const MixCall &c) {
+  earhip_ctx *ctx = c.ctx;
+  const ColumnPlan &cp = c.cp;
+  const MixLaunch &ml = c.ml;
+  const CallWords &w = c.w;
+  const int pnt = c.piece_tiles();
+  // as many workgroups as are resident at once (a multiple of 8: a workgroup's tiles stay on its XCD), each carrying its
+  // pipeline from one tile's list into the next (gain_p2.h); option P2_WGS: that number (0: a workgroup per tile)
+  int wgs = std::max(8, (ctx->num_cus * (ml.pw == 4 ? 2 : 1) / std::max(1, ml.gsplit * cp.mnz * cp.mgroups)) & ~7);
+  if (ctx->has(OPT_P2_WGS)) wgs = ctx->get(OPT_P2_WGS) > 0 ? ctx->get(OPT_P2_WGS) : pnt;
+  if (!p2_persistent(cp.nct, ml.pw, ml.paired)) wgs = pnt;  // (a tile per workgroup)
+  const dim3 grid = c.tile_grid(std::min(pnt, wgs));
+  const float xs = c.x_scale();
+  const float *gs = c.cs.column_scales();
+  // (both forms of the kernel body in one kernel: the device-side mode word picks; without a probe the wide form)
+  dispatch<0, 1>(ml.paired ? 1 : 0, [&](auto PAIRED) {
+    dispatch<1, 2, 3>(cp.nct, [&](auto NCT) {
+      dispatch<4, 8>(ml.pw == 4 ? 4 : 8, [&](auto NW) {
+        constexpr int nw = decltype(NW)::value;
+        hipLaunchKernelGGL((k_gain_mix_p2<decltype(NCT)::value, nw, decltype(PAIRED)::value != 0>), grid, dim3(64 * nw), 0, c.stream(), c.P, c.pl, xs, gs,
+                           w.level_cur, w.level_next, w.wide_cur, w.wide_next, c.standby_gate(), pnt);
+      });
+    });
+  });
+}
+
+static void launch_hinge(const MixCall &c) {
+  const CallWords &w = c.w;
+  const float xs = c.x_scale();
+  const float *gs = c.cs.column_scales();
+  dispatch<1, 2, 3>(c.cp.nct, [&](auto NCT) {
+    dispatch<4, 8>(c.ml.tile() == 256 ? 4 : 8, [&](auto NW) {
+      constexpr int nw = decltype(NW)::value;
+      hipLaunchKernelGGL((k_gain_mix_hg<decltype(NCT)::value, nw>), c.tile_grid(c.ml.ntiles), dim3(64 * nw), 0, c.stream(), c.P, c.hl, xs, gs, w.level_cur,
+                         w.level_next, w.wide_cur, w.wide_next, c.gate_word(false), c.gate_word(true));
+    });
+  });
+}
+
+// the parameter block of K1
+static GainMixParams mix_params(const MixCall &c, float *out_dev, size_t out_stride, size_t part_stride, unsigned *record) {
+  const float *in_dev = c.in_dev;
+  const size_t in_stride = c.in_stride;
+  const bool valu = c.ml.kind == GainKernel::Valu;
   GainMixParams P;
-  P.mode_word = gate;
-  P.record = gate ? record : nullptr;
-  P.sl = sl;
+  P.mode_word = c.w.gate;
+  P.record = c.w.gate ? record : nullptr;
+  P.sl = c.sl;
   P.in = in_dev;
   P.in_stride = in_stride;
   P.out = out_dev;
   P.out_stride = out_stride;
   P.part_stride = part_stride;
-  P.desc = desc;
-  P.ps = ps;
-  P.t_call = t_call;
-  P.nsamples = nsamples;
-  P.ntiles = ml.ntiles;
-  P.M = M;
-  P.ncols = cs.ncols();
-  P.ngroups = ml.mfma ? cp.mgroups : cp.ngroups;
-  P.wsplit = ml.wsplit;
-  P.tiles_per_wg = ml.mfma ? ml.tpw : 1;
-  P.vec_ok = (in_stride % 4 == 0 && out_stride % 4 == 0 && part_stride % 4 == 0 &&
-              ((uintptr_t)in_dev & 15) == 0 && ((uintptr_t)out_dev & 15) == 0)
-                 ? 1
-                 : 0;
-  const dim3 grid(ml.mfma ? (ml.ntiles + ml.tpw - 1) / ml.tpw : ml.ntiles, ml.gsplit,
-                  ml.mfma ? cp.mnz : cp.nz);
-  const dim3 block(64 * P.ngroups * P.tiles_per_wg * ml.wsplit);
-  const size_t lds = mix_lds_bytes(cp, ml);
-  if (ev) EARHIP_HIP(hipEventRecord(ev[2], ctx->stream));
-  bool launched = false;
-  if (ml.hinge) {
-    const dim3 bgrid(ml.ntiles, ml.gsplit, cp.mnz * cp.mgroups);
-    const float xs = std::ldexp(1.0f, ctx->x_scale_log2);
-    const float *gs = cs.column_scales();
-#define EARHIP_HG_LAUNCH(NCT_, NW_)                                                                                  \
-  hipLaunchKernelGGL((k_gain_mix_hg<NCT_, NW_>), bgrid, dim3(64 * NW_), 0, ctx->stream, P, hl, xs, gs, level_cur,     \
-                     level_next, wide_cur, wide_next, hg_robust ? nullptr : gate, hg_robust ? gate : nullptr);
-#define EARHIP_HG_CASE(NCT_)                                                                                          \
-  if (cp.nct == NCT_) {                                                                                               \
-    if (ml.tile() == 256) EARHIP_HG_LAUNCH(NCT_, 4)                                                                   \
-    else EARHIP_HG_LAUNCH(NCT_, 8)                                                                                    \
-  }
-    EARHIP_HG_CASE(1) EARHIP_HG_CASE(2) EARHIP_HG_CASE(3)
-#undef EARHIP_HG_CASE
-#undef EARHIP_HG_LAUNCH
-    launched = true;
-  }
-  if (ml.pieces || (ml.hinge && gate && !hg_robust)) {
-    // as many workgroups as are resident at once (a multiple of 8: a workgroup's tiles stay on its XCD), each carrying its
-    // pipeline from one tile's list into the next (gain_p2.h); option P2_WGS: that number (0: a workgroup per tile)
-    int wgs = std::max(8, (ctx->num_cus * (ml.pw == 4 ? 2 : 1) / std::max(1, ml.gsplit * cp.mnz * cp.mgroups)) & ~7);
-    if (ctx->has(OPT_P2_WGS)) wgs = ctx->get(OPT_P2_WGS) > 0 ? ctx->get(OPT_P2_WGS) : pnt;
-    if (!p2_persistent(cp.nct, ml.pw, ml.paired)) wgs = pnt;  // (a tile per workgroup)
-    const dim3 bgrid(std::min(pnt, wgs), ml.gsplit, cp.mnz * cp.mgroups);
-    const float xs = std::ldexp(1.0f, ctx->x_scale_log2);
-    const float *gs = cs.column_scales();
-    // (both forms of the kernel body in one kernel: the device-side mode word picks; without a probe the wide form)
-#define EARHIP_P2_LAUNCH(NCT_, NW_, PR_)                                                                             \
-  hipLaunchKernelGGL((k_gain_mix_p2<NCT_, NW_, PR_>), bgrid, dim3(64 * NW_), 0, ctx->stream, P, pl, xs, gs,         \
-                     level_cur, level_next, wide_cur, wide_next, ml.hinge ? gate : nullptr, pnt);
-#define EARHIP_P2_CASE(NCT_, PR_)                                                                                   \
-  if (cp.nct == NCT_ && ml.paired == PR_) {                                                                         \
-    if (ml.pw == 4) EARHIP_P2_LAUNCH(NCT_, 4, PR_)                                                                  \
-    else EARHIP_P2_LAUNCH(NCT_, 8, PR_)                                                                             \
-  }
-    EARHIP_P2_CASE(1, false) EARHIP_P2_CASE(2, false) EARHIP_P2_CASE(3, false)
-    EARHIP_P2_CASE(1, true) EARHIP_P2_CASE(2, true) EARHIP_P2_CASE(3, true)
-#undef EARHIP_P2_CASE
-#undef EARHIP_P2_LAUNCH
-    launched = true;
-  }
-  if (ml.f32grid) {  // exact f32 on the tile grid (gain_f32g.h): a workgroup per 512-sample tile, descriptors from k_seg_prep
-    if (nsamples % kF32GridTile != 0) fail_internal("f32 grid kernel: the call is not whole tiles");
-    const dim3 bgrid(ml.ntiles, ml.gsplit, cp.mnz * cp.mgroups);
-#define EARHIP_F32G_CASE(NCT_)                                                                       \
-  if (cp.nct == NCT_) hipLaunchKernelGGL((k_gain_mix_f32g<NCT_>), bgrid, dim3(512), 0, ctx->stream, P, ps.zero_row);
-    EARHIP_F32G_CASE(1) EARHIP_F32G_CASE(2) EARHIP_F32G_CASE(3)
-#undef EARHIP_F32G_CASE
-    launched = true;
-  }
-  if (ml.split) {
-    // as many workgroups as are resident at once (a multiple of 8: a workgroup's tiles stay on its XCD), each working
-    // through its share of the tiles in one software pipeline (gain_h2.h)
-    const int per_cu = ml.tile() == 512 ? 1 : (cp.nct == 1 ? 3 : 2);  // (the 8-wave forms: 154-243 registers, one workgroup per CU)
-    int wgs = std::max(8, (ctx->num_cus * per_cu / std::max(1, ml.gsplit * cp.mnz * cp.mgroups)) & ~7);
-    if (ctx->has(OPT_H2_WGS)) wgs = std::max(1, ctx->get(OPT_H2_WGS));  // tuning knob
-    wgs = std::max(wgs, ((ml.ntiles + 63) / 64 + 7) & ~7);  // (at most 64 tiles per workgroup: its redo mask)
-    // a workgroup's tiles as one contiguous run (option H2_RUNS: 1 on, 0 off; default: the single-column-tile forms — config 2)
-    P.tile_runs = ctx->has(OPT_H2_RUNS) ? (ctx->get(OPT_H2_RUNS) != 0) : 0;
-    if (!h2_persistent(cp.nct, ml.tile() == 512 ? 8 : 4)) wgs = ml.ntiles;  // (a tile per workgroup)
-    const dim3 bgrid(std::min(ml.ntiles, wgs), ml.gsplit, cp.mnz * cp.mgroups);
-    const float xs = std::ldexp(1.0f, ctx->x_scale_log2);
-    const float *gs = cs.column_scales();
-    // two forms of the kernel: the 8-wave kernel carries both and branches on the device-side mode word (round 6); the 4-wave
-    // kernels are launched as a pair, back to back: the form the word names runs, the other returns at once
-    // (gain_h2.h; the piece-list and hinge kernels carry both forms in one kernel — for this one the merged kernel measured
-    // slower: config 2 0.224 -> 0.259 ms, its 4-wave form loses a wave per SIMD to the larger of the two register counts);
-    // without a probe only the wide form
-    const bool two_launches = ctx->get(OPT_H2_PAIR, 0) != 0;  // (tuning knob: the 8-wave kernel as a pair of launches, as until round 6)
-#define EARHIP_H2_LAUNCH(NCT_, NW_, WIDE_)                                                                          \
-  hipLaunchKernelGGL((k_gain_mix_h2<NCT_, NW_, WIDE_>), bgrid, dim3(64 * NW_), 0, ctx->stream, P, ps.zero_row, xs,  \
-                     gs, level_cur, level_next, slow_cur, slow_next, wide_cur, wide_next);
-#define EARHIP_H2T1_LAUNCH(NCT_, NW_, WIDE_)                                                                        \
-  hipLaunchKernelGGL((k_gain_mix_h2_t1<NCT_, NW_, WIDE_>), bgrid, dim3(64 * NW_), 0, ctx->stream, P, ps.zero_row, xs, \
-                     gs, level_cur, level_next, slow_cur, slow_next, wide_cur, wide_next);
-#define EARHIP_H2_CASE(NCT_)                                                                                        \
-  if (cp.nct == NCT_) {                                                                                             \
-    if (ml.tile() == 512) {                                                                                         \
-      if (wide_cur && !two_launches) EARHIP_H2_LAUNCH(NCT_, 8, 2)                                                   \
-      else {                                                                                                        \
-        if (wide_cur) EARHIP_H2_LAUNCH(NCT_, 8, 0)                                                                  \
-        EARHIP_H2_LAUNCH(NCT_, 8, 1)                                                                                \
-      }                                                                                                             \
-    } else if (NCT_ == 1) {                                                                                         \
-      if (wide_cur) EARHIP_H2_LAUNCH(1, 4, 0)                                                                       \
-      EARHIP_H2_LAUNCH(1, 4, 1)                                                                                     \
-    } else {                                                                                                        \
-      if (wide_cur) EARHIP_H2T1_LAUNCH(NCT_, 4, false)                                                              \
-      EARHIP_H2T1_LAUNCH(NCT_, 4, true)                                                                             \
-    }                                                                                                               \
-  }
-    EARHIP_H2_CASE(1) EARHIP_H2_CASE(2) EARHIP_H2_CASE(3)
-#undef EARHIP_H2_CASE
-#undef EARHIP_H2_LAUNCH
-#undef EARHIP_H2T1_LAUNCH
-    launched = true;
-  }
-#define EARHIP_MIX_CASE(NOUT_, SPL_, STRICT_)                                   \
-  if (cp.nout == NOUT_ && ml.spl == SPL_ && strict == STRICT_) {                 \
-    launch_mix_t<NOUT_, SPL_, STRICT_>(P, grid, block, lds, ctx->stream);        \
-    launched = true;                                                             \
-  }
-#define EARHIP_MFMA_CASE(NCT_, NRT_)                                            \
-  if (slots && cp.nct == NCT_ && ml.nrt == NRT_) {                                          \
-    launch_mfma_t<NCT_, NRT_>(P, grid, block, lds, ctx->stream);                 \
-    launched = true;                                                             \
-  }
-  EARHIP_MFMA_CASE(1, 8) EARHIP_MFMA_CASE(2, 8) EARHIP_MFMA_CASE(3, 8)
-  EARHIP_MFMA_CASE(1, 4) EARHIP_MFMA_CASE(2, 4) EARHIP_MFMA_CASE(3, 4)
-#undef EARHIP_MFMA_CASE
-  if (!ml.mfma && !launched) {
-  EARHIP_MIX_CASE(8, 4, false) EARHIP_MIX_CASE(8, 4, true)
-  EARHIP_MIX_CASE(16, 4, false) EARHIP_MIX_CASE(16, 4, true)
-  EARHIP_MIX_CASE(24, 4, false) EARHIP_MIX_CASE(24, 4, true)
-  EARHIP_MIX_CASE(8, 2, false) EARHIP_MIX_CASE(8, 2, true)
-  EARHIP_MIX_CASE(16, 2, false) EARHIP_MIX_CASE(16, 2, true)
-  EARHIP_MIX_CASE(24, 2, false) EARHIP_MIX_CASE(24, 2, true)
-  }
-#undef EARHIP_MIX_CASE
-  if (!launched) fail_internal("no gain_mix instantiation for this column plan");
-  if (ev) EARHIP_HIP(hipEventRecord(ev[3], ctx->stream));
-  EARHIP_HIP(hipGetLastError());
+  P.desc = c.scratch;
+  P.ps = c.ps;
+  P.t_call = c.t_call;
+  P.nsamples = c.nsamples;
+  P.ntiles = c.ml.ntiles;
+  P.M = c.M;
+  P.ncols = c.cs.ncols();
+  P.ngroups = valu ? c.cp.ngroups : c.cp.mgroups;
+  P.wsplit = c.ml.wsplit;
+  P.tiles_per_wg = valu ? 1 : c.ml.tpw;
+  P.vec_ok = in_stride % 4 == 0 && out_stride % 4 == 0 && part_stride % 4 == 0 && ((uintptr_t)in_dev & 15) == 0 && ((uintptr_t)out_dev & 15) == 0;
+  return P;
 }
 
-// What the split-operand kernels of a call of up to `max_samples` samples on M objects keep PER CONTEXT — the level and mode
-// words, the per-object levels of the probe, the per-tile "exact path" words of the grid kernel (tiles of 256 samples at the
-// smallest) — made where a renderer is created, so that no process call allocates or synchronises for them.
-void reserve_call_words(earhip_ctx *ctx, int M, size_t max_samples) {
-  if (!ctx->level.p) ctx->level.alloc_zero(4, ctx->stream);
-  const size_t ntiles = (max_samples + 255) / 256;
-  const bool grow_obj = ctx->obj_level_cap < M, grow_tiles = ctx->tile_slow_cap < ntiles;
-  if (grow_obj || grow_tiles) EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (calls of other stages may be using the old ones)
-  if (grow_obj) {
-    ctx->obj_level_cap = M + M / 2 + 64;
-    ctx->obj_level.alloc_zero(2 * (size_t)ctx->obj_level_cap, ctx->stream);
+// K0 (the probe, then what the kind's K1 reads: descriptors or lists, in the call's scratch buffer) + K1
+MixResult launch_gain_mix(earhip_ctx *ctx, const CurveSet &cs, const MixLaunch &ml, bool strict, int64_t t_call, int nsamples,
+                          const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride, size_t part_stride, SegDesc *desc,
+                          unsigned *record, hipEvent_t *ev) {
+  const GainKernel kind = ml.kind;
+  MixCall c{ctx, cs, ml, cs.plan(), cs.device(), cs.M(), nsamples, t_call, in_dev, in_stride, desc, scratch_layout(cs, ml, cs.M(), nsamples)};
+  if (kind == GainKernel::Slots) c.sl = c.lay.slot_lists(desc);
+  if (kind == GainKernel::Pieces || kind == GainKernel::Hinge) c.pl = c.lay.piece_lists(desc, ml.paired);
+  if (kind == GainKernel::Hinge) c.hl = c.lay.hinge_lists(desc);
+  if (kind == GainKernel::Slots && c.M > kMaxSlotObjects) fail_internal("slot lists address objects with 16 bits");
+  if (ev) EARHIP_HIP(hipEventRecord(ev[0], ctx->stream));
+  c.w = acquire_call_words(ctx, ml, c.M, in_dev, in_stride, nsamples);
+  c.hg_robust = kind == GainKernel::Hinge && ctx->get(OPT_HG_ROBUST, 1) != 0;
+  c.standby = kind == GainKernel::Hinge && c.w.gate && !c.hg_robust;
+  switch (kind) {
+    case GainKernel::Hinge:
+      prep_hinge_lists(c);
+      if (c.standby) prep_piece_lists(c);
+      break;
+    case GainKernel::Pieces: prep_piece_lists(c); break;
+    case GainKernel::Slots: {
+      // short curves (static or nearly static gains, <= 8 points per object on average): K0s finds the segments itself and the
+      // descriptor pass is skipped; with long curves the 16-lanes-per-object search of k_seg_prep is the faster one (measured both ways)
+      const bool own_search = (size_t)c.ps.npoints <= (size_t)8 * c.M;
+      if (!own_search) prep_descriptors(c);
+      prep_slot_lists(c, own_search);
+      break;
+    }
+    default: prep_descriptors(c); break;
   }
-  if (grow_tiles) {
-    ctx->tile_slow_cap = std::max<size_t>(ntiles + ntiles / 4, 1024);
-    ctx->tile_slow.alloc_zero(2 * ctx->tile_slow_cap, ctx->stream);
-    ctx->tile_slow_idx = 0;
+  if (ev) EARHIP_HIP(hipEventRecord(ev[1], ctx->stream));
+  c.P = mix_params(c, out_dev, out_stride, part_stride, record);
+  if (ev) EARHIP_HIP(hipEventRecord(ev[2], ctx->stream));
+  switch (kind) {
+    case GainKernel::Valu: launch_valu(c, strict); break;
+    case GainKernel::Slots: launch_slots(c); break;
+    case GainKernel::F32Grid: launch_f32grid(c); break;
+    case GainKernel::Grid: launch_grid(c); break;
+    case GainKernel::Pieces: launch_pieces(c); break;
+    case GainKernel::Hinge:
+      launch_hinge(c);
+      if (c.standby) launch_pieces(c);
+      break;
   }
+  if (ev) EARHIP_HIP(hipEventRecord(ev[3], ctx->stream));
+  EARHIP_HIP(hipGetLastError());
+  MixResult res;
+  res.gated = kind == GainKernel::Hinge && c.w.gate;
+  res.device_form = c.w.wide_cur != nullptr;
+  res.hinge_robust = res.gated && c.hg_robust;
+  res.grew = c.w.grew;
+  return res;
 }
 
 // k_hinge_build keeps up to 128 KB of dynamic LDS per workgroup: the limit is an attribute of the function ON A DEVICE, so
@@ -425,12 +485,10 @@ size_t hinge_build_allow_lds(const hipDeviceProp_t &prop) {
   size_t ask = std::min(want, device_max > 4096 ? device_max - 4096 : dflt);  // (the kernel's static arrays: ~3 KB)
   if (ask <= dflt) return dflt;
   bool ok = true;
-#define EARHIP_HBUILD_ATTR(T_, NW_)                                                                       \
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hinge_build<T_, NW_>),                 \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ask) == hipSuccess;
-  EARHIP_HBUILD_ATTR(1, 4) EARHIP_HBUILD_ATTR(2, 4) EARHIP_HBUILD_ATTR(4, 4) EARHIP_HBUILD_ATTR(8, 4)
-  EARHIP_HBUILD_ATTR(1, 8) EARHIP_HBUILD_ATTR(2, 8) EARHIP_HBUILD_ATTR(4, 8) EARHIP_HBUILD_ATTR(8, 8)
-#undef EARHIP_HBUILD_ATTR
+  for_each_hinge_build([&](auto T, auto NW) {
+    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hinge_build<decltype(T)::value, decltype(NW)::value>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)ask) == hipSuccess;
+  });
   if (!ok) (void)hipGetLastError();  // (refused: the default limit stands)
   return ok ? ask : dflt;
 }
@@ -457,26 +515,13 @@ struct GainStage {
     // segment descriptors express such a curve (describe_segment's policy mode); the matrix-core kernels' list builders
     // computed something else outside [start, end) for 32 inputs and more.
     const bool strict = ctx->strict || n_in == 1 || force_ramp;
-    MixLaunch ml = plan_mix(ctx, curves.plan(), n_in, nsamples, strict, 32,
-                            curves.aligned_tile(t_call), curves.ramp_share(), curves.gain_scale(), curves.point_density_all(),
-                            curves.pair_waste(256), curves.pair_waste(512), curves.hinge_exact_share(in_stride, (size_t)nsamples), false,
-                            curves.deltas_per_pair(256));
-    if (ml.hinge) curves.ensure_kinks(ctx);
+    const MixLaunch ml = plan_mix(ctx, curves.plan(), n_in, nsamples, strict, 32, curves.stats(t_call, in_stride, (size_t)nsamples, false));
+    if (ml.kind == GainKernel::Hinge) curves.ensure_kinks(ctx);
     desc.reserve(scratch_units(curves, ml, n_in));
-    if (ml.gsplit == 1) {
-      launch_gain_mix(ctx, curves, ml, strict, t_call, nsamples, in_dev, in_stride, out_dev,
-                      out_stride, 0, desc.p, nullptr);
-    } else {
-      const size_t row_stride = ((size_t)nsamples + 3) & ~(size_t)3;
-      const size_t part_stride = row_stride * n_out;
-      parts.reserve(part_stride * ml.gsplit);
-      launch_gain_mix(ctx, curves, ml, strict, t_call, nsamples, in_dev, in_stride, parts.p,
-                      row_stride, part_stride, desc.p, nullptr);
-      hipLaunchKernelGGL(k_sum_parts, dim3((nsamples + 255) / 256, n_out), dim3(256), 0,
-                         ctx->stream, parts.p, part_stride, ml.gsplit, row_stride, n_out,
-                         nsamples, out_dev, out_stride);
-      EARHIP_HIP(hipGetLastError());
-    }
+    const size_t row_stride = ((size_t)nsamples + 3) & ~(size_t)3;
+    if (ml.gsplit > 1) parts.reserve(row_stride * n_out * ml.gsplit);
+    launch_gain_mix_summed(ctx, curves, ml, strict, t_call, nsamples, in_dev, in_stride, out_dev, out_stride, parts.p, row_stride, desc.p,
+                           nullptr, nullptr);
   }
 
   // host planar pointers, samples [r0, r1) of each channel

@@ -298,10 +298,7 @@ struct earhip_render {
   // the launch plan of a call of nblocks blocks at the current sample clock
   MixLaunch plan_call(size_t nblocks, size_t in_stride) {
     const int nsamples = (int)(nblocks * (size_t)B);
-    MixLaunch ml = plan_mix(ctx, curves->plan(), M, nsamples, ctx->strict, max_gsplit, curves->aligned_tile(t),
-                            curves->ramp_share(), curves->gain_scale(), curves->point_density_all(), curves->pair_waste(256), curves->pair_waste(512),
-                            curves->hinge_exact_share(in_stride, (size_t)nsamples), curves->tiles_aligned(kF32GridTile, t),
-                            curves->deltas_per_pair(256));
+    MixLaunch ml = plan_mix(ctx, curves->plan(), M, nsamples, ctx->strict, max_gsplit, curves->stats(t, in_stride, (size_t)nsamples, true));
     const size_t bus_stride = ((size_t)nsamples + 3) & ~(size_t)3;
     while (ml.gsplit > 1 && bus_stride * K * N * ml.gsplit > bus.n) ml.gsplit /= 2;
     return ml;
@@ -320,7 +317,7 @@ struct earhip_render {
     for (size_t nb : lens) {
       const MixLaunch ml = plan_call(nb, last_in_stride ? last_in_stride : nb * (size_t)B);
       need = std::max(need, scratch_units(*curves, ml, M));
-      hinge = hinge || ml.hinge;
+      hinge = hinge || ml.kind == GainKernel::Hinge;
     }
     if (hinge) curves->ensure_kinks(ctx);
     if (need > desc.n) {
@@ -332,7 +329,7 @@ struct earhip_render {
   // Workgroups of the gain kernel the chip holds at once for a plan: the tiles of a call are worked off in rounds of so many
   // (8-wave forms: one workgroup per CU; 4-wave forms: two)
   int resident_workgroups(const MixLaunch &ml) const {
-    if (!(ml.split || ml.pieces || ml.hinge)) return 0;
+    if (!ml.split_operands()) return 0;
     return ctx->num_cus * (ml.tile() >= 512 ? 1 : 2);
   }
 
@@ -445,9 +442,9 @@ struct earhip_render {
     }
     const bool strict = ctx->strict;
     MixLaunch ml = planned ? *planned : plan_call(nblocks, in_stride);
-    if (ml.hinge) curves->ensure_kinks(ctx);  // (already there unless an option changed the plan since the commit)
+    if (ml.kind == GainKernel::Hinge) curves->ensure_kinks(ctx);  // (already there unless an option changed the plan since the commit)
 
-    last_kind = ml.f32grid ? 2 : ml.hinge ? 5 : ml.pieces ? 4 : ml.split ? 3 : ml.mfma ? 1 : 0;
+    last_kind = (int)ml.kind;
     {
       // K0 / K1 scratch for THIS plan and THESE curves (round 3: 537 MB at the headline's size for any curves): reserved
       // when the curves were committed (reserve_for_curves).  The one exception, documented in earhip.h: a plan that no
@@ -466,7 +463,7 @@ struct earhip_render {
     // (the bus is sized for every plan plan_mix can make, earhip_render_create; should a tuning knob push a plan
     // beyond it, plan_call has taken fewer object splits, always a valid plan)
     if (part_stride * ml.gsplit > bus.n) fail_internal("bus buffer too small for this launch plan");
-    last_paired = (ml.pieces || ml.hinge) ? (ml.paired ? 1 : 0) : -1;
+    last_paired = (ml.kind == GainKernel::Pieces || ml.kind == GainKernel::Hinge) ? (ml.paired ? 1 : 0) : -1;
     last_plan[0] = ml.tile();
     last_plan[1] = ml.ntiles;
     last_plan[2] = ml.gsplit;
@@ -481,24 +478,14 @@ struct earhip_render {
       pd.continues = continues;
       evp = pd.e;
     }
-    const long lazy_before = ctx->lazy_allocs;
-    ctx->record_slot = rec.p + (continues ? 1 : 0);  // (consumed by the launch_gain_mix below)
+    unsigned *const record = rec.p + (continues ? 1 : 0);  // (where K1 leaves the call's mode word: this renderer's own slot)
+    MixResult mix;
     if (K == 1) {
       // direct bus only: K1 writes the output rows itself
-      if (ml.gsplit == 1) {
-        launch_gain_mix(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, out_dev,
-                        out_stride, 0, desc.p, evp);
-      } else {
-        launch_gain_mix(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, bus.p,
-                        bus_stride, part_stride, desc.p, evp);
-        hipLaunchKernelGGL(k_sum_parts, dim3((nsamples + 255) / 256, N), dim3(256), 0,
-                           ctx->stream, bus.p, part_stride, ml.gsplit, bus_stride, N, nsamples,
-                           out_dev, out_stride);
-        EARHIP_HIP(hipGetLastError());
-      }
+      mix = launch_gain_mix_summed(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, out_dev, out_stride, bus.p, bus_stride, desc.p,
+                                   record, evp);
     } else {
-      launch_gain_mix(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, bus.p,
-                      bus_stride, part_stride, desc.p, evp);
+      mix = launch_gain_mix(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, bus.p, bus_stride, part_stride, desc.p, record, evp);
       DecorParams P;
       P.bus = bus.p;
       P.bus_stride = bus_stride;
@@ -552,10 +539,8 @@ struct earhip_render {
       fresh = false;
     }
     if (timed) pending.push_back(pd);
-    last_gated = ctx->last_gate_idx >= 0;  // (set by launch_gain_mix for this call)
-    last_device_form = ctx->last_wide_idx >= 0;
-    last_hg_robust = last_gated && ctx->last_hinge_robust;
-    if (ctx->lazy_allocs != lazy_before) scratch_regrows++;  // (a buffer of the context no renderer had announced: earhip.h)
+    last_gated = mix.gated, last_device_form = mix.device_form, last_hg_robust = mix.hinge_robust;
+    if (mix.grew) scratch_regrows++;  // (a buffer of the context no renderer had announced: earhip.h)
     t += nsamples;
   }
 };

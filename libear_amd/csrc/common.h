@@ -161,11 +161,8 @@ struct earhip_ctx {
                      // when all curve points lie on tile boundaries, else f32 MFMA
   int x_scale_log2 = 14;  // f16x2 kernel: inputs are scaled by 2^x_scale_log2 before the split (gain_h2.h) ...
   bool x_scale_auto = true;  // ... unless a level estimate of the call's inputs is available (default: K0 probes them)
-  earhip::DevBuf<unsigned> level;  // [2] input level words (float bits), used alternately by successive calls
+  earhip::DevBuf<unsigned> level;  // [0..1] input level words (float bits), [2..3] mode words, each pair used alternately by successive calls
   int level_idx = 0;
-  int last_gate_idx = -1;  // the mode word ([2 + idx]) of the last call planned for the hinge kernel; -1: the last call was not
-  bool last_hinge_robust = false;  // ... and a call beyond the packed kink products' span runs the kernel's robust form (else: the piece lists standing by)
-  int last_wide_idx = -1;  // the mode word of the last call whose split-operand kernel picked its form on the device; -1: none (wide form)
   // [2][tile_slow_cap] words used alternately by successive calls of the f16x2 gain kernel: non-zero = some object
   // of the tile needs the kernel's exact path (set by K0: k_seg_prep, cleared for the call after next by K1)
   earhip::DevBuf<unsigned> tile_slow;
@@ -175,7 +172,6 @@ struct earhip_ctx {
                                        // smallest non-zero magnitude the level probe saw (k_level_probe: plain stores, no state between calls)
   int obj_level_cap = 0;
   long lazy_allocs = 0;  // process calls that had to make or grow one of the buffers above themselves (reserve_call_words did not cover them)
-  unsigned *record_slot = nullptr;  // where the NEXT launch_gain_mix leaves a copy of its call's mode word (a renderer's own slot; consumed by the launch)
   int max_waves = 4;  // waves per gain_mix workgroup (column groups x object splits)
   int tiles_per_wg = 4;  // MFMA kernel: adjacent tiles per workgroup (share gain rows through L1)
   bool tiles_per_wg_forced = false;  // (EARHIP_TPW: taken as given)

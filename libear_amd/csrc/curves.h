@@ -75,6 +75,20 @@ k_curve_upload(CurveImage src, CurveImage dst, const int32_t *changed, int row) 
   for (size_t i = threadIdx.x; i < gn / 4; i += 256) dg[i] = sg[i];
 }
 
+// What plan_mix looks at in a curve set for one call (CurveSet::stats).  The defaults: curves off every grid that ramp all the
+// time, gains no scale can bring into f16 range — never the paired lists, never the hinge kernel.
+struct CurveStats {
+  int aligned_tile = 0;            // largest tile (512, 256) of the split-operand kernels with no curve point strictly inside; 0: none
+  double ramp_share = 1.0;         // fraction of the curves' time in ramps
+  float gain_scale = 0.0f;         // power of two that brings the gains into f16 range; 0: none does
+  double point_density = 0.0;      // curve points per sample and object of the whole set
+  double pair_waste256 = 1.0;      // extra slots of the paired piece lists on 256-sample tiles ...
+  double pair_waste512 = 1.0;      // ... and on 512-sample tiles (CurveSet::pair_waste)
+  double hinge_exact_share = 2.0;  // share of (object, tile) pairs the hinge kernel would send through its exact path; > 1: not its curves
+  bool grid512_strict = false;     // EVERY curve point lies on the call's 512-sample tile grid
+  double deltas256 = 0.0;          // ramp pieces per (object, 256-sample tile) pair of the whole set
+};
+
 // The gain curves of M objects: libear's GainInterpolator::interp_points per object (gain_interpolator.hpp:42-43: a
 // public vector the caller changes freely), as a device image the kernels read and a host mirror of it.
 //
@@ -447,6 +461,22 @@ class CurveSet {
     return std::ldexp(1.0f, 14 - e);
   }
 
+  // what the planner looks at for a call of nsamples samples at t_call whose input rows lie in_stride floats apart
+  // (grid512: the caller takes the exact f32 grid kernel where the curves lie on the call's 512-sample grid)
+  CurveStats stats(int64_t t_call, size_t in_stride, size_t nsamples, bool grid512) const {
+    CurveStats s;
+    s.aligned_tile = aligned_tile(t_call);
+    s.ramp_share = ramp_share();
+    s.gain_scale = gain_scale();
+    s.point_density = point_density_all();
+    s.pair_waste256 = pair_waste(256);
+    s.pair_waste512 = pair_waste(512);
+    s.hinge_exact_share = hinge_exact_share(in_stride, nsamples);
+    s.grid512_strict = grid512 && tiles_aligned(kF32GridTile, t_call);
+    s.deltas256 = deltas_per_pair(256);
+    return s;
+  }
+
   // [row] per-column gain scales of the split-operand kernels (powers of two; device memory)
   const float *column_scales() const { return d_gcol_.p; }
 
@@ -699,50 +729,70 @@ class CurveSet {
   hipEvent_t staged_ = nullptr;
 };
 
-// How K1 is spread over the chip for one call.
-struct MixLaunch {
-  bool mfma;                   // matrix-core kernel (default) or VALU kernel (strict mode)
-  bool split = false;          // matrix-core kernel on f16x2 split operands (gain_h2.h); tile = 256 samples
-  bool wide = false;           // with split: 8 waves on 512-sample tiles
-  bool pieces = false;         // matrix-core kernel on f16x2 split operands over per-tile piece lists (gain_p2.h)
-  int pw = 2;                  // with pieces: waves per workgroup (2 or 4); tile = 64 pw samples
-  bool paired = false;         // with pieces: the lists' paired layout (gain_p2.h)
-  bool f32grid = false;        // exact-f32 matrix-core kernel for curves on the 512-sample tile grid (gain_f32g.h)
-  bool hinge = false;          // matrix-core kernel on f16x2 split operands with the curve points inside a tile as hinges (gain_hg.h)
-  int hinge_tile = 512;        // with hinge: 512 (8 waves, up to two kinks on either side of a tile's centre) or 256 (4 waves, one:
-                               // EARHIP_HG_TILE=256; 4 % slower per step, 8.1e-7 instead of 8.6e-7 from the CPU path on the
-                               // always-ramping scene at 1024 objects)
-  int spl;                     // VALU: samples per lane (2 or 4); tile = 64 * spl samples
-  int nrt;                     // MFMA: 16-sample row tiles per wave; tile = 16 * nrt samples
-  int ntiles, wsplit, gsplit;  // tiles, in-workgroup object splits, grid-level splits
-  int tpw = 1;                 // MFMA: adjacent tiles per workgroup
-  int tile() const { return f32grid ? kF32GridTile : hinge ? hinge_tile : pieces ? 64 * pw : split ? (wide ? 512 : 256) : mfma ? 16 * nrt : 64 * spl; }
+// The gain kernel of a call (the codes earhip_render_gain_kernel reports)
+enum class GainKernel : int {
+  Valu = 0,     // k_gain_mix: SGPR-operand FMAs, libear's own arithmetic in strict mode (gain_kernels.h)
+  Slots = 1,    // k_gain_mix_mfma: exact f32 on the matrix cores over per-tile slot lists (gain_mfma.h)
+  F32Grid = 2,  // k_gain_mix_f32g: exact f32 for curves on the 512-sample tile grid (gain_f32g.h)
+  Grid = 3,     // k_gain_mix_h2 / _h2_t1: f16x2 split operands, no curve point inside a tile (gain_h2.h, gain_h2_t1.h)
+  Pieces = 4,   // k_gain_mix_p2: f16x2 split operands over per-tile piece lists (gain_p2.h)
+  Hinge = 5     // k_gain_mix_hg: f16x2 split operands, the curve points inside a tile as hinges (gain_hg.h)
 };
 
-inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, int nsamples,
-                          bool strict, int max_gsplit, int aligned_tile = 0, double ramp_share = 1.0,
-                          float gain_scale = 0.0f, double point_density = 0.0, double pair_waste256 = 1.0,
-                          double pair_waste512 = 1.0, double hinge_exact_share = 2.0, bool grid512_strict = false,
-                          double deltas256 = 0.0) {
+// How K1 is spread over the chip for one call.
+struct MixLaunch {
+  GainKernel kind = GainKernel::Valu;
+  bool wide = false;           // Grid: 8 waves on 512-sample tiles (else 4 waves on 256)
+  int pw = 2;                  // Pieces: waves per workgroup (4 or 8); tile = 64 pw samples (Hinge: of the lists standing by)
+  bool paired = false;         // Pieces: the lists' paired layout (gain_p2.h)
+  int hinge_tile = 512;        // Hinge: 512 (8 waves, up to two kinks on either side of a tile's centre) or 256 (4 waves, one:
+                               // EARHIP_HG_TILE=256; 4 % slower per step, 8.1e-7 instead of 8.6e-7 from the CPU path on the
+                               // always-ramping scene at 1024 objects)
+  int spl;                     // Valu: samples per lane (2 or 4); tile = 64 * spl samples
+  int nrt;                     // Slots: 16-sample row tiles per wave; tile = 16 * nrt samples
+  int ntiles, wsplit, gsplit;  // tiles, in-workgroup object splits, grid-level splits
+  int tpw = 1;                 // Slots: adjacent tiles per workgroup
+  // the kernels on f16x2 split operands: level probe and mode words in front of them, a persistent grid of workgroups
+  bool split_operands() const { return kind == GainKernel::Grid || kind == GainKernel::Pieces || kind == GainKernel::Hinge; }
+  int tile() const {
+    switch (kind) {
+      case GainKernel::Valu: return 64 * spl;
+      case GainKernel::Slots: return 16 * nrt;
+      case GainKernel::F32Grid: return kF32GridTile;
+      case GainKernel::Grid: return wide ? 512 : 256;
+      case GainKernel::Pieces: return 64 * pw;
+      case GainKernel::Hinge: return hinge_tile;
+    }
+    return 0;
+  }
+};
+
+inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, int nsamples, bool strict, int max_gsplit,
+                          const CurveStats &st) {
+  const int aligned_tile = st.aligned_tile;
+  const double ramp_share = st.ramp_share, point_density = st.point_density, pair_waste256 = st.pair_waste256,
+               pair_waste512 = st.pair_waste512, hinge_exact_share = st.hinge_exact_share, deltas256 = st.deltas256;
+  const float gain_scale = st.gain_scale;
   const bool aligned = aligned_tile >= 256;  // no curve point inside 256- (512-) sample tiles of the call
   MixLaunch L;
-  L.mfma = !strict && ctx->use_mfma;
+  // matrix-core kernels (default) or the VALU kernel (strict mode)
+  const bool mfma = !strict && ctx->use_mfma;
   // Split-operand kernel (tile = 256 or 512 samples, no curve point inside a tile; 4 forces it where the
   // gains allow): f16x2 when the gains can be scaled into f16 range — its cost does not depend on the
   // curves and is below the f32 slot kernel's even for static gains.  Curve sets with non-finite gains
   // stay on the f32 slot kernel.
-  L.split = L.mfma && M >= 32 && gain_scale > 0.0f && ctx->use_mfma != 5 && ctx->use_mfma != 6 &&
-            (ctx->use_mfma == 4 || (ctx->use_mfma == 3 && aligned));
+  const bool split = mfma && M >= 32 && gain_scale > 0.0f && ctx->use_mfma != 5 && ctx->use_mfma != 6 &&
+                     (ctx->use_mfma == 4 || (ctx->use_mfma == 3 && aligned));
   // long calls on a 512 grid: 8-wave workgroups on 512-sample tiles (two rounds of workgroups or more:
   // 512 blocks of 512: K1 0.215 vs 0.236 ms; one round, 256 blocks: 0.127 vs 0.120)
   // (EARHIP_H2_TILE=256|512 forces one of them where the curves allow it: tests, tuning)
   const int forced = ctx->get(OPT_H2_TILE);
   // Piece-list kernel: everything else the f16x2 operands can represent — metadata that ignores the tile
   // grid costs its curve points, not a different kernel (5 forces it for aligned curves as well).
-  L.pieces = L.mfma && !L.split && M >= 32 && M <= kMaxPieceObjects && gain_scale > 0.0f &&
-             (ctx->use_mfma == 3 || ctx->use_mfma == 5 || ctx->use_mfma == 6);
-  if ((ctx->use_mfma == 5 || ctx->use_mfma == 6) && L.pieces) L.split = false;
-  if (L.pieces) {
+  bool pieces = mfma && !split && M >= 32 && M <= kMaxPieceObjects && gain_scale > 0.0f &&
+                (ctx->use_mfma == 3 || ctx->use_mfma == 5 || ctx->use_mfma == 6);
+  bool hinge = false;
+  if (pieces) {
     const int ptile = ctx->get(OPT_P2_TILE);
     // Layout of the lists: paired (an object's base and delta piece share one input request, and the objects without a
     // ramp in a tile skip the position factors) unless objects often have several ramps inside one tile — every ramp
@@ -780,10 +830,10 @@ inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, in
     // (its list builder keeps 16 bytes per object and tile in LDS: as many objects as this device's limit holds)
     const int hinge_max = (int)std::min((size_t)kMaxHingeCached, ctx->hinge_build_lds / 16);
     // (curves the paired lists take are theirs: faster there than here in every measured case)
-    L.hinge = M <= hinge_max && hinge_exact_share <= kHingeExact && ramp_share >= kHingeRamps && !(paired_by_rule && L.paired);
-    if (ctx->has(OPT_HINGE)) L.hinge = ctx->get(OPT_HINGE) != 0 && M <= hinge_max && hinge_exact_share <= 1.0;
-    if (ctx->use_mfma == 6) L.hinge = M <= hinge_max && hinge_exact_share <= 1.0;
-    if (ctx->use_mfma == 5) L.hinge = false;  // (5 forces the piece lists)
+    hinge = M <= hinge_max && hinge_exact_share <= kHingeExact && ramp_share >= kHingeRamps && !(paired_by_rule && L.paired);
+    if (ctx->has(OPT_HINGE)) hinge = ctx->get(OPT_HINGE) != 0 && M <= hinge_max && hinge_exact_share <= 1.0;
+    if (ctx->use_mfma == 6) hinge = M <= hinge_max && hinge_exact_share <= 1.0;
+    if (ctx->use_mfma == 5) hinge = false;  // (5 forces the piece lists)
     // Curves that ramp most of the time AND hold in between (ADM blocks whose interpolationLength is 50-80 % of their duration):
     // both kernels take them, and which is faster follows the curves — the hinge kernel pays per curve point, the packed lists per
     // ramp piece.  Fitted on 1024 objects x 24 channels over update periods of 240-1920 samples and ramp shares of 0.5-1
@@ -795,32 +845,38 @@ inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, in
     // one in 2: 0.694 / 0.679).  Within 3 %: the hinge kernel.  Only where nothing forces a kernel.
     // (three column tiles only: with one or two a kink set is one or two thirds of the MFMAs and the hinge kernel wins these
     // cases too — a bed with one fast mover in 8 on 5 / 10 channels: 0.414 / 0.443 ms per step against the lists' 0.489 / 0.505)
-    if (L.hinge && !ctx->has(OPT_HINGE) && ctx->use_mfma == 3 && cp.nct == 3 && deltas256 > 0.0 && point_density > 0.0) {
+    if (hinge && !ctx->has(OPT_HINGE) && ctx->use_mfma == 3 && cp.nct == 3 && deltas256 > 0.0 && point_density > 0.0) {
       const double hinge_est = 0.56 + 0.077 * (point_density * 512.0), lists_est = 0.151 + 0.238 * (1.0 + deltas256);
-      if (lists_est < 0.97 * hinge_est) L.hinge = false;
+      if (lists_est < 0.97 * hinge_est) hinge = false;
     }
-    if (L.hinge) {
+    if (hinge) {
       if (ctx->has(OPT_HG_TILE)) L.hinge_tile = ctx->get(OPT_HG_TILE) == 256 ? 256 : 512;  // tuning knob
       // (the piece lists stand by on 256-sample tiles of their own, packed: k_hinge_gate)
-      L.pieces = false, L.paired = false, L.pw = 4;
+      pieces = false, L.paired = false, L.pw = 4;
     }
   }
   // (rounds 3-5 kept one column tile — up to 16 output columns, BASELINE config 2 — on the 4-wave kernel: its 8-wave form was held to
   // 128 registers for two workgroups per CU and spilled inside the chunk loop: 0.296 ms against 0.261)
   // (round 6: the single-column-tile form too — its 8-wave kernel no longer spills (154 registers, one workgroup per CU): config 2
   // 0.2257 ms against 0.2283 / 0.2487 (the two buffer modes) over six fresh processes each, and never in the slow mode)
-  L.wide = L.split && aligned_tile >= 512 && forced != 256 && (forced == 512 || nsamples / 512 >= 2 * ctx->num_cus);
+  L.wide = split && aligned_tile >= 512 && forced != 256 && (forced == 512 || nsamples / 512 >= 2 * ctx->num_cus);
   // Exact f32 asked for (MFMA = 1) and EVERY curve point on the 512-sample tile grid of a call of whole tiles: the line form
   // of the ramp on the f32 matrix pipe, no per-sample arithmetic in front of it (gain_f32g.h).  Finite gains only (a
   // constant segment's row is used as it is, but a ramp through a non-finite gain is libear's own arithmetic's business).
-  L.f32grid = L.mfma && !L.split && !L.pieces && !L.hinge && ctx->use_mfma == 1 && grid512_strict && gain_scale > 0.0f &&
-              nsamples % kF32GridTile == 0 && M >= 16;
-  // the slot lists of the f32 MFMA kernel address objects with 16 bits
-  if (L.mfma && !L.split && !L.pieces && !L.hinge && !L.f32grid && M > kMaxSlotObjects) L.mfma = false;
+  const bool f32grid = mfma && !split && !pieces && !hinge && ctx->use_mfma == 1 && st.grid512_strict && gain_scale > 0.0f &&
+                       nsamples % kF32GridTile == 0 && M >= 16;
+  // (the slot lists of the f32 MFMA kernel address objects with 16 bits: beyond that the VALU kernel)
+  L.kind = !mfma     ? GainKernel::Valu
+           : split   ? GainKernel::Grid
+           : pieces  ? GainKernel::Pieces
+           : hinge   ? GainKernel::Hinge
+           : f32grid ? GainKernel::F32Grid
+                     : (M > kMaxSlotObjects ? GainKernel::Valu : GainKernel::Slots);
+  const bool slots = L.kind == GainKernel::Slots;
   L.spl = ctx->spl;
   L.nrt = ctx->nrt;
   L.ntiles = (nsamples + L.tile() - 1) / L.tile();
-  if (L.split || L.pieces || L.hinge || L.f32grid) {
+  if (L.split_operands() || L.kind == GainKernel::F32Grid) {
     // one workgroup = 4 adjacent 64-sample tiles x all objects of its grid-level
     // split; few tiles (block mode): split the objects across workgroups
     L.wsplit = 1;
@@ -837,20 +893,20 @@ inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, in
     return L;
   }
   // 8 waves per workgroup: what the column groups leave goes to object splits
-  const int groups = L.mfma ? cp.mgroups : cp.ngroups;
-  if (L.mfma) L.tpw = std::max(1, std::min(std::min(ctx->tiles_per_wg, L.ntiles), ctx->max_waves / groups));
+  const int groups = slots ? cp.mgroups : cp.ngroups;
+  if (slots) L.tpw = std::max(1, std::min(std::min(ctx->tiles_per_wg, L.ntiles), ctx->max_waves / groups));
   // The exact f32 kernel adds every term to its running total in its own rounding step (an MFMA of k = 4 is four fused
   // multiply-adds in a row): with many objects the waves of a workgroup split the slot list rather than taking adjacent
   // tiles, so that no wave's chain is longer than ~256 terms (1024 ramping objects, one wave: 8.5e-7 from a float64 render
   // and 1.06e-6 from the CPU path; eight waves: 4.6e-7 and 7.9e-7, for 3 % of that kernel's time)
-  if (L.mfma && !ctx->tiles_per_wg_forced) L.tpw = std::max(1, std::min(L.tpw, (ctx->max_waves / groups) / std::max(1, (M + 127) / 128)));
+  if (slots && !ctx->tiles_per_wg_forced) L.tpw = std::max(1, std::min(L.tpw, (ctx->max_waves / groups) / std::max(1, (M + 127) / 128)));
   L.wsplit = std::max(1, std::min(std::max(1, ctx->max_waves / (groups * L.tpw)), std::max(1, M / 8)));
   // few tiles (block mode): split the objects across workgroups as well until
   // the grid covers the chip about twice over
   const int per_wg = std::max(1, M / L.wsplit);
   int g = 1;
   const int want = 2 * ctx->num_cus;
-  while (g < max_gsplit && (L.ntiles / L.tpw) * (L.mfma ? cp.mnz : cp.nz) * g < want && per_wg / (g * 2) >= 8) g *= 2;
+  while (g < max_gsplit && (L.ntiles / L.tpw) * (slots ? cp.mnz : cp.nz) * g < want && per_wg / (g * 2) >= 8) g *= 2;
   L.gsplit = g;
   return L;
 }
@@ -867,29 +923,126 @@ inline size_t bus_samples_bound(const earhip_ctx *ctx, size_t max_samples, int m
   return std::max(pad, std::min(pad * (size_t)max_gsplit, split));
 }
 
-size_t mix_lds_bytes(const ColumnPlan &cp, const MixLaunch &ml);
 void reserve_call_words(earhip_ctx *ctx, int M, size_t max_samples);  // api_core.hip
 
-// 16-byte units of the scratch buffer launch_gain_mix needs for a plan: descriptors (grid kernel, VALU kernel), + slot lists
-// (f32 kernel), piece lists sized from the curves, hinge lists (+ the piece lists standing by for them)
-inline size_t scratch_units(const CurveSet &cs, const MixLaunch &ml, int M) {
-  const size_t nt = (size_t)ml.ntiles;
-  // (the piece lists that stand by behind the hinge kernel: tiles of 64 pw samples, at most tile / (64 pw) times as many)
-  // (+ M x tiles units behind the lists: the staging matrix of the two-kernel builders, 16 bytes per (object, tile) pair)
-  if (ml.hinge) {
-    const size_t pnt = nt * (size_t)std::max(1, ml.tile() / (64 * ml.pw));
-    return std::max(hinge_units((size_t)M, nt) + (size_t)M * nt,
-                    piece_units((size_t)M, pnt, (size_t)cs.piece_cap(64 * ml.pw, ml.paired)) + (size_t)M * pnt);
+// The scratch buffer of one call (K0 writes it, K1 reads it), in 16-byte units from its start.  What a kind does not have is an
+// empty region.
+//   Valu, F32Grid, Grid:  desc
+//   Slots:                desc | slots
+//   Pieces:               pieces | piece_stage
+//   Hinge:                hinge | hinge_stage, and over the same memory pieces | piece_stage of the lists standing by: a call is
+//                         the hinge lists' or theirs (k_hinge_gate decides on the device, every builder looks at its word), so
+//                         the buffer holds the larger of the two
+struct ScratchLayout {
+  struct Region {
+    size_t at = 0, units = 0;
+  };
+  Region desc;         // SegDesc [ntiles][M] (k_seg_prep), and a spare unit
+  Region slots;        // Slot [ntiles][kTileSlots M], counts [ntiles][4], overflow words [ntiles][M] (k_slot_list)
+  Region pieces;       // Piece [tiles][piece_slots], counts [tiles][8], overflow words [tiles][M] (k_piece_build)
+  Region piece_stage;  // PairRec [M][tiles]: the staging matrix of the two-kernel builder (k_piece_classify)
+  Region hinge;        // LinEntry, HingeEntry [ntiles][cap], chunk flags, counts [ntiles][4], overflow words [ntiles][M] (k_hinge_build)
+  Region hinge_stage;  // HingeCached [M][ntiles] (k_hinge_classify)
+  size_t total = 0;
+  int M = 0, ntiles = 0, piece_tiles = 0, piece_slots = 0;
+
+  SlotLists slot_lists(SegDesc *base) const {
+    SlotLists sl;
+    sl.slots = reinterpret_cast<Slot *>(base + slots.at);
+    sl.count = reinterpret_cast<int *>(sl.slots + (size_t)kTileSlots * M * ntiles);
+    sl.ovf = sl.count + (size_t)4 * ntiles;
+    sl.M = M;
+    return sl;
   }
-  if (ml.pieces) return piece_units((size_t)M, nt, (size_t)cs.piece_cap(ml.tile(), ml.paired)) + (size_t)M * nt;
-  if (ml.split || ml.f32grid || !ml.mfma) return (size_t)M * nt + 1;
-  return desc_units((size_t)M, nt);
+  PieceLists piece_lists(SegDesc *base, bool paired) const {
+    PieceLists pl;
+    pl.pieces = reinterpret_cast<Piece *>(base + pieces.at);
+    pl.M = M;
+    pl.paired = paired ? 1 : 0;
+    pl.slots = piece_slots;
+    pl.count = reinterpret_cast<int *>(pl.pieces + (size_t)pl.cap() * piece_tiles);
+    pl.ovf = pl.count + (size_t)8 * piece_tiles;
+    return pl;
+  }
+  PairRec *piece_staging(SegDesc *base) const { return reinterpret_cast<PairRec *>(base + piece_stage.at); }
+  HingeLists hinge_lists(SegDesc *base) const { return earhip::hinge_lists(base + hinge.at, M, ntiles); }
+  HingeCached *hinge_staging(SegDesc *base) const { return reinterpret_cast<HingeCached *>(base + hinge_stage.at); }
+};
+static_assert(sizeof(Slot) == 16 && sizeof(Piece) == 16 && sizeof(PairRec) == 16 && sizeof(HingeCached) == 16 && sizeof(SegDesc) == 16,
+              "the scratch buffer is laid out in 16-byte units");
+
+// piece_tiles, piece_slots: tiles and slots per tile of the piece lists (Pieces: the call's own tiles; Hinge: those of the lists
+// standing by, which keep tiles of their own); plain numbers, no curve set: a host test runs it
+inline ScratchLayout scratch_layout(GainKernel kind, size_t M, size_t ntiles, size_t piece_tiles, size_t piece_slots) {
+  ScratchLayout L;
+  L.M = (int)M, L.ntiles = (int)ntiles, L.piece_tiles = (int)piece_tiles, L.piece_slots = (int)piece_slots;
+  auto behind = [](const ScratchLayout::Region &r, size_t units) { return ScratchLayout::Region{r.at + r.units, units}; };
+  switch (kind) {
+    case GainKernel::Valu:
+    case GainKernel::F32Grid:
+    case GainKernel::Grid:
+      L.desc = {0, M * ntiles + 1};
+      L.total = L.desc.units;
+      break;
+    case GainKernel::Slots:
+      L.desc = {0, M * ntiles};
+      L.slots = behind(L.desc, desc_units(M, ntiles) - M * ntiles);
+      L.total = L.slots.at + L.slots.units;
+      break;
+    case GainKernel::Hinge:
+      L.hinge = {0, hinge_units(M, ntiles)};
+      L.hinge_stage = behind(L.hinge, M * ntiles);
+      [[fallthrough]];
+    case GainKernel::Pieces:
+      L.pieces = {0, piece_units(M, piece_tiles, piece_slots)};
+      L.piece_stage = behind(L.pieces, M * piece_tiles);
+      L.total = std::max(L.hinge_stage.at + L.hinge_stage.units, L.piece_stage.at + L.piece_stage.units);
+      break;
+  }
+  return L;
 }
 
+// the layout of a plan on a curve set: the piece lists are sized from the curves (CurveSet::piece_cap)
+// (nsamples: of the call, for the lists' own tile count; 0: the most a call of ml.ntiles tiles can have — what a buffer is sized for)
+inline ScratchLayout scratch_layout(const CurveSet &cs, const MixLaunch &ml, int M, int nsamples = 0) {
+  // (the piece lists that stand by behind the hinge kernel: tiles of 64 pw samples, up to tile / (64 pw) times as many)
+  const int ptile = 64 * ml.pw;
+  const size_t ptiles = nsamples > 0 ? (size_t)(nsamples + ptile - 1) / ptile
+                                     : (size_t)ml.ntiles * (ml.kind == GainKernel::Hinge ? (size_t)std::max(1, ml.tile() / ptile) : 1);
+  const bool lists = ml.kind == GainKernel::Pieces || ml.kind == GainKernel::Hinge;
+  return scratch_layout(ml.kind, (size_t)M, (size_t)ml.ntiles, lists ? ptiles : 0, lists ? (size_t)cs.piece_cap(ptile, ml.paired) : 0);
+}
+// 16-byte units of the scratch buffer launch_gain_mix needs for a plan
+inline size_t scratch_units(const CurveSet &cs, const MixLaunch &ml, int M) { return scratch_layout(cs, ml, M).total; }
+
+// What a call turned out to be (the renderer's queries)
+struct MixResult {
+  bool gated = false;         // Hinge behind a probe: k_hinge_gate decides on the device whose call it is (the call's mode word says)
+  bool device_form = false;   // the split-operand kernel picks its form (wide / plain) on the device; else: the wide form
+  bool hinge_robust = false;  // gated, and a call beyond the packed kink products' span runs the kernel's robust form (else: the stand-by lists)
+  bool grew = false;          // a buffer of the context had to be made or grown (reserve_call_words had not covered the call)
+};
+
 // Enqueue K0 + K1.  out: [gsplit][ncols][out_stride] (part_stride floats apart)
-void launch_gain_mix(earhip_ctx *ctx, const CurveSet &cs, const MixLaunch &ml, bool strict,
-                     int64_t t_call, int nsamples, const float *in_dev, size_t in_stride,
-                     float *out_dev, size_t out_stride, size_t part_stride, SegDesc *desc,
-                     hipEvent_t *ev /* optional [4]: prep begin/end, mix begin/end */);
+// record: where the kernel leaves a copy of the call's mode word (a renderer's own slot; may be null)
+MixResult launch_gain_mix(earhip_ctx *ctx, const CurveSet &cs, const MixLaunch &ml, bool strict,
+                          int64_t t_call, int nsamples, const float *in_dev, size_t in_stride,
+                          float *out_dev, size_t out_stride, size_t part_stride, SegDesc *desc, unsigned *record,
+                          hipEvent_t *ev /* optional [4]: prep begin/end, mix begin/end */);
+
+// K0 + K1 with the grid-level object splits summed: straight into out_dev when the plan has none, else partial slabs in `parts`
+// ([gsplit][ncols][row_stride]) and k_sum_parts behind them
+inline MixResult launch_gain_mix_summed(earhip_ctx *ctx, const CurveSet &cs, const MixLaunch &ml, bool strict, int64_t t_call, int nsamples,
+                                        const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride, float *parts,
+                                        size_t row_stride, SegDesc *desc, unsigned *record, hipEvent_t *ev) {
+  if (ml.gsplit == 1) return launch_gain_mix(ctx, cs, ml, strict, t_call, nsamples, in_dev, in_stride, out_dev, out_stride, 0, desc, record, ev);
+  const int ncols = cs.ncols();
+  const size_t part_stride = row_stride * ncols;
+  const MixResult res = launch_gain_mix(ctx, cs, ml, strict, t_call, nsamples, in_dev, in_stride, parts, row_stride, part_stride, desc, record, ev);
+  hipLaunchKernelGGL(k_sum_parts, dim3((nsamples + 255) / 256, ncols), dim3(256), 0, ctx->stream, parts, part_stride, ml.gsplit, row_stride,
+                     ncols, nsamples, out_dev, out_stride);
+  EARHIP_HIP(hipGetLastError());
+  return res;
+}
 
 }  // namespace earhip

@@ -32,7 +32,9 @@ int main() {
                         const int ns = nb * B;
                         for (int aligned : {0, 256, 512}) {
                           for (bool strict : {false, true}) {
-                            const MixLaunch ml = plan_mix(&ctx, cp, M, ns, strict, max_gsplit, aligned, 1.0, 1.0f);
+                            CurveStats st;  // (curves that ramp all the time: never the paired lists, never the hinge kernel)
+                            st.aligned_tile = aligned, st.gain_scale = 1.0f;
+                            const MixLaunch ml = plan_mix(&ctx, cp, M, ns, strict, max_gsplit, st);
                             const size_t need = (((size_t)ns + 3) & ~(size_t)3) * ml.gsplit;
                             plans++;
                             if (need > cap || ml.gsplit < 1 || ml.gsplit > max_gsplit) {

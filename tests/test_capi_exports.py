@@ -130,6 +130,18 @@ def test_launch_plans_fit_the_bus_buffer_on_cpu(tmp_path):
     assert res.returncode == 0, res.stdout
 
 
+def test_launch_plan_table_and_scratch_layout_on_cpu(tmp_path):
+    """libear_amd/csrc/curves.h: the plans plan_mix makes for a fixed list of cases are those of tests/golden/plan_table.txt (every
+    kernel kind, layout, tile and option; written before the kernel kind replaced the planner's flags), and the regions of the
+    scratch buffer lie in order, without overlap, and end at the total scratch_units returns (host code, hipcc)"""
+    exe = tmp_path / "test_plan_table"
+    src = os.path.join(ROOT, "tests", "cpp", "test_plan_table.cpp")
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-I",
+                    os.path.join(ROOT, "libear_amd", "csrc"), src, "-o", str(exe)], check=True)
+    res = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "plan_table.txt")], stdout=subprocess.PIPE, text=True)
+    assert res.returncode == 0, res.stdout
+
+
 def test_the_environment_is_read_once_at_context_creation():
     """SURVEY 5 / include/earhip.h (earhip_ctx_set_option): tuning knobs are options of the context; the only getenv of
     the library is the loop in earhip_ctx_create — nothing on a process call's path reads the environment."""
