@@ -3,63 +3,63 @@
 // BlockConvolver (filter queue, spectra queues, "is all zero" flags —
 // src/dsp/block_convolver_impl.{hpp,cpp}); the arithmetic runs in the kernels of
 // fft_kernels.h on device-resident queues.
+#include <cmath>
 #include <cstring>
 #include <memory>
 
 #include "common.h"
 #include "fft_kernels.h"
+#include "fft_launch.h"
 
 namespace earhip {
-std::vector<cf> make_twiddles(int L);
-void launch_spectrum(int L, const float *in, size_t stride, int n_valid, const cf *tw, cf *out,
-                     int rows, hipStream_t s);
-
-template <int L>
-static void ifft_real_t(const cf *in, const cf *tw, float *out, int rows, hipStream_t s) {
-  hipLaunchKernelGGL((k_ifft_real<L>), dim3(rows), dim3(kFftThreads), 0, s, in, tw, out);
-}
-template <int L>
-static void conv_forward_t(const float *x, int fade, const cf *tw, cf *Xo, cf *Xn, hipStream_t s) {
-  hipLaunchKernelGGL((k_conv_forward<L>), dim3(1), dim3(kFftThreads), 0, s, x, fade, tw, Xo, Xn);
-}
-template <int L>
-static void conv_ifft_ola_t(const cf *Y, const cf *tw, float *tail, int use_tail, int mode,
-                            float *out, hipStream_t s) {
-  hipLaunchKernelGGL((k_conv_ifft_ola<L>), dim3(1), dim3(kFftThreads), 0, s, Y, tw, tail, use_tail,
-                     mode, out);
-}
-
-// CALL(L) for the power-of-two sizes with their own instantiation, CALL_RT for every other size
-#define EARHIP_DISPATCH_L(L, CALL, CALL_RT)                                     \
-  switch (L) {                                                                  \
-    case 64: CALL(64); break;                                                   \
-    case 128: CALL(128); break;                                                 \
-    case 256: CALL(256); break;                                                 \
-    case 512: CALL(512); break;                                                 \
-    case 1024: CALL(1024); break;                                               \
-    case 2048: CALL(2048); break;                                               \
-    case 4096: CALL(4096); break;                                               \
-    case 8192: CALL(8192); break;                                               \
-    default: CALL_RT; break;                                                    \
+std::vector<cf> make_twiddles(int L) {
+  std::vector<cf> tw(L);
+  const double pi = 3.14159265358979323846264338327950288;
+  for (int t = 0; t < L; t++) {
+    const double a = -2.0 * pi * (double)t / (double)L;
+    tw[t] = cf_make((float)std::cos(a), (float)std::sin(a));
   }
+  return tw;
+}
+void upload_twiddles(DevBuf<cf> &tw, int L) {
+  const std::vector<cf> host = make_twiddles(L);
+  tw.alloc(host.size());
+  EARHIP_HIP(hipMemcpy(tw.p, host.data(), sizeof(cf) * host.size(), hipMemcpyHostToDevice));
+}
 
-static FftShape shape_of(int L) {
-  FftShape S;
-  if (!fft_make_shape(L, &S)) fail_invalid("FFT size must be in [4, 8192]");
-  return S;
+// Every launcher: the size's own instantiation (the powers of two from 64), any other size mixed radix at run time.
+void launch_spectrum(int L, const float *in, size_t stride, int n_valid, const cf *tw, cf *out, int rows, hipStream_t s) {
+  fft_size_switch<64>(
+      L, [&](auto LL) { hipLaunchKernelGGL((k_spectrum_real<decltype(LL)::value>), dim3(rows), dim3(kFftThreads), 0, s, in, stride, n_valid, tw, out); },
+      [&] {
+        hipLaunchKernelGGL(k_spectrum_real_rt, dim3(rows), dim3(kFftThreads), fft_rt_lds(k_spectrum_real_rt, L), s, shape_of(L), in, stride,
+                           n_valid, tw, out);
+      });
+  EARHIP_HIP(hipGetLastError());
 }
-static void ifft_real_rt(int L, const cf *in, const cf *tw, float *out, int rows, hipStream_t s) {
-  hipLaunchKernelGGL(k_ifft_real_rt, dim3(rows), dim3(kFftThreads), fft_rt_lds(k_ifft_real_rt, L), s, shape_of(L),
-                     in, tw, out);
+static void launch_ifft_real(int L, const cf *in, const cf *tw, float *out, int rows, hipStream_t s) {
+  fft_size_switch<64>(
+      L, [&](auto LL) { hipLaunchKernelGGL((k_ifft_real<decltype(LL)::value>), dim3(rows), dim3(kFftThreads), 0, s, in, tw, out); },
+      [&] { hipLaunchKernelGGL(k_ifft_real_rt, dim3(rows), dim3(kFftThreads), fft_rt_lds(k_ifft_real_rt, L), s, shape_of(L), in, tw, out); });
+  EARHIP_HIP(hipGetLastError());
 }
-static void conv_forward_rt(int L, const float *x, int fade, const cf *tw, cf *Xo, cf *Xn, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv_forward_rt, dim3(1), dim3(kFftThreads), fft_rt_lds(k_conv_forward_rt, L), s,
-                     shape_of(L), x, fade, tw, Xo, Xn);
+static void launch_conv_forward(int L, const float *x, int fade, const cf *tw, cf *Xo, cf *Xn, hipStream_t s) {
+  fft_size_switch<64>(
+      L, [&](auto LL) { hipLaunchKernelGGL((k_conv_forward<decltype(LL)::value>), dim3(1), dim3(kFftThreads), 0, s, x, fade, tw, Xo, Xn); },
+      [&] {
+        hipLaunchKernelGGL(k_conv_forward_rt, dim3(1), dim3(kFftThreads), fft_rt_lds(k_conv_forward_rt, L), s, shape_of(L), x, fade, tw, Xo, Xn);
+      });
+  EARHIP_HIP(hipGetLastError());
 }
-static void conv_ifft_ola_rt(int L, const cf *Y, const cf *tw, float *tail, int use_tail, int mode, float *out,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(k_conv_ifft_ola_rt, dim3(1), dim3(kFftThreads), fft_rt_lds(k_conv_ifft_ola_rt, L), s,
-                     shape_of(L), Y, tw, tail, use_tail, mode, out);
+static void launch_conv_ifft_ola(int L, const cf *Y, const cf *tw, float *tail, int use_tail, int mode, float *out, hipStream_t s) {
+  fft_size_switch<64>(
+      L,
+      [&](auto LL) { hipLaunchKernelGGL((k_conv_ifft_ola<decltype(LL)::value>), dim3(1), dim3(kFftThreads), 0, s, Y, tw, tail, use_tail, mode, out); },
+      [&] {
+        hipLaunchKernelGGL(k_conv_ifft_ola_rt, dim3(1), dim3(kFftThreads), fft_rt_lds(k_conv_ifft_ola_rt, L), s, shape_of(L), Y, tw, tail,
+                           use_tail, mode, out);
+      });
+  EARHIP_HIP(hipGetLastError());
 }
 }  // namespace earhip
 
@@ -173,9 +173,7 @@ int earhip_fft_plan_create(earhip_ctx *ctx, size_t n_fft, earhip_fft_plan **out)
     std::unique_ptr<earhip_fft_plan> p(new earhip_fft_plan);
     p->ctx = ctx;
     p->L = (int)n_fft;
-    const auto tw = make_twiddles(p->L);
-    p->tw.alloc(p->L);
-    EARHIP_HIP(hipMemcpy(p->tw.p, tw.data(), sizeof(cf) * p->L, hipMemcpyHostToDevice));
+    upload_twiddles(p->tw, p->L);
     p->spec.alloc(p->L);
     p->td.alloc(p->L);
     *out = p.release();
@@ -210,10 +208,7 @@ int earhip_fft_reverse(earhip_fft_plan *p, const float *in_complex, float *out) 
     ctx->use();
     EARHIP_HIP(hipMemcpyAsync(p->spec.p, in_complex, sizeof(cf) * (p->L / 2 + 1),
                               hipMemcpyHostToDevice, ctx->stream));
-#define CALL(LL) ifft_real_t<LL>(p->spec.p, p->tw.p, p->td.p, 1, ctx->stream)
-    EARHIP_DISPATCH_L(p->L, CALL, ifft_real_rt(p->L, p->spec.p, p->tw.p, p->td.p, 1, ctx->stream))
-#undef CALL
-    EARHIP_HIP(hipGetLastError());
+    launch_ifft_real(p->L, p->spec.p, p->tw.p, p->td.p, 1, ctx->stream);
     EARHIP_HIP(hipMemcpyAsync(out, p->td.p, sizeof(float) * p->L, hipMemcpyDeviceToHost, ctx->stream));
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
   });
@@ -232,9 +227,7 @@ int earhip_conv_ctx_create(earhip_ctx *ctx, size_t block_size, earhip_conv_ctx *
     c->ctx = ctx;
     c->B = (int)block_size;
     c->L = 2 * c->B;
-    const auto tw = make_twiddles(c->L);
-    c->tw.alloc(c->L);
-    EARHIP_HIP(hipMemcpy(c->tw.p, tw.data(), sizeof(cf) * c->L, hipMemcpyHostToDevice));
+    upload_twiddles(c->tw, c->L);
     *out = c.release();
   });
 }
@@ -388,10 +381,7 @@ int earhip_conv_process(earhip_conv *c, const float *in, float *out) {
       EARHIP_HIP(hipMemcpyAsync(c->d_in.p, c->p_io.p, sizeof(float) * B, hipMemcpyHostToDevice, s));
       staged = true;
       const int fade = c->filt(1) != c->filt(0) ? 1 : 0;  // :162
-#define CALL(LL) conv_forward_t<LL>(c->d_in.p, fade, cc->tw.p, c->old_at(0), c->new_at(0), s)
-      EARHIP_DISPATCH_L(L, CALL, conv_forward_rt(L, c->d_in.p, fade, cc->tw.p, c->old_at(0), c->new_at(0), s))
-#undef CALL
-      EARHIP_HIP(hipGetLastError());
+      launch_conv_forward(L, c->d_in.p, fade, cc->tw.p, c->old_at(0), c->new_at(0), s);
       c->new_zero[i0] = 0;
       c->old_zero[i0] = fade ? 0 : 1;  // :186
     }
@@ -424,16 +414,10 @@ int earhip_conv_process(earhip_conv *c, const float *in, float *out) {
 
     bool have_out = true;
     if (any) {  // :217-226
-#define CALL(LL) conv_ifft_ola_t<LL>(c->Y.p, cc->tw.p, c->tail.p, c->tail_zero ? 0 : 1, 0, c->d_out.p, s)
-      EARHIP_DISPATCH_L(L, CALL, conv_ifft_ola_rt(L, c->Y.p, cc->tw.p, c->tail.p, c->tail_zero ? 0 : 1, 0, c->d_out.p, s))
-#undef CALL
-      EARHIP_HIP(hipGetLastError());
+      launch_conv_ifft_ola(L, c->Y.p, cc->tw.p, c->tail.p, c->tail_zero ? 0 : 1, 0, c->d_out.p, s);
       c->tail_zero = false;
     } else if (!c->tail_zero) {  // :227-230
-#define CALL(LL) conv_ifft_ola_t<LL>(c->Y.p, cc->tw.p, c->tail.p, 1, 1, c->d_out.p, s)
-      EARHIP_DISPATCH_L(L, CALL, conv_ifft_ola_rt(L, c->Y.p, cc->tw.p, c->tail.p, 1, 1, c->d_out.p, s))
-#undef CALL
-      EARHIP_HIP(hipGetLastError());
+      launch_conv_ifft_ola(L, c->Y.p, cc->tw.p, c->tail.p, 1, 1, c->d_out.p, s);
       c->tail_zero = true;  // tail contents are ignored while the flag is set
     } else {  // :231-234
       have_out = false;

@@ -5,13 +5,10 @@
 #include <memory>
 
 #include "common.h"
+#include "fft_launch.h"
 #include "firmix_kernels.h"
 
 using namespace earhip;
-
-namespace earhip {
-std::vector<cf> make_twiddles(int L);  // api_render.hip
-}
 
 struct earhip_firmix {
   earhip_ctx *ctx = nullptr;
@@ -112,24 +109,19 @@ struct earhip_firmix {
     EARHIP_HIP(hipGetLastError());
   }
 
-#define EARHIP_FIRMIX_SIZES(F, ...)             \
-  switch (B) {                                  \
-    case 64: F<128>(__VA_ARGS__); break;        \
-    case 128: F<256>(__VA_ARGS__); break;       \
-    case 256: F<512>(__VA_ARGS__); break;       \
-    case 512: F<1024>(__VA_ARGS__); break;      \
-    case 1024: F<2048>(__VA_ARGS__); break;     \
-    case 2048: F<4096>(__VA_ARGS__); break;     \
-    case 4096: F<8192>(__VA_ARGS__); break;     \
-    default: fail_internal("FIR matrix block size without a kernel"); \
+  // f(the transform size 2 B as a constant): the kernels exist for blocks of 64 ... 4096 samples
+  template <typename F>
+  void with_transform_size(F &&f) {
+    fft_size_switch<128>(2 * B, f, [] { fail_internal("FIR matrix block size without a kernel"); });
   }
 
   // device rows; the caller has checked the room and the strides
   void feed(size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride) {
-    EARHIP_FIRMIX_SIZES(launch_t, (int)nblocks, in, in_stride, out, out_stride)
+    with_transform_size([&](auto L) { launch_t<decltype(L)::value>((int)nblocks, in, in_stride, out, out_stride); });
   }
-  void spectra_of_taps(const float *staged, cf *Hdst, int pairs) { EARHIP_FIRMIX_SIZES(spectra_of_taps_t, staged, Hdst, pairs) }
-#undef EARHIP_FIRMIX_SIZES
+  void spectra_of_taps(const float *staged, cf *Hdst, int pairs) {
+    with_transform_size([&](auto L) { spectra_of_taps_t<decltype(L)::value>(staged, Hdst, pairs); });
+  }
 
   // ---- filter sets ----
   void check_loadable(int set) const {
@@ -206,9 +198,7 @@ int earhip_firmix_create(earhip_ctx *ctx, const earhip_firmix_config *cfg, earhi
     const FirmixPlan &p = fm->plan;
     fm->C = p.n_in, fm->K = p.n_out, fm->B = p.block, fm->P = p.partitions, fm->R = p.ring, fm->max_blocks = cfg->max_blocks;
     const size_t B = (size_t)p.block, PB = (size_t)p.partitions * B;
-    const auto tw = make_twiddles(2 * p.block);
-    fm->tw.alloc(tw.size());
-    EARHIP_HIP(hipMemcpy(fm->tw.p, tw.data(), sizeof(cf) * tw.size(), hipMemcpyHostToDevice));
+    upload_twiddles(fm->tw, 2 * p.block);
     fm->H.alloc(p.spectra_elems());
     fm->X.alloc(p.ring_elems());
     fm->prev.alloc(p.state_elems());
@@ -263,9 +253,7 @@ int earhip_firmix_create_sets(earhip_ctx *ctx, const earhip_firmix_config *cfg, 
     fm->loaded.assign((size_t)n_sets, 0);
     fm->set_pairs.assign((size_t)n_sets, 0);
     const size_t B = (size_t)p.block;
-    const auto tw = make_twiddles(2 * p.block);
-    fm->tw.alloc(tw.size());
-    EARHIP_HIP(hipMemcpy(fm->tw.p, tw.data(), sizeof(cf) * tw.size(), hipMemcpyHostToDevice));
+    upload_twiddles(fm->tw, 2 * p.block);
     fm->H.alloc((size_t)n_sets * fm->set_spectra());
     fm->X.alloc(p.ring_elems());
     fm->prev.alloc(p.state_elems());

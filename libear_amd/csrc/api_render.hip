@@ -3,6 +3,8 @@
 // decorrelate_delay_mix, `nblocks` blocks per call, state resident in HBM.
 // Around it: the taps on its output bus (meter, FIR matrix, limiter), the host-pointer forms (long calls: the chunk pipeline of
 // host_pipeline.h) and the forms that take and make interleaved PCM frames (their conversions: api_frames.hip, pcm_frames.h).
+// Elsewhere: the gain stage's launches (api_core.hip), the decorrelator stage K2 (decor_stage.h; its decisions: decor_plan.h;
+// its kernels are compiled here), the transforms' launch layer (fft_launch.h; launch_spectrum itself: api_conv.hip).
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
@@ -11,140 +13,42 @@
 
 #include "common.h"
 #include "curves.h"
+#include "decor_stage.h"
 #include "host_pipeline.h"
 #include "pcm_frames.h"
-#include "fft_kernels.h"
-#include "render_kernels.h"
 
 using namespace earhip;
 
-namespace earhip {
-// twiddle table exp(-2*pi*i*t/L), computed in double
-std::vector<cf> make_twiddles(int L) {
-  std::vector<cf> tw(L);
-  const double pi = 3.14159265358979323846264338327950288;
-  for (int t = 0; t < L; t++) {
-    const double a = -2.0 * pi * (double)t / (double)L;
-    tw[t] = cf_make((float)std::cos(a), (float)std::sin(a));
-  }
-  return tw;
-}
-
-template <int L>
-static void launch_spectrum_t(const float *in, size_t stride, int n_valid, const cf *tw, cf *out,
-                              int rows, hipStream_t s) {
-  hipLaunchKernelGGL((k_spectrum_real<L>), dim3(rows), dim3(kFftThreads), 0, s, in, stride,
-                     n_valid, tw, out);
-}
-void launch_spectrum(int L, const float *in, size_t stride, int n_valid, const cf *tw, cf *out,
-                     int rows, hipStream_t s) {
-  switch (L) {
-    case 64: launch_spectrum_t<64>(in, stride, n_valid, tw, out, rows, s); break;
-    case 128: launch_spectrum_t<128>(in, stride, n_valid, tw, out, rows, s); break;
-    case 256: launch_spectrum_t<256>(in, stride, n_valid, tw, out, rows, s); break;
-    case 512: launch_spectrum_t<512>(in, stride, n_valid, tw, out, rows, s); break;
-    case 1024: launch_spectrum_t<1024>(in, stride, n_valid, tw, out, rows, s); break;
-    case 2048: launch_spectrum_t<2048>(in, stride, n_valid, tw, out, rows, s); break;
-    case 4096: launch_spectrum_t<4096>(in, stride, n_valid, tw, out, rows, s); break;
-    case 8192: launch_spectrum_t<8192>(in, stride, n_valid, tw, out, rows, s); break;
-    default: {  // any other size: mixed radix at run time
-      FftShape S;
-      if (!fft_make_shape(L, &S)) fail_invalid("FFT size must be in [4, 8192]");
-      hipLaunchKernelGGL(k_spectrum_real_rt, dim3(rows), dim3(kFftThreads), fft_rt_lds(k_spectrum_real_rt, L), s, S,
-                         in, stride, n_valid, tw, out);
-    }
-  }
-  EARHIP_HIP(hipGetLastError());
-}
-}  // namespace earhip
-
-template <int L>
-static void launch_decor_t(const DecorParams &P, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_decorrelate_delay_mix<L>), grid, dim3(256), 0, s, P);
-}
-static void launch_decor(int L, const DecorParams &P, dim3 grid, hipStream_t s, bool force_wg) {
-  switch (L) {
-    case 128: launch_decor_t<128>(P, grid, s); break;
-    case 256: launch_decor_t<256>(P, grid, s); break;
-    case 512: launch_decor_t<512>(P, grid, s); break;
-    case 1024:
-      if (force_wg) {  // the workgroup-per-run kernel (FIRs of several partitions; option K2_WG)
-        launch_decor_t<1024>(P, grid, s);
-      } else {  // one wave per run, kDecorWaves runs per workgroup
-        hipLaunchKernelGGL(k_decorrelate_wave, dim3((grid.x + kDecorWaves - 1) / kDecorWaves, grid.y),
-                           dim3(64 * kDecorWaves), 0, s, P);
-      }
-      break;
-    case 2048: launch_decor_t<2048>(P, grid, s); break;
-    case 4096: launch_decor_t<4096>(P, grid, s); break;
-    case 8192: launch_decor_t<8192>(P, grid, s); break;
-    default: {  // any other block size: mixed-radix transforms at run time
-      FftShape S;
-      if (!fft_make_shape(L, &S)) fail_invalid("block_size must be in [16, 4096]");
-      const size_t lds = fft_rt_lds(k_decorrelate_delay_mix_rt, L, sizeof(float) * (L / 2));
-      hipLaunchKernelGGL(k_decorrelate_delay_mix_rt, grid, dim3(256), lds, s, P, S);
-    }
-  }
-  EARHIP_HIP(hipGetLastError());
-}
-
-// Run length (odd, so that the warm-up block pairs with the first one) of k_decorrelate_wave for a
-// call of T blocks on N loudspeakers.  A run of R blocks costs (R+1)/2 pair transforms, each
-// workgroup puts one wave on every SIMD, and a CU holds three workgroups (LDS): the cost of a
-// round of k = 1..3 resident workgroups per CU is pairs x c[k] with the measured pair times
-// c = 6.9, 9.3, 12.2 us (latency-bound at this occupancy).  NOTES.md (round 2, section 4, K2).
-static int wave_run_len(int T, int N, int num_cus) {
-  const double c[4] = {0.0, 6.9, 9.3, 12.2};
-  int best = 1;
-  double best_cost = 1e30;
-  for (int R = 1; R <= 31; R += 2) {
-    const long runs = (T + R - 1) / R;
-    const long wgs = (runs + earhip::kDecorWaves - 1) / earhip::kDecorWaves * N;
-    const long full = wgs / (3L * num_cus), rem = wgs - full * 3L * num_cus;
-    const double pairs = (R + 1) / 2;
-    const double cost = pairs * (full * c[3] + c[(rem + num_cus - 1) / num_cus]);
-    if (cost <= best_cost) best_cost = cost, best = R;  // (ties: the longer run does less warm-up work)
-    if (runs == 1) break;
-  }
-  return best;
-}
+// What a call reports about itself afterwards (the query exports at the end of this file).  A call cut in two (render_spans)
+// is reported as its main span, with the blocks of its tail.
+struct CallReport {
+  int kind = -1;  // gain kernel of the call: 0 VALU (strict), 1 f32 MFMA, 2 f32 MFMA on the tile grid, 3 f16x2 MFMA, 4 f16x2 MFMA over piece lists,
+                  // 5 f16x2 MFMA with hinges (gain_hg.h)
+  int plan[3] = {0, 0, 0};   // tile samples, tiles, grid-level object splits
+  int paired = -1;           // layout of its piece lists: 1 paired, 0 packed, -1 none built
+  size_t scratch_bytes = 0;  // K0 / K1 scratch the call needed
+  bool gated = false;        // the call was planned for the hinge kernel behind a device-side gate
+  bool device_form = false;  // ... its split-operand kernel picked its form (plain / wide) on the device
+  bool hg_robust = false;    // ... a gated call beyond the packed kink products' span runs the hinge kernel's robust form (no stand-by lists)
+  int tail_blocks = 0;       // blocks of the call that ran as its tail part (0: the call was not cut)
+};
 
 struct earhip_render {
   earhip_ctx *ctx = nullptr;
-  int M = 0, N = 0, B = 0, K = 1, D = 0, T = 0;
-  // The decorrelators' own partition size Bk (and transform size Lk = 2 Bk).  A linear convolution does not
-  // depend on how it is partitioned, so callers' blocks of 1024, 2048 ... samples run through 512-sample
-  // partitions whenever the FIRs fit one of them: the wave kernel (k_decorrelate_wave) exists for that size
-  // and is 2.5 times faster per sample than the workgroup kernel at 2048 points (BASELINE config 5: K2 0.125
-  // -> 0.05 ms).  Otherwise Bk = B, libear's own partitioning (src/dsp/block_convolver_impl.cpp:16-41).
-  int Bk = 0, Lk = 0;
-  int NP = 1;  // partitions of the decorrelator FIRs (ceil(n_taps / Bk))
+  int M = 0, N = 0, B = 0, K = 1, T = 0;
   std::unique_ptr<CurveSet> curves;
   int64_t t = 0;  // sample clock: absolute time of the next block
-  int last_plan[3] = {0, 0, 0};  // tile samples, tiles, grid-level object splits of the last call
-  int last_paired = -1;          // layout of its piece lists: 1 paired, 0 packed, -1 none built
-  size_t last_scratch_bytes = 0;  // K0 / K1 scratch the last call needed
-  long scratch_regrows = 0;       // process calls that had to grow the scratch themselves (none on committed curves)
+  CallReport report;         // of the last call
+  long scratch_regrows = 0;  // process calls that had to grow the scratch themselves (none on committed curves)
   // What the last call's gain kernel decided on the device: the kernel that did the call left a copy of the context's mode
   // word in THIS renderer's own slot (rec[0]: the call, or the main span of a call cut in two; rec[1]: the tail span), so the
   // queries below stay valid whatever other renderers of the context do afterwards.
   DevBuf<unsigned> rec;
-  bool last_gated = false;       // the last call (its main span) was planned for the hinge kernel behind a device-side gate
-  bool last_device_form = false; // ... its split-operand kernel picked its form (plain / wide) on the device
-  bool last_hg_robust = false;   // ... a gated call beyond the packed kink products' span runs the hinge kernel's robust form (no stand-by lists)
-  int last_kind = -1;  // gain kernel of the last call: 0 VALU (strict), 1 f32 MFMA, 2 f32 MFMA on the tile grid, 3 f16x2 MFMA, 4 f16x2 MFMA over piece lists,
-                       // 5 f16x2 MFMA with hinges (gain_hg.h)
-  int run_len = 11;       // blocks per decorrelator run of the workgroup kernel
-  bool run_len_set = false;  // EARHIP_RUN given: also fixes the run length of the wave kernel
 
   DevBuf<SegDesc> desc;
   DevBuf<float> bus;  // [gsplit][K*N][bus_stride], strides chosen per call
   int max_gsplit = 1;
-  DevBuf<cf> H, tw;
-  DevBuf<float> tail[2], dly[2], hist[2];  // tails [NP][N][Bk]; diffuse-bus history [N][(NP-1) Bk]
-  DevBuf<float> ztail, zdly, zhist;  // all-zero state, never written: what the first call after a reset reads
-  bool fresh = true;          // no call since create / reset: the state is zero
-  int cur = 0;  // which state buffer holds the current state
+  DecorStage decor;  // K2 (made when K == 2; NP stays 1 on one bus)
   // host-pointer staging
   DevBuf<float> d_in, d_out;
   PinBuf<float> p_in, p_out;
@@ -281,7 +185,7 @@ struct earhip_render {
   // (FIRs of several partitions accumulate into the output: that stays in device memory, and out_st is 0 then)
   void process_short_call(size_t nblocks, float *out0, size_t out_st) {
     const size_t n = nblocks * (size_t)B;
-    const bool direct_out = NP <= 1;
+    const bool direct_out = decor.NP <= 1;
     process_device(nblocks, d_in.p, n, out_st ? out0 : direct_out ? p_out.p : d_out.p, out_st ? out_st : n);
     if (!out_st && !direct_out) EARHIP_HIP(hipMemcpyAsync(p_out.p, d_out.p, sizeof(float) * n * N, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -413,24 +317,17 @@ struct earhip_render {
         if (rest > 0 && rest <= (size_t)W * eighths / 8 && main_samples % (size_t)B == 0) {
           const size_t main_blocks = main_samples / (size_t)B;
           process_span(main_blocks, in_dev, in_stride, out_dev, out_stride, false);
-          const int kind = last_kind, plan3[3] = {last_plan[0], last_plan[1], last_plan[2]};
-          const size_t scratch = last_scratch_bytes;
-          const bool gated = last_gated, device_form = last_device_form, hg_robust = last_hg_robust;
-          const int paired = last_paired;
+          const CallReport main = report;
           process_span(nblocks - main_blocks, in_dev + main_samples, in_stride, out_dev + main_samples, out_stride, true);
-          last_kind = kind;  // (what the call is reported as: its main part — kernel, plan and what it decided on the device)
-          last_gated = gated, last_device_form = device_form, last_paired = paired, last_hg_robust = hg_robust;
-          for (int i = 0; i < 3; i++) last_plan[i] = plan3[i];
-          last_scratch_bytes = scratch;
-          last_tail_blocks = (int)(nblocks - main_blocks);
+          report = main;  // (what the call is reported as: its main part — kernel, plan and what it decided on the device)
+          report.tail_blocks = (int)(nblocks - main_blocks);
           return;
         }
       }
     }
-    last_tail_blocks = 0;
+    report.tail_blocks = 0;
     process_span(nblocks, in_dev, in_stride, out_dev, out_stride, false, have_plan ? &whole : nullptr);
   }
-  int last_tail_blocks = 0;  // blocks of the last call that ran as its tail part (0: the call was not cut)
 
   void process_span(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev,
                     size_t out_stride, bool continues, const MixLaunch *planned = nullptr) {
@@ -444,7 +341,7 @@ struct earhip_render {
     MixLaunch ml = planned ? *planned : plan_call(nblocks, in_stride);
     if (ml.kind == GainKernel::Hinge) curves->ensure_kinks(ctx);  // (already there unless an option changed the plan since the commit)
 
-    last_kind = (int)ml.kind;
+    report.kind = (int)ml.kind;
     {
       // K0 / K1 scratch for THIS plan and THESE curves (round 3: 537 MB at the headline's size for any curves): reserved
       // when the curves were committed (reserve_for_curves).  The one exception, documented in earhip.h: a plan that no
@@ -456,17 +353,17 @@ struct earhip_render {
         desc.reserve(need + need / 2);
         scratch_regrows++;
       }
-      last_scratch_bytes = need * 16;
+      report.scratch_bytes = need * 16;
     }
     const size_t bus_stride = ((size_t)nsamples + 3) & ~(size_t)3;
     const size_t part_stride = bus_stride * K * N;
     // (the bus is sized for every plan plan_mix can make, earhip_render_create; should a tuning knob push a plan
     // beyond it, plan_call has taken fewer object splits, always a valid plan)
     if (part_stride * ml.gsplit > bus.n) fail_internal("bus buffer too small for this launch plan");
-    last_paired = (ml.kind == GainKernel::Pieces || ml.kind == GainKernel::Hinge) ? (ml.paired ? 1 : 0) : -1;
-    last_plan[0] = ml.tile();
-    last_plan[1] = ml.ntiles;
-    last_plan[2] = ml.gsplit;
+    report.paired = (ml.kind == GainKernel::Pieces || ml.kind == GainKernel::Hinge) ? (ml.paired ? 1 : 0) : -1;
+    report.plan[0] = ml.tile();
+    report.plan[1] = ml.ntiles;
+    report.plan[2] = ml.gsplit;
     Pending pd;
     hipEvent_t *evp = nullptr;
     // (the second part of a call cut in two is timed when its first part was)
@@ -486,60 +383,10 @@ struct earhip_render {
                                    record, evp);
     } else {
       mix = launch_gain_mix(ctx, *curves, ml, strict, t, nsamples, in_dev, in_stride, bus.p, bus_stride, part_stride, desc.p, record, evp);
-      DecorParams P;
-      P.bus = bus.p;
-      P.bus_stride = bus_stride;
-      P.part_stride = part_stride;
-      P.nparts = ml.gsplit;
-      const bool wave_k2 = Lk == 1024 && NP == 1 && !ctx->get(OPT_K2_WG);
-      const int kblocks = (int)(nblocks * (size_t)(B / Bk));  // the call in decorrelator partitions
-      if (wave_k2 && ml.gsplit > 1) {
-        // The wave kernel has one wave per run: summing the object splits there is a chain of
-        // dependent loads on the call's critical path (block mode).  Sum them into slab 0 with the
-        // whole chip first (K N rows; in place: a thread reads and writes its own sample only).
-        if (evp) EARHIP_HIP(hipEventRecord(evp[4], ctx->stream));
-        hipLaunchKernelGGL(k_sum_parts, dim3((nsamples + 255) / 256, K * N), dim3(256), 0, ctx->stream, bus.p,
-                           part_stride, ml.gsplit, bus_stride, K * N, nsamples, bus.p, bus_stride);
-        EARHIP_HIP(hipGetLastError());
-        P.nparts = 1;
-      }
-      P.out = out_dev;
-      P.out_stride = out_stride;
-      P.tw = tw.p;
-      P.dly_in = fresh ? zdly.p : dly[cur].p;
-      P.dly_out = dly[cur ^ 1].p;
-      P.N = N;
-      P.T = kblocks;
-      const int R = wave_k2 && !run_len_set ? wave_run_len(kblocks, N, ctx->num_cus) : run_len;
-      P.R = R;
-      P.D = D;
-      P.hist_len = (NP - 1) * Bk;
-      P.hist_in = fresh ? zhist.p : hist[cur].p;
-      P.hist_out = hist[cur ^ 1].p;
-      const dim3 grid((unsigned)((kblocks + R - 1) / R), N);
-      if (evp && P.nparts == ml.gsplit) EARHIP_HIP(hipEventRecord(evp[4], ctx->stream));
-      // one launch per partition of the FIRs: partition 0 writes (decorrelated + delayed direct), the
-      // others add their share of the decorrelated signal (render_kernels.h)
-      for (int part = 0; part < NP; part++) {
-        P.H = H.p + (size_t)part * N * Lk;
-        P.tail_in = (fresh ? ztail.p : tail[cur].p) + (fresh ? 0 : (size_t)part * N * Bk);
-        P.tail_out = tail[cur ^ 1].p + (size_t)part * N * Bk;
-        P.shift = part * Bk;
-        P.accumulate = part > 0 ? 1 : 0;
-        if (wave_k2) {
-          hipLaunchKernelGGL(k_decorrelate_wave, dim3((grid.x + kDecorWaves - 1) / kDecorWaves, grid.y), dim3(64 * kDecorWaves),
-                             0, ctx->stream, P);
-          EARHIP_HIP(hipGetLastError());
-        } else {
-          launch_decor(Lk, P, grid, ctx->stream, true);
-        }
-      }
-      if (evp) EARHIP_HIP(hipEventRecord(evp[5], ctx->stream));
-      cur ^= 1;
-      fresh = false;
+      decor.run(ctx, nblocks, nsamples, bus.p, bus_stride, part_stride, ml.gsplit, out_dev, out_stride, evp);
     }
     if (timed) pending.push_back(pd);
-    last_gated = mix.gated, last_device_form = mix.device_form, last_hg_robust = mix.hinge_robust;
+    report.gated = mix.gated, report.device_form = mix.device_form, report.hg_robust = mix.hinge_robust;
     if (mix.grew) scratch_regrows++;  // (a buffer of the context no renderer had announced: earhip.h)
     t += nsamples;
   }
@@ -577,19 +424,7 @@ int earhip_render_create(earhip_ctx *ctx, const earhip_render_config *cfg, earhi
     r->N = cfg->n_out;
     r->B = cfg->block_size;
     r->K = cfg->n_buses;
-    r->D = cfg->delay;
     r->T = cfg->max_blocks;
-    r->Bk = r->B;
-    if (r->K == 2 && r->B > 512 && r->B % 512 == 0 && cfg->n_taps <= 512 && !ctx->get(OPT_K2_OWN_BLOCK)) r->Bk = 512;
-    r->Lk = 2 * r->Bk;
-    // workgroup decorrelator kernel: blocks per run.  Block 1024 (BASELINE config 5, 512 blocks x 24
-    // loudspeakers): 7 -> K2 0.113 ms, 5 -> 0.117, 11 -> 0.128, 15 -> 0.140 (two rounds of workgroups that fill
-    // the chip evenly beat one ragged round)
-    if (r->Lk == 2048) r->run_len = 7;
-    if (ctx->has(OPT_RUN)) {  // tuning knob: blocks per decorrelator run (odd)
-      const int v = ctx->get(OPT_RUN);
-      if (v >= 1 && v <= 255) r->run_len = v | 1, r->run_len_set = true;
-    }
     r->curves.reset(new CurveSet(r->M, r->K * r->N, r->K, false));
     const size_t max_samples = (size_t)r->T * r->B;
     reserve_call_words(ctx, r->M, max_samples);  // (the context's words for calls of this size: no process call makes them)
@@ -611,46 +446,7 @@ int earhip_render_create(earhip_ctx *ctx, const earhip_render_config *cfg, earhi
       if (v >= 1 && v <= 32) r->max_gsplit = v;
     }
     r->bus.alloc_zero((size_t)r->K * r->N * bus_samples_bound(ctx, max_samples, r->max_gsplit), ctx->stream);
-    if (r->K == 2) {
-      const auto tw = make_twiddles(r->Lk);
-      r->tw.alloc(r->Lk);
-      EARHIP_HIP(hipMemcpy(r->tw.p, tw.data(), sizeof(cf) * r->Lk, hipMemcpyHostToDevice));
-      // H[p] = DFT_L(zero-padded partition p of the FIR: taps [p B, (p + 1) B), Filter::Filter,
-      // block_convolver_impl.cpp:16-41), computed with the device transform, then made exactly Hermitian so
-      // that two real blocks separate cleanly
-      r->NP = (cfg->n_taps + r->Bk - 1) / r->Bk;
-      const size_t rows = (size_t)r->NP * r->N;
-      std::vector<float> parts(rows * r->Bk, 0.0f);  // [NP][N][B]
-      for (int n = 0; n < r->N; n++)
-        for (int t = 0; t < cfg->n_taps; t++)
-          parts[((size_t)(t / r->Bk) * r->N + n) * r->Bk + t % r->Bk] = cfg->decorrelators[(size_t)n * cfg->n_taps + t];
-      DevBuf<float> taps;
-      taps.alloc(parts.size());
-      EARHIP_HIP(hipMemcpy(taps.p, parts.data(), sizeof(float) * parts.size(), hipMemcpyHostToDevice));
-      r->H.alloc(rows * r->Lk);
-      launch_spectrum(r->Lk, taps.p, r->Bk, r->Bk, r->tw.p, r->H.p, (int)rows, ctx->stream);
-      EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-      std::vector<cf> h(rows * r->Lk);
-      EARHIP_HIP(hipMemcpy(h.data(), r->H.p, sizeof(cf) * h.size(), hipMemcpyDeviceToHost));
-      for (size_t n = 0; n < rows; n++) {
-        cf *hn = h.data() + n * r->Lk;
-        hn[0].y = 0.0f;
-        hn[r->Bk].y = 0.0f;
-        for (int k = 1; k < r->Bk; k++) hn[r->Lk - k] = cf_conj(hn[k]);
-      }
-      EARHIP_HIP(hipMemcpy(r->H.p, h.data(), sizeof(cf) * h.size(), hipMemcpyHostToDevice));
-      const size_t hist_n = (size_t)r->N * std::max((r->NP - 1) * r->Bk, 1);
-      for (int i = 0; i < 2; i++) {
-        r->tail[i].alloc_zero(rows * r->Bk, ctx->stream);
-        r->dly[i].alloc_zero((size_t)r->N * std::max(r->D, 1), ctx->stream);
-        r->hist[i].alloc_zero(hist_n, ctx->stream);
-        if (i == 0) {
-          r->ztail.alloc_zero((size_t)r->N * r->Bk, ctx->stream);
-          r->zdly.alloc_zero((size_t)r->N * std::max(r->D, 1), ctx->stream);
-          r->zhist.alloc_zero(hist_n, ctx->stream);
-        }
-      }
-    }
+    if (r->K == 2) r->decor.create(ctx, *cfg, r->B);
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
     *out = r.release();
   });
@@ -698,7 +494,7 @@ int earhip_render_reset(earhip_render *r, int64_t sample_time) {
     require(r != nullptr, "render must not be NULL");
     r->ctx->use();
     r->t = sample_time;
-    r->fresh = true;  // the next call reads the all-zero state and rewrites its own pair completely
+    r->decor.reset();
     r->levels.zero(r->ctx->stream);  // (only a renderer that has made PCM frames has any)
   });
 }
@@ -788,7 +584,7 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
     const double t_a = dbg ? now() : 0.0;
     const bool short_call = r->host_plan(nblocks, false).short_call;
     const size_t in_st = r->direct_stride(in, r->M, n);
-    const size_t out_st = r->NP <= 1 || !short_call ? r->direct_stride(out, r->N, n) : 0;
+    const size_t out_st = r->decor.NP <= 1 || !short_call ? r->direct_stride(out, r->N, n) : 0;
     r->last_host_chunks = 0;
     if (!short_call) {
       // Long calls (libear's calling convention for offline renders: host channel pointers, any length) run as the pipeline of
@@ -891,7 +687,7 @@ static void process_frames_host(earhip_render *r, size_t nblocks, const void *fr
   // interleaved outputs, float or PCM, as bytes: a frame is ofb bytes; ilv_host the caller's frames, ilv_dev / ilv_pin ours
   const size_t ofb = (size_t)N * (po ? (size_t)pcm_sample_bytes(po->format) : sizeof(float));
   unsigned char *const ilv_host = po ? static_cast<unsigned char *>(out_pcm) : reinterpret_cast<unsigned char *>(out0);
-  const size_t out_st = out_interleaved ? 0 : r->NP <= 1 || !plan.short_call ? r->direct_stride(out, N, n) : 0;
+  const size_t out_st = out_interleaved ? 0 : r->decor.NP <= 1 || !plan.short_call ? r->direct_stride(out, N, n) : 0;
   const bool out_direct = out_interleaved ? ctx->host_reachable(ilv_host, n * ofb) : out_st != 0;
   r->d_in.reserve(cap * M);
   r->d_out.reserve(cap * N);
@@ -1078,7 +874,7 @@ int earhip_render_get_timing(earhip_render *r, double out[6]) {
 int earhip_render_gain_kernel(const earhip_render *r, int *kind) {
   return guarded([&] {
     require(r != nullptr && kind != nullptr, "NULL argument");
-    *kind = r->last_kind;
+    *kind = r->report.kind;
   });
 }
 
@@ -1086,7 +882,7 @@ int earhip_render_hinge_standby(earhip_render *r, int *standby) {
   return guarded([&] {
     require(r != nullptr && standby != nullptr, "NULL argument");
     *standby = 0;
-    if (r->last_kind != 5 || !r->last_gated || r->last_hg_robust) return;  // (robust form allowed: nobody stands by)
+    if (r->report.kind != 5 || !r->report.gated || r->report.hg_robust) return;  // (robust form allowed: nobody stands by)
     *standby = (r->mode_word() & kGateHingeUnsafe) ? 1 : 0;
   });
 }
@@ -1095,7 +891,7 @@ int earhip_render_hinge_robust(earhip_render *r, int *robust) {
   return guarded([&] {
     require(r != nullptr && robust != nullptr, "NULL argument");
     *robust = 0;
-    if (r->last_kind != 5 || !r->last_hg_robust) return;
+    if (r->report.kind != 5 || !r->report.hg_robust) return;
     *robust = hinge_span_exceeded(r->mode_word(), r->M) ? 1 : 0;
   });
 }
@@ -1104,8 +900,8 @@ int earhip_render_wide_form(earhip_render *r, int *wide) {
   return guarded([&] {
     require(r != nullptr && wide != nullptr, "NULL argument");
     *wide = 1;
-    if (r->last_kind < 3) *wide = -1;  // (no split operands at all)
-    if (r->last_kind < 3 || !r->last_device_form) return;
+    if (r->report.kind < 3) *wide = -1;  // (no split operands at all)
+    if (r->report.kind < 3 || !r->report.device_form) return;
     *wide = (r->mode_word() & 1u) ? 1 : 0;
   });
 }
@@ -1113,7 +909,7 @@ int earhip_render_wide_form(earhip_render *r, int *wide) {
 int earhip_render_scratch_bytes(const earhip_render *r, size_t *bytes) {
   return guarded([&] {
     require(r != nullptr && bytes != nullptr, "NULL argument");
-    *bytes = r->last_scratch_bytes;
+    *bytes = r->report.scratch_bytes;
   });
 }
 
@@ -1127,7 +923,7 @@ int earhip_render_scratch_regrows(const earhip_render *r, long *count) {
 int earhip_render_last_tail_blocks(const earhip_render *r, int *blocks) {
   return guarded([&] {
     require(r != nullptr && blocks != nullptr, "NULL argument");
-    *blocks = r->last_tail_blocks;
+    *blocks = r->report.tail_blocks;
   });
 }
 
@@ -1141,15 +937,15 @@ int earhip_render_last_host_chunks(const earhip_render *r, int *chunks) {
 int earhip_render_last_list_layout(const earhip_render *r, int *paired) {
   return guarded([&] {
     require(r != nullptr && paired != nullptr, "NULL argument");
-    *paired = r->last_paired;
+    *paired = r->report.paired;
   });
 }
 
 int earhip_render_last_plan(const earhip_render *r, int out[4]) {
   return guarded([&] {
     require(r != nullptr && out != nullptr, "NULL argument");
-    out[0] = r->last_kind;
-    for (int i = 0; i < 3; i++) out[1 + i] = r->last_plan[i];
+    out[0] = r->report.kind;
+    for (int i = 0; i < 3; i++) out[1 + i] = r->report.plan[i];
   });
 }
 

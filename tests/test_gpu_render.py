@@ -274,6 +274,32 @@ def test_long_stream_properties():
     r.close()
 
 
+@pytest.mark.parametrize("block,n_taps", [(64, 100), (512, 512)])
+def test_reset_gives_a_fresh_renderers_bits(block, n_taps):
+    """earhip_render_reset: the decorrelator stage reads the all-zero state after it, which is the state of a renderer just made,
+    so the calls after a reset repeat the calls after create bit for bit: no tolerance.  FIRs of two partitions with a
+    history buffer and accumulating launches (block 64, 100 taps) and the wave kernel (block 512, 512 taps); delay 7."""
+    from libear_amd import capi
+    m, n, nblocks = 4, 5, 3
+    dec = np.random.default_rng(3).uniform(-0.1, 0.1, (n, n_taps)).astype(np.float32)
+    x = scenes.audio(m, 2 * nblocks * block)
+    c = capi.Context(0)
+    try:
+        r = capi.Renderer(c, m, n, block, dec, 7, max_blocks=nblocks)
+        set_renderer_curves(r, scenes.dense_curves(m, n, block, 2 * nblocks))
+        outs = []
+        for again in range(2):
+            if again:
+                r.reset(0)
+            outs += [r.process(x[:, :nblocks * block]), r.process(x[:, nblocks * block:])]
+        r.close()
+    finally:
+        c.close()
+    assert all(np.all(np.isfinite(o)) for o in outs)
+    assert np.any(outs[0]) and np.any(outs[1]) and not np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[2], outs[0]) and np.array_equal(outs[3], outs[1])
+
+
 @pytest.mark.parametrize("m,layout,two_bus", [(64, "9+10+3", True), (40, "4+5+0", False), (1, "0+5+0", True)])
 def test_pinned_and_registered_channel_matrices_skip_the_staging_copies(m, layout, two_bus):
     """earhip_host_alloc / earhip_host_register (include/earhip.h): channel pointers evenly spaced inside memory

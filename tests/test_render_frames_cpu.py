@@ -72,6 +72,24 @@ def test_contiguous_staging_copy_and_shared_chunk_plan_on_cpu(tmp_path):
     assert m and int(m.group(2)) > 1000 and int(m.group(3)) > 100, res.stdout
 
 
+def test_decorrelator_stage_decisions_on_cpu(tmp_path):
+    """decor_plan.h: the partition size, partition count, run length and kernel choice of the renderer's decorrelator stage and
+    the wave kernel's run length == what the renderer decided inline before the header existed (tests/golden/decor_plan.txt: block
+    sizes 16 ... 4096, FIRs of 1 ... 2048 taps, options K2_OWN_BLOCK, K2_WG and RUN; calls of 1 ... 4096 blocks on 1 ... 24
+    loudspeakers and 1 ... 256 CUs), under ASan + UBSan"""
+    exe = tmp_path / "test_decor_plan"
+    src = os.path.join(ROOT, "tests", "cpp", "test_decor_plan.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "libear_amd", "csrc"), src, "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([str(exe), os.path.join(ROOT, "tests", "golden", "decor_plan.txt")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                         text=True, env=env)
+    print(res.stdout)
+    assert res.returncode == 0, res.stdout
+    assert "144 run lengths, 540 plans, 0 failed" in res.stdout, res.stdout
+
+
 def test_frames_symbols_declared_and_exported():
     from libear_amd import build, lib_path
     text = open(os.path.join(ROOT, "include", "earhip.h")).read()

@@ -1,5 +1,6 @@
 """SHA-256 of the outputs of a fixed list of renders that between them pass the branches of the gain stage's launch code:
     python tools/render_digest.py            (EARHIP_LIB=<another build of libearhip.so>: the same list through that build)
+    python tools/render_digest.py k2         (the second list: the decorrelator stage and the transforms' launch layer, at the end)
 One line per case: its name, what the renderer reports about the call (gain kernel, tile, tiles, object splits, list layout, whether
 the device handed the call to the stand-by lists or ran the robust form) and the digest of the output rows.  Two builds whose host
 code enqueues the same kernels on the same data print the same lines; a refactor of the launch code is compared this way.
@@ -132,7 +133,106 @@ def run(name, curves, opts, n_out=24, strict=False, block=B, nblocks=NB, t0=0, l
     print(f"{name:42s} {what}\n    {hashlib.sha256(out.tobytes()).hexdigest()} {hashlib.sha256(out2.tobytes()).hexdigest()}")
 
 
+# ---- the second list (argument "k2"): what launches a transform -----------------------------------------------------------
+# The decorrelator stage at every block size that takes another kernel or partitioning, its options, FIRs of several partitions,
+# object splits summed in front of the wave kernel, a call cut into a main span and a tail (with and without the call timer); then
+# the FFT plugin, a BlockConvolver and a FIR matrix at their smallest, an odd and their largest sizes.
+K2_CASES = []
+
+
+def k2_case(name, block, opts=None, **kw):
+    for n_out in kw.pop("n_outs", (5, 24)):
+        K2_CASES.append((f"{name}_{n_out}ch", block, opts or {}, dict(kw, n_out=n_out)))
+
+
+for b in (48, 64, 128, 256, 512):
+    k2_case(f"k2_block{b}", b)
+k2_case("k2_block512_wg", 512, {"K2_WG": 1})
+k2_case("k2_block512_run3", 512, {"RUN": 3})
+k2_case("k2_block512_taps700", 512, n_taps=700)
+k2_case("k2_block512_taps700_delay0", 512, n_taps=700, delay=0)
+for b in (1024, 2048):
+    k2_case(f"k2_block{b}", b)
+    k2_case(f"k2_block{b}_own_block", b, {"K2_OWN_BLOCK": 1})
+k2_case("k2_block4096_taps4096", 4096, n_taps=4096)
+k2_case("k2_sum_parts", 512, m=128, nblocks=2)
+# (96 objects: from 128 on the planner splits the objects of a call of so few tiles, and a call with object splits is not cut)
+k2_case("k2_tail_cut", 512, {"H2_TILE": 512, "HOST_CHUNK_MB": 0}, m=96, nblocks=264, calls=1, n_outs=(24,))
+k2_case("k2_tail_cut_timed", 512, {"H2_TILE": 512, "HOST_CHUNK_MB": 0}, m=96, nblocks=264, calls=1, timing=True, n_outs=(24,))
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def run_k2(name, block, opts, n_out, m=16, nblocks=4, n_taps=512, delay=255, calls=2, timing=False):
+    rng = np.random.default_rng(6)
+    dec = rng.uniform(-0.1, 0.1, (n_out, n_taps)).astype(np.float32)
+    x = scenes.audio(m, block * nblocks)
+    ctx = capi.Context(0)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    r = capi.Renderer(ctx, m, n_out, block, dec, delay, max_blocks=nblocks)
+    for i, (t, d, f) in enumerate(scenes.dense_curves(m, n_out, block, nblocks)):
+        r.set_object_points(i, t, d, f)
+    if timing:
+        r.enable_timing(1)
+    outs, what = [], ""
+    for _ in range(calls):
+        outs.append(r.process(x))
+        plan = r.last_plan()
+        what += f" [kernel {plan['kernel']} tile {plan['tile']} ntiles {plan['ntiles']} gsplit {plan['gsplit']} tail {r.last_tail_blocks()}]"
+    if timing:
+        tm = r.get_timing()
+        what += f" timed calls: gain {tm['gain_mix_launches']:g} decor {tm['decor_launches']:g} prep {tm['prep_launches']:g}"
+    r.close()
+    ctx.close()
+    assert all(np.all(np.isfinite(o)) for o in outs), name
+    print(f"{name:42s}{what}\n    {' '.join(sha(o) for o in outs)}")
+
+
+def run_transforms():
+    rng = np.random.default_rng(9)
+    ctx = capi.Context(0)
+    for n in (64, 96, 8192):
+        p = capi.FFTPlan(ctx, n)
+        X = p.forward(rng.uniform(-1.0, 1.0, n).astype(np.float32))
+        y = p.reverse(X)
+        p.close()
+        assert np.all(np.isfinite(y)), n
+        print(f"{'fft_%d' % n:42s}\n    {sha(X)} {sha(y)}")
+    for b in (48, 512):
+        cc = capi.ConvCtx(ctx, b)
+        fa = capi.ConvFilter(cc, rng.uniform(-0.1, 0.1, 2 * b + 5).astype(np.float32))
+        fb = capi.ConvFilter(cc, rng.uniform(-0.1, 0.1, b).astype(np.float32))
+        conv = capi.BlockConvolver(cc, fa)
+        x = rng.uniform(-1.0, 1.0, (9, b)).astype(np.float32)
+        outs = []
+        for i in range(9):  # (a crossfade, silence until the tail has run out, input again)
+            if i == 2:
+                conv.crossfade_filter(fb)
+            outs.append(conv.process(None if 4 <= i < 8 else x[i]))
+        assert np.all(np.isfinite(outs)), b
+        print(f"{'block_convolver_%d' % b:42s}\n    {sha(np.stack(outs))}")
+    for b in (64, 4096):
+        taps = rng.uniform(-0.1, 0.1, (2, 3, b + 7)).astype(np.float32)
+        taps[1, 2] = 0.0
+        fm = capi.FirMatrix(ctx, taps, b, max_blocks=3)
+        x = rng.uniform(-1.0, 1.0, (3, 3 * b)).astype(np.float32)
+        y1, y2 = fm.process(x), fm.process(x[:, :b])
+        fm.close()
+        assert np.all(np.isfinite(y1)) and np.all(np.isfinite(y2)), b
+        print(f"{'firmix_%d' % b:42s}\n    {sha(y1)} {sha(y2)}")
+    ctx.close()
+
+
 if __name__ == "__main__":
-    for name, curves, opts, kw in CASES:
-        run(name, curves, opts, **kw)
-    print(f"{len(CASES)} cases")
+    if sys.argv[1:] == ["k2"]:
+        for name, block, opts, kw in K2_CASES:
+            run_k2(name, block, opts, **kw)
+        run_transforms()
+        print(f"{len(K2_CASES)} renders, the transforms")
+    else:
+        for name, curves, opts, kw in CASES:
+            run(name, curves, opts, **kw)
+        print(f"{len(CASES)} cases")
