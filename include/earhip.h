@@ -1144,6 +1144,80 @@ int earhip_render_attach_limiter(earhip_render *r, earhip_limiter *lim, float *s
                                  size_t sink_capacity);
 int earhip_render_limiter_position(earhip_render *r, size_t *samples);
 
+/* ------------------------------------------------------------------------
+ * (O) Biquad filter matrix — recursive filters on the output bus, on the device: bass management, loudspeaker or room EQ,
+ * Linkwitz-Riley crossovers.  libear has no counterpart.  The FIR matrix of group M can stand in for these only with thousands
+ * of taps (a 4th-order crossover at 80 Hz has pole radius 0.993); this stage runs the recursion itself, in parallel along time.
+ *
+ * The operation, exactly (a caller can reproduce it).  n_in input rows, n_out output rows, a list of R routes; route r is
+ * (in_r, out_r, gain_r, S_r sections, coefficients [S_r][5] = b0 b1 b2 a1 a2).  One sample clock n since create / reset; every
+ * state is zero before it starts.  Per route, float64 arithmetic on the float32 samples in transposed direct form II, every
+ * multiply-add fused (ONE rounding), the sections in list order, x the input sample as a double, per section
+ *     y = fma(b0, x, s1);   s1 = fma(-a1, y, fma(b1, x, s2));   s2 = fma(-a2, y, b2 * x);   the next section's x = y,
+ * and z_r[n] = the last section's y.  S_r = 0 is a pure gain route: z_r[n] = (double)x[n].
+ *     out_k[n] = (float)(sum over the routes with out_r = k, in ASCENDING LIST INDEX, of gain_r z_r[n]):
+ * the sum is float64, starts from +0.0, takes one fused multiply-add per route, acc = fma(gain_r, z_r[n], acc), and is
+ * rounded to float32 once.  An output without a route is written as +0.0.
+ * STABILITY is checked at create: every section needs |a2| < 1 and |a1| < 1 + a2; all coefficients and gains must be finite.
+ * DETERMINISM: the same calls give the same bits (no floating-point atomics, fixed orders everywhere).  The stage is NOT
+ * bit-identical under different cuttings of the stream into calls: the time axis of a call is cut into chunks of
+ * earhip_iir_info's length on the clock's grid, every chunk's start state is carried across the chunks before it with powers of
+ * the cascade's transition matrix, and those propagated states round differently from the sample-by-sample recursion and
+ * differently for different cuts.  What is promised under any cutting is accuracy:
+ *     |out - ref| <= 2^-24 |ref| + 1e-9 (the peak of |ref| over that output row),
+ * ref the float64 recursion above run sample by sample (scipy.signal.sosfilt per route, then the ordered sum): the first term is
+ * the one rounding to float32.
+ * NON-FINITE INPUT: from the first non-finite sample of an input row on, the outputs fed by routes that read that row are
+ * unspecified non-finite values until earhip_iir_reset.  Earlier samples are untouched, and so are outputs fed only by other
+ * rows.  There are no guard passes.
+ *
+ * Out of scope: per-route delays, changing coefficients or gains while running, crossfaded sets, float32 state, a multi-GPU
+ * stage (run it on the rank that owns whole channels, as the meter of group L), attaching the stage to a renderer as groups L, M
+ * and N attach (feed it the rows a process call wrote: earhip_iir_process_device on the same context follows the call's kernels
+ * on the stream).
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_iir earhip_iir;
+typedef struct earhip_iir_route {
+  int in;               /* [0, n_in) */
+  int out;              /* [0, n_out) */
+  double gain;          /* finite */
+  int n_sections;       /* S in [0, 8] */
+  double coeffs[8][5];  /* the first S rows: b0 b1 b2 a1 a2 (a0 = 1) */
+} earhip_iir_route;
+typedef struct earhip_iir_config {
+  int n_in;                       /* [1, 64] */
+  int n_out;                      /* [1, 64] */
+  int n_routes;                   /* R in [1, 512] */
+  const earhip_iir_route *routes; /* [R]; copied */
+  size_t max_samples;             /* >= 1: the longest process call */
+} earhip_iir_config;
+/* Everything is made here — the routes' states (2 S doubles each, double-buffered: a call reads one and writes the other), the
+ * powers of the transition matrices (in long double, rounded once) and the chunk states [routes][chunks of max_samples][2 S]:
+ * a process call allocates nothing and synchronises nothing.  Anything outside the limits above is EARHIP_INVALID_ARGUMENT. */
+int earhip_iir_create(earhip_ctx *ctx, const earhip_iir_config *config, earhip_iir **out);
+int earhip_iir_destroy(earhip_iir *iir);
+int earhip_iir_reset(earhip_iir *iir); /* states and clock to zero */
+/* info: [0] the chunk length Lc, [1] chunks per scan group, [2] scan groups chained per workgroup (a launch holds at most
+ * [1] * [2] + 2 chunks; longer calls run as several launches), [3] routes, [4] the largest state size 2 S, [5] scratch bytes */
+int earhip_iir_info(const earhip_iir *iir, int info[6]);
+/* planar float32 rows in device memory: input i at in_dev + i * in_stride, output k at out_dev + k * out_stride, nsamples each,
+ * any nsamples >= 0; the rows of in and out must not overlap.  nsamples > max_samples is EARHIP_INVALID_ARGUMENT and nothing
+ * is consumed.  Enqueues on the context's stream, allocates nothing, does not synchronise. */
+int earhip_iir_process_device(earhip_iir *iir, size_t nsamples, const float *in_dev, size_t in_stride, float *out_dev,
+                              size_t out_stride);
+/* host rows in[n_in], out[n_out]: H2D + the above + D2H; synchronises */
+int earhip_iir_process(earhip_iir *iir, size_t nsamples, const float *const *in, float *const *out);
+/* A pure host function, no context and no device (like the host forms of groups K and L): one section b0 b1 b2 a1 a2 of the
+ * RBJ audio EQ cookbook, normalised by a0.  q is the cookbook's Q for every kind (the shelves' too); gain_db is used by the
+ * peaking and shelving kinds only.  Two Q = 1/sqrt(2) sections of one kind make a Linkwitz-Riley 4th-order filter.  f0 outside
+ * (0, sample_rate / 2), q <= 0, an unknown kind or a non-finite argument is EARHIP_INVALID_ARGUMENT. */
+#define EARHIP_IIR_LOWPASS 0
+#define EARHIP_IIR_HIGHPASS 1
+#define EARHIP_IIR_PEAKING 2
+#define EARHIP_IIR_LOW_SHELF 3
+#define EARHIP_IIR_HIGH_SHELF 4
+int earhip_iir_design(int kind, double sample_rate, double f0, double q, double gain_db, double out[5]);
+
 #ifdef __cplusplus
 }
 #endif

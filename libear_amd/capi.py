@@ -1313,3 +1313,91 @@ class Limiter:
         if self.h:
             load().earhip_limiter_destroy(self.h)
             self.h = C.c_void_p()
+
+
+# (O) biquad filter matrix
+
+IIR_KINDS = {"lowpass": 0, "highpass": 1, "peaking": 2, "low_shelf": 3, "high_shelf": 4}
+
+
+class _IirRoute(C.Structure):
+    _fields_ = [("in_", C.c_int), ("out", C.c_int), ("gain", C.c_double), ("n_sections", C.c_int),
+                ("coeffs", (C.c_double * 5) * 8)]
+
+
+class _IirConfig(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("n_routes", C.c_int), ("routes", C.POINTER(_IirRoute)),
+                ("max_samples", C.c_size_t)]
+
+
+def iir_design(kind, sample_rate, f0, q=2.0 ** -0.5, gain_db=0.0):
+    """one RBJ cookbook section [b0 b1 b2 a1 a2] (float64); kind: a name of IIR_KINDS or its number.  A pure host function"""
+    out = np.zeros(5, np.float64)
+    code = IIR_KINDS.get(kind, -1) if isinstance(kind, str) else int(kind)
+    load().earhip_iir_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    check(load().earhip_iir_design(code, float(sample_rate), float(f0), float(q), float(gain_db), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class IirBank:
+    """(O) a matrix of biquad cascades: routes = [(in, out, gain, sections)], sections [S][5] = b0 b1 b2 a1 a2 with S in
+    [0, 8] (S = 0, or None: a pure gain route); out_k = the sum of gain * filtered input over the routes into k."""
+
+    def __init__(self, ctx, n_in, n_out, routes, max_samples=48000):
+        for name, v in (("n_in", n_in), ("n_out", n_out), ("max_samples", max_samples)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise InvalidArgument(INVALID_ARGUMENT, f"{name} must be an integer")
+        if int(max_samples) < 1:
+            raise InvalidArgument(INVALID_ARGUMENT, "max_samples must be >= 1")
+        routes = list(routes)
+        arr = (_IirRoute * max(len(routes), 1))()
+        for i, route in enumerate(routes):
+            if len(route) != 4:
+                raise InvalidArgument(INVALID_ARGUMENT, "a route is (in, out, gain, sections)")
+            rin, rout, gain, sections = route
+            for name, v in (("in", rin), ("out", rout)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                    raise InvalidArgument(INVALID_ARGUMENT, f"a route's {name} must be an integer")
+            sec = np.zeros((0, 5)) if sections is None else _f64(sections)
+            if sec.size == 0:
+                sec = sec.reshape(0, 5)
+            if sec.ndim != 2 or sec.shape[1] != 5:
+                raise InvalidArgument(INVALID_ARGUMENT, "a route's sections must be [S][5]")
+            arr[i].in_, arr[i].out, arr[i].gain, arr[i].n_sections = int(rin), int(rout), float(gain), sec.shape[0]
+            for s in range(min(sec.shape[0], 8)):
+                for j in range(5):
+                    arr[i].coeffs[s][j] = sec[s, j]
+        self.ctx, self.n_in, self.n_out = ctx, int(n_in), int(n_out)
+        self.max_samples = int(max_samples)
+        cfg = _IirConfig(self.n_in, self.n_out, len(routes), arr, self.max_samples)
+        self.h = C.c_void_p()
+        check(load().earhip_iir_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(self.h)))
+
+    def info(self):
+        """dict: chunk (Lc), scan_lanes, scan_groups, routes, max_state, scratch_bytes"""
+        v = (C.c_int * 6)()
+        check(load().earhip_iir_info(self.h, v))
+        return dict(zip(("chunk", "scan_lanes", "scan_groups", "routes", "max_state", "scratch_bytes"), list(v)))
+
+    def process(self, x):
+        """x [n_in][n] host array, any n -> [n_out][n]"""
+        x = _f32(x)
+        if x.ndim != 2 or x.shape[0] != self.n_in:
+            raise InvalidArgument(INVALID_ARGUMENT, "x must be [n_in][n]")
+        n = x.shape[1]
+        out = np.empty((self.n_out, n), np.float32)
+        check(load().earhip_iir_process(self.h, C.c_size_t(n), _chan_ptrs(x), _chan_ptrs(out)))
+        return out
+
+    def process_device(self, nsamples, in_ptr, in_stride, out_ptr, out_stride):
+        """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); enqueues on the context's stream"""
+        check(load().earhip_iir_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                               C.c_void_p(out_ptr), C.c_size_t(out_stride)))
+
+    def reset(self):
+        check(load().earhip_iir_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_iir_destroy(self.h)
+            self.h = C.c_void_p()
