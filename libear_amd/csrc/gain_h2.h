@@ -54,54 +54,174 @@
 
 #include "gain_kernels.h"
 #include "gain_mfma.h"
+#include "gain_split.h"
 
 namespace earhip {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kSplitTile = 256;   // samples per workgroup tile of the 4-wave kernel (descriptor tile)
-constexpr int kSplitChunk = 32;   // objects per MFMA (k)
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-
-// two floats -> packed f16 pair, round to nearest even (v_cvt_pk_f16_f32)
-__device__ __forceinline__ uint32_t pack_f16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
+// ---- the per-chunk code of the grid kernel, shared by its two forms (k_gain_mix_h2 below; k_gain_mix_h2_t1, gain_h2_t1.h) ----
+// What a WAVE converts for a chunk: the gains of NQ objects.  Their descriptors are wave-uniform: scalar loads (requested
+// one chunk ahead), scalar row arithmetic, and the gain rows come in as (scalar row pointer) + (the lane's column).
+// (read through the constant address space: the compiler cannot prove that nothing in the kernel writes the descriptors —
+// K0 wrote them, this kernel only reads — and would otherwise use vector loads and vector row arithmetic for these uniform
+// values)
+typedef const SegDesc __attribute__((address_space(4))) *ConstDesc;
+template <int NQ>
+struct ChunkDesc {
+  SegDesc d[NQ];
+};
+template <int NQ>
+struct ChunkCoef {
+  float p0[NQ], scale[NQ];
+};
+// the descriptors of objects m0 .. m0 + NQ - 1 in a workgroup tile (dtile: the tile's row of P.desc)
+template <int NQ>
+__device__ __forceinline__ ChunkDesc<NQ> load_desc(const SegDesc *dtile, int m0) {
+  ConstDesc dp = (ConstDesc)(dtile + m0);
+  ChunkDesc<NQ> D;
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    D.d[q].row = dp[q].row;
+    D.d[q].d0 = dp[q].d0;
+    D.d[q].scale = dp[q].scale;
+    D.d[q].info = dp[q].info;
+  }
+  return D;
 }
-__device__ __forceinline__ float f16_lo(uint32_t u) { return (float)__builtin_bit_cast(f16x2_t, u)[0]; }
-__device__ __forceinline__ float f16_hi(uint32_t u) { return (float)__builtin_bit_cast(f16x2_t, u)[1]; }
-// v - (the low / high half of u as a float): the exact residual of a split in ONE instruction (v_fma_mix_f32 converts its
-// f16 operand on the way in; the conversion alone, v_cvt_f32_f16, issues at the same 4.3 cycles, and the subtraction came on
-// top — profiles/r05_valu_issue_rates.txt)
-// (written out: the compiler turns fma(half, -1, v) back into a conversion and a subtraction)
-__device__ __forceinline__ float sub_f16_lo(float v, uint32_t u) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(u), "v"(v));
-  return r;
+// requests the two gain rows of each of the wave's objects m0 .. m0 + NQ - 1 (the lane's column bcol_e of them: S, E) and makes
+// their line's coefficients.  m_new: the chunk's first object that the previous chunk has not covered already (the last
+// chunk of a tile is moved back to end at the last object); TILE: samples of a workgroup tile
+template <int NQ, int TILE>
+__device__ __forceinline__ void load_gains(const ChunkDesc<NQ> &R, int m0, int m_new, int zero_row, const float *__restrict__ gain,
+                                           unsigned rowlen, unsigned bcol_e, ChunkCoef<NQ> &D, float (&S)[NQ], float (&E)[NQ]) {
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const SegDesc d = R.d[q];
+    // objects the previous chunk already covered (last chunk moved back) and objects with
+    // curve points inside the tile (slow path) get the all-zero row
+    const bool valid = m0 + q >= m_new && !(d.info & (kSegMulti | kSegQuiet));
+    const unsigned rs = (unsigned)(valid ? d.row : zero_row);
+    // (a select between two uniform values: "rs + (ramp ? 1 : 0)" turns the uniform condition into a lane value and
+    // the row products into eight quarter-rate vector multiplies per chunk)
+    const unsigned re = (valid && (d.info & kSegRamp)) ? (unsigned)d.row + 1u : rs;
+    // gain_interpolator.hpp:272 at the workgroup tile's CENTRE sample (constant segments: scale = 0): the line is anchored
+    // there — (s - c) runs over +-half a tile, not over a whole one: half the weight on the slope totals' rounding
+    D.p0[q] = d.scale != 0.0f ? (float)(d.d0 + TILE / 2) * d.scale : 0.0f;
+    D.scale[q] = d.scale;             // constant segments: scale = 0, d0 = 0
+    const float *rps = gain + (size_t)rs * rowlen, *rpe = gain + (size_t)re * rowlen;
+    S[q] = rps[bcol_e];
+    E[q] = rpe[bcol_e];
+  }
 }
-__device__ __forceinline__ float sub_f16_hi(float v, uint32_t u) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(u), "v"(v));
-  return r;
+// B0 (gain at the tile's centre, part 0) or B1 (slope, part 1) of the wave's NQ objects, scaled (g_scale: the lane's column's)
+// and split -> LDS at f, the lane's entry of the fragment's high pieces (k = 8 kgw + 2 i + j of the fragment entry of lane
+// 16 kgw + column; the low pieces one fragment further, wide mode's h 2^-11 two)
+template <int NQ, bool WIDE>
+__device__ __forceinline__ void store_b(const ChunkCoef<NQ> &D, const float (&S)[NQ], const float (&E)[NQ], float g_scale, u32x4 *f,
+                                        int w, int part) {
+  uint32_t h[NQ / 2], l[NQ / 2], hs[NQ / 2];
+#pragma unroll
+  for (int i = 0; i < NQ / 2; i++) {
+    float v[2];
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const int q = 2 * i + j;
+      v[j] = (part == 0 ? __builtin_fmaf(1.0f - D.p0[q], S[q], D.p0[q] * E[q]) : D.scale[q] * (E[q] - S[q])) *
+             g_scale;
+    }
+    const uint32_t H = pack_f16(v[0], v[1]);
+    h[i] = H;
+    l[i] = pack_f16(sub_f16_lo(v[0], H), sub_f16_hi(v[1], H));  // residuals: exact in fp32
+    hs[i] = WIDE ? scale_f16x2_down(H) : 0u;                // h 2^-11: the partner of the inputs' scaled low piece
+  }
+  if constexpr (NQ == 8) {
+    f[0] = u32x4{h[0], h[1], h[2], h[3]};
+    f[64] = u32x4{l[0], l[1], l[2], l[3]};
+    if constexpr (WIDE) f[128] = u32x4{hs[0], hs[1], hs[2], hs[3]};
+  } else {  // half an entry: words 2 (w & 1), + 1
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 *g = reinterpret_cast<u32x2 *>(f) + (w & 1);
+    g[0] = u32x2{h[0], h[1]};
+    g[128] = u32x2{l[0], l[1]};
+    if constexpr (WIDE) g[256] = u32x2{hs[0], hs[1]};
+  }
+}
+// The MFMAs of a chunk: A fragments ah / al (split_inputs), B fragments in bf (= bfrag[buf]: {B0, B1} x column tiles x {h, l,
+// h 2^-11}), into the totals.  2*NCT blocks (column tile ct = blk >> 1, operand blk & 1: B0 / B1) of 12 MFMAs: three
+// partial products per operand pair, smallest first.  MFMA and VALU instructions do not overlap except for one VALU
+// instruction directly behind an MFMA (tools/experiments/coissue2.hip), so what else the chunk has to do is woven between
+// the MFMAs:
+//   request_x(q0, n)  the inputs q0 .. q0 + n - 1 of the chunk after next go into the registers the split has just freed, a
+//                     few requests per MFMA block: requested in one burst, by all the workgroup's waves at once, they queue
+//                     up in the CU's address unit and the waves sit in their load instructions instead of issuing MFMAs;
+//   convert(part)     the conversion of the next chunk's gains (store_b), between the MFMAs of the last two blocks.
+template <int NCT, bool WIDE, typename RequestX, typename Convert>
+__device__ __forceinline__ void chunk_mfmas(const u32x4 (*bf)[64], int lane, const u32x4 (&ah)[kSplitRowTiles],
+                                            const u32x4 (&al)[kSplitRowTiles], f32x4 (&tot0)[kSplitRowTiles][NCT],
+                                            f32x4 (&tot1)[kSplitRowTiles][NCT], RequestX request_x, Convert convert) {
+  constexpr int NRT = kSplitRowTiles;
+  constexpr int XB = 2 * NCT >= 4 ? 4 : 2 * NCT;  // blocks that carry input requests
+  constexpr int NBLK = 2 * NCT;
+  // (h, l) of a block are read one block ahead into alternating registers; wide mode reads the scaled high piece
+  // as its block starts, behind the four MFMAs that do not need it (one register set: the kernel sits at the
+  // register limit)
+  u32x4 b[2][2], b2;
+  auto load_b = [&](int blk, u32x4 (&bb)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) bb[q] = bf[((blk & 1) * NCT + (blk >> 1)) * 3 + q][lane];
+  };
+  load_b(0, b[0]);
+  __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // (block 0's reads; each block below places the NEXT block's)
+#pragma unroll
+  for (int blk = 0; blk < NBLK; blk++) {
+    u32x4(&bc)[2] = b[blk & 1];
+    const int ct = blk >> 1;
+    if constexpr (WIDE) b2 = bf[((blk & 1) * NCT + (blk >> 1)) * 3 + 2][lane];
+    if (blk + 1 < NBLK) load_b(blk + 1, b[(blk + 1) & 1]);
+    // (the two small products first, the large one last; wide mode: the one whose operand is read last second)
+    f32x4(&tt)[NRT][NCT] = (blk & 1) == 0 ? tot0 : tot1;
+    if constexpr (WIDE) {
+#pragma unroll
+      for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[1], tt[r][ct]);
+#pragma unroll
+      for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(al[r], b2, tt[r][ct]);
+    } else {
+#pragma unroll
+      for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(al[r], bc[0], tt[r][ct]);
+#pragma unroll
+      for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[1], tt[r][ct]);
+    }
+#pragma unroll
+    for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[0], tt[r][ct]);
+    if (blk < XB) request_x(blk * (8 / XB), 8 / XB);
+    const bool conv0 = blk == NBLK - 2, conv1 = blk == NBLK - 1;
+    if (conv0) convert(0);  // next chunk's gains (after the last chunk:
+    if (conv1) convert(1);  // written, never read)
+    // issue order: the LDS reads first, then every MFMA followed by VALU instructions
+    if constexpr (WIDE) {
+      if (blk + 1 < NBLK) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+      else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    } else {
+      if (blk + 1 < NBLK) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    }
+    if (conv0 || conv1) {
+#pragma unroll
+      for (int k = 0; k < 12; k++) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
+      }
+    } else if (blk < XB) {
+#pragma unroll
+      for (int k = 0; k < 8 / XB; k++) {  // MFMAs, then one request (address arithmetic + load)
+        __builtin_amdgcn_sched_group_barrier(0x008, 12 / (8 / XB), 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      }
+    } else {
+      __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+    }
+  }
 }
 
-// Wide mode: the low piece of an input is kept as (residual x 2^11) and multiplied with (h x 2^-11) of the gain —
-// both exact scalings, the same product — so that it is a normal f16 over 21 binades below the level the prescale
-// aims at instead of 11 (measured relative RMS of the products: 6.5e-8 down to 2^-18, 1.4e-7 at 2^-20, 5e-7 at
-// 2^-22; with the plain residual 2.5e-7 at 2^-10 and 1e-6 at 2^-12).
-constexpr float kLowPieceScale = 2048.0f;
-__device__ __forceinline__ uint32_t scale_f16x2_down(uint32_t h) {  // both halves x 2^-11 (exact unless subnormal)
-  const f16x2_t k = {(_Float16)0.00048828125f, (_Float16)0.00048828125f};
-  return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2_t, h) * k);
-}
-
-__device__ __forceinline__ f32x4 mfma_f16(const u32x4 &a, const u32x4 &b, const f32x4 &c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
-                                                0, 0, 0);
-}
 
 // P.ntiles / P.desc refer to WORKGROUP tiles of kSplitTile samples.  x_scale: an exact power of two (see
 // above); gcol: [row] per-COLUMN gain scales, powers of two that put the largest gain a column ever gets at 2^14
@@ -135,7 +255,7 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
   __shared__ u32x4 bfrag[2][NFRAG + 6][64];  // + 6 never-read fragments: the lanes without a column write there
   // the wave's output tile of one column tile, [16 columns][64 samples (+ 4: bank spread)], on its way from the
   // D fragments (a lane: one column, 16-byte pieces 64 bytes apart) to stores of whole 256-byte rows
-  constexpr int OP = TS + 4;
+  constexpr int OP = kSplitOutPitch;
   __shared__ __attribute__((aligned(16))) float otile[NW][16 * OP];
   __shared__ float inv_gcol[16 * NCT];  // 1 / the gain scale of the workgroup's columns: read at the END of a tile, where a
                                         // round trip to memory would stand in the open
@@ -169,16 +289,7 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     record_mode(P, wide_cur != nullptr);
   }
   if (level_cur) {
-    // input scale of THIS call from the level K0 probed: the largest magnitude seen, in [2^E, 2^(E+1)),
-    // goes to [2^7, 2^8) — peaks up to 256x the probed maximum stay inside the f16 range (beyond:
-    // exact fallback below), and samples down to 2^-11 of it keep a normal low piece (2^-22 relative;
-    // below that 2^-33 of the maximum, absolute).  Nothing seen (silence), absurd or non-finite
-    // levels: clamped.
-    const unsigned lv = *level_cur;
-    if (lv) {
-      const int E = max(-60, min(20, (int)(lv >> 23) - 127));
-      x_scale = __uint_as_float((unsigned)(127 + 7 - E) << 23);
-    }
+    x_scale = probed_input_scale(level_cur, x_scale);  // (beyond the f16 range at that scale: the exact redo below)
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *level_next = 0;
   }
   const int nparts = gridDim.y;
@@ -229,8 +340,6 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     for (int c = 0; c < NCT; c++) gsc[c] = sg ? gcol[col0 + c * 16 + li] : 1.0f;
     const int base = P.ps.off[m], n = P.ps.cnt[m];
     const float *row = P.in + (size_t)m * P.in_stride + tile_s0;
-    const bool is_b = kg & 1;
-    const bool slot0 = kg < 2;
     int k;
     if (khint >= 0) {
       k = min(khint, n);
@@ -238,36 +347,7 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     } else {
       k = upper_bound_time(P.ps.time + base, n, tile_t0);
     }
-    int cur = 0;
-    while (cur < tile_len) {
-      const SegDesc dk = describe_segment(P.ps, base, n, k, tile_t0, tile_t1);
-      const int r1 = min(seg_r1(dk.info), tile_len);
-      if (r1 > cur) {  // duplicate times make empty segments (steps)
-        const bool ramp = dk.info & kSegRamp;
-        float a[NRT], gv[NCT];
-#pragma unroll
-        for (int r = 0; r < NRT; r++) {
-          const int s = li * NRT + r;
-          const float x = row[min(s, tile_len - 1)];
-          const float p = (float)(dk.d0 + s) * dk.scale;  // gain_interpolator.hpp:272
-          float coef = ramp ? (is_b ? p : 1.0f - p) : (is_b ? 0.0f : 1.0f);
-          coef = (slot0 && s >= cur && s < r1) ? coef : 0.0f;
-          a[r] = (x * coef) * sx;
-        }
-        const int grow = dk.row + ((ramp && is_b && slot0) ? 1 : 0);
-        const float *gp = gain + (size_t)grow * rowlen + col0 + li;
-#pragma unroll
-        for (int c = 0; c < NCT; c++) gv[c] = gp[c * 16] * gsc[c];
-#pragma unroll
-        for (int r = 0; r < NRT; r++)
-#pragma unroll
-          for (int c = 0; c < NCT; c++)
-            tot0[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], gv[c], tot0[r][c], 0, 0, 0);
-        cur = r1;
-      }
-      if (!(dk.info & kSegMulti)) break;
-      k++;
-    }
+    exact_segments<NCT>(P.ps, base, n, k, row, tile_t0, tile_t1, tile_len, li, kg, gsc, sx, col0, tot0);
   };
 
   const int nobj = m_hi - m_lo;
@@ -279,58 +359,13 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     const int tile_s0 = tile_first(t), tile_len = tile_length(t);
     if (tile_len > 0) {
       const int ol = opaque_lane(), li = ol & 15, kg = ol >> 4;
-      // D fragment of row tile r: rows 4kg + e = samples 16kg + 4e + r: for fixed e the
-      // four row tiles are 4 consecutive samples.  (s - s0) of the rows: sample 64w + 16kg + 4e + r.
-      const float wf0 = (float)(w * TS + kg * 16 - (TS * NW) / 2);  // (s - c): the line is anchored at the tile's centre
+      // (s - c) of the lane's rows, samples 64w + 16kg + 4e + r: the line is anchored at the tile's centre
+      const float wf0 = (float)(w * TS + kg * 16 - (TS * NW) / 2);
       float inv_gc[NCT];  // inverse gain scale of the lane's column in each column tile (the D fragments' layout)
 #pragma unroll
       for (int c = 0; c < NCT; c++) inv_gc[c] = col_scaled ? inv_gcol[c * 16 + li] : 1.0f;
       float *op = P.out + (size_t)blockIdx.y * P.part_stride + tile_s0;
-      const bool whole = P.vec_ok && tile_len == TS;  // (wave-uniform)
-#pragma unroll
-      for (int c = 0; c < NCT; c++) {
-        if (whole) {
-          // Through wave-private LDS: written straight from the fragments, one store instruction covers 4 columns x
-          // 64 bytes in 16-byte pieces (64 scattered pieces per instruction: the stores of the 100 MB of buses cost a
-          // tenth of this kernel's time, a quarter at 256 objects); transposed, it covers 4 whole 256-byte rows.  The
-          // rows are written past the caches (K2 reads them once, much later: headline K1 0.437 -> 0.412 ms).
-          float *ot = otile[w];
-#pragma unroll
-          for (int e = 0; e < 4; e++) {
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < NRT; r++)
-              v[r] = (__builtin_fmaf(wf0 + (float)(4 * e + r), tot1[r][c][e], tot0[r][c][e]) * inv_x) * inv_gc[c];
-            *reinterpret_cast<f32x4 *>(ot + li * OP + kg * 16 + e * 4) = v;
-          }
-#pragma unroll
-          for (int j = 0; j < 4; j++) {  // lane: column 4 j + (lane >> 4), samples 4 (lane & 15) .. + 3
-            const int cl = 4 * j + kg, col = col0 + c * 16 + cl;
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(ot + cl * OP + li * 4);
-            if (col < P.ncols) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(op + (size_t)col * P.out_stride + li * 4));
-          }
-          continue;
-        }
-        const int col = col0 + c * 16 + li;
-        if (col >= P.ncols) continue;
-        float *o = op + (size_t)col * P.out_stride;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const int s = kg * 16 + e * 4;
-          f32x4 v;
-#pragma unroll
-          for (int r = 0; r < NRT; r++)
-            v[r] = (__builtin_fmaf(wf0 + (float)(4 * e + r), tot1[r][c][e], tot0[r][c][e]) * inv_x) * inv_gc[c];
-          if (P.vec_ok && s + 3 < tile_len) {
-            *reinterpret_cast<f32x4 *>(o + s) = v;
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-              if (s + i < tile_len) o[s + i] = v[i];
-          }
-        }
-      }
-
+      write_tile<NCT>(tot0, tot1, wf0, inv_x, inv_gc, otile[w], op, P.out_stride, col0, P.ncols, li, kg, tile_len, P.vec_ok);
     }
     clear_totals();
   };
@@ -385,82 +420,13 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
           x[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(bp + (size_t)q * rstride + xo));
     };
     auto load_x = [&](const Stage &st, bool live, f32x4 (&x)[8]) { load_x_part(st, live, x, 0, 8); };
-    // What this WAVE converts for chunk c: objects chunk_base + NQ w + q.  Their descriptors are
-    // wave-uniform: scalar loads (requested one chunk ahead), scalar row arithmetic, and the
-    // gain rows come in as (scalar row pointer) + (the lane's column).
-    // (read through the constant address space: the compiler cannot prove that nothing in the kernel
-    // writes the descriptors — K0 wrote them, this kernel only reads — and would otherwise use vector
-    // loads and vector row arithmetic for these uniform values)
-    typedef const SegDesc __attribute__((address_space(4))) *ConstDesc;
-    struct ChunkDesc {
-      SegDesc d[NQ];
+    // what this WAVE converts for a chunk: objects chunk_base + NQ w + q
+    auto stage_desc = [&](const Stage &st) { return load_desc<NQ>(P.desc + (size_t)st.tile * P.M, chunk_base(st.c) + w * NQ); };
+    auto chunk_gains = [&](const ChunkDesc<NQ> &R, int cc, ChunkCoef<NQ> &D, float (&S)[NQ], float (&E)[NQ]) {
+      load_gains<NQ, TS * NW>(R, chunk_base(cc) + w * NQ, m_lo + cc * CH, zero_row, gain, rowlen, bcol_e, D, S, E);
     };
-    auto load_desc = [&](const Stage &st) {
-      ConstDesc dp = (ConstDesc)(P.desc + (size_t)st.tile * P.M + chunk_base(st.c) + w * NQ);
-      ChunkDesc D;
-#pragma unroll
-      for (int q = 0; q < NQ; q++) {
-        D.d[q].row = dp[q].row;
-        D.d[q].d0 = dp[q].d0;
-        D.d[q].scale = dp[q].scale;
-        D.d[q].info = dp[q].info;
-      }
-      return D;
-    };
-    struct ChunkCoef {
-      float p0[NQ], scale[NQ];
-    };
-    auto load_gains = [&](const ChunkDesc &R, int cc, ChunkCoef &D, float (&S)[NQ], float (&E)[NQ]) {
-      const int m0 = chunk_base(cc) + w * NQ;
-#pragma unroll
-      for (int q = 0; q < NQ; q++) {
-        const SegDesc d = R.d[q];
-        // objects the previous chunk already covered (last chunk moved back) and objects with
-        // curve points inside the tile (slow path) get the all-zero row
-        const bool valid = m0 + q >= m_lo + cc * CH && !(d.info & (kSegMulti | kSegQuiet));
-        const unsigned rs = (unsigned)(valid ? d.row : zero_row);
-        // (a select between two uniform values: "rs + (ramp ? 1 : 0)" turns the uniform condition into a lane value and
-        // the row products into eight quarter-rate vector multiplies per chunk)
-        const unsigned re = (valid && (d.info & kSegRamp)) ? (unsigned)d.row + 1u : rs;
-        // gain_interpolator.hpp:272 at the workgroup tile's CENTRE sample (constant segments: scale = 0): the line is anchored
-        // there — (s - c) runs over +-half a tile, not over a whole one: half the weight on the slope totals' rounding
-        D.p0[q] = d.scale != 0.0f ? (float)(d.d0 + (TS * NW) / 2) * d.scale : 0.0f;
-        D.scale[q] = d.scale;             // constant segments: scale = 0, d0 = 0
-        const float *rps = gain + (size_t)rs * rowlen, *rpe = gain + (size_t)re * rowlen;
-        S[q] = rps[bcol_e];
-        E[q] = rpe[bcol_e];
-      }
-    };
-    // B0 (gain at the tile start, part 0) or B1 (slope, part 1) of the wave's NQ objects,
-    // scaled and split -> LDS (k = 8 kgw + 2 i + j of the fragment entry of lane 16 kgw + column)
-    auto store_b = [&](const ChunkCoef &D, const float (&S)[NQ], const float (&E)[NQ], int buf, int part) {
-      uint32_t h[NQ / 2], l[NQ / 2], hs[NQ / 2];
-#pragma unroll
-      for (int i = 0; i < NQ / 2; i++) {
-        float v[2];
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          const int q = 2 * i + j;
-          v[j] = (part == 0 ? __builtin_fmaf(1.0f - D.p0[q], S[q], D.p0[q] * E[q]) : D.scale[q] * (E[q] - S[q])) *
-                 g_scale;
-        }
-        const uint32_t H = pack_f16(v[0], v[1]);
-        h[i] = H;
-        l[i] = pack_f16(sub_f16_lo(v[0], H), sub_f16_hi(v[1], H));  // residuals: exact in fp32
-        hs[i] = WIDE ? scale_f16x2_down(H) : 0u;                // h 2^-11: the partner of the inputs' scaled low piece
-      }
-      u32x4 *f = &bfrag[buf][bfr][blane] + (part ? bfr1 * 64 : 0);
-      if constexpr (NQ == 8) {
-        f[0] = u32x4{h[0], h[1], h[2], h[3]};
-        f[64] = u32x4{l[0], l[1], l[2], l[3]};
-        if constexpr (WIDE) f[128] = u32x4{hs[0], hs[1], hs[2], hs[3]};
-      } else {  // half an entry: words 2 (w & 1), + 1
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        u32x2 *g = reinterpret_cast<u32x2 *>(f) + (w & 1);
-        g[0] = u32x2{h[0], h[1]};
-        g[128] = u32x2{l[0], l[1]};
-        if constexpr (WIDE) g[256] = u32x2{hs[0], hs[1]};
-      }
+    auto convert = [&](const ChunkCoef<NQ> &D, const float (&S)[NQ], const float (&E)[NQ], int buf, int part) {
+      store_b<NQ, WIDE>(D, S, E, g_scale, &bfrag[buf][bfr][blane] + (part ? bfr1 * 64 : 0), w, part);
     };
 
     // Inputs are requested TWO chunks ahead (a chunk is about 1 us of work for the wave, less
@@ -470,7 +436,7 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     // so per chunk the gain rows of the next chunk are requested BEFORE the inputs and
     // converted while those are in flight.
     f32x4 X0[8], X1[8];
-    ChunkDesc L;
+    ChunkDesc<NQ> L;
     Stage sa, sb, sc;
     sa.tile = tile_at(vb_c);
     sa.c = 0;
@@ -479,115 +445,30 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
     int ka = 0;  // stage A's tile is the workgroup's ka-th
     {
       float S[NQ], E[NQ];
-      ChunkCoef D;
-      L = load_desc(sa);
-      load_gains(L, 0, D, S, E);
+      ChunkCoef<NQ> D;
+      L = stage_desc(sa);
+      chunk_gains(L, 0, D, S, E);
       load_x(sa, true, X0);
       load_x(sb, left > 1, X1);
-      store_b(D, S, E, 0, 0);
-      store_b(D, S, E, 0, 1);
-      L = load_desc(sb);
+      convert(D, S, E, 0, 0);
+      convert(D, S, E, 0, 1);
+      L = stage_desc(sb);
     }
     // the chunk of stage A: inputs in xc, B fragments in bfrag[buf]
     auto chunk = [&](int buf, f32x4 (&xc)[8]) __attribute__((always_inline)) {
       __syncthreads();  // B fragments of this chunk are in bfrag[buf]; bfrag[buf^1] is free
       float S[NQ], E[NQ];
-      ChunkCoef D;
-      load_gains(L, sb.c, D, S, E);  // the next chunk (its descriptors were fetched one chunk ago)
-      L = load_desc(sc);
+      ChunkCoef<NQ> D;
+      chunk_gains(L, sb.c, D, S, E);  // the next chunk (its descriptors were fetched one chunk ago)
+      L = stage_desc(sc);
       __builtin_amdgcn_sched_barrier(0);  // every gain row is requested before any input (see above)
 
-      // A fragments: row tile r = sample 4*li + r of the 8 objects of this lane.  2 x 2
-      // blocks: an f16 pair packs two OBJECTS (q, q+1) of one row tile, the scaling and the
-      // exact residual subtractions pair two SAMPLES (r, r+1) of one object (neighbours in
-      // the loaded float4: packed arithmetic without operand moves).
-      u32x4 ah[NRT], al[NRT];
-#pragma unroll
-      for (int qp = 0; qp < 4; qp++)
-#pragma unroll
-        for (int rp = 0; rp < NRT; rp += 2) {
-          const f32x2 s0 = f32x2{xc[2 * qp][rp], xc[2 * qp][rp + 1]} * x_scale;          // object 2qp
-          const f32x2 s1 = f32x2{xc[2 * qp + 1][rp], xc[2 * qp + 1][rp + 1]} * x_scale;  // object 2qp+1
-          const uint32_t H0 = pack_f16(s0[0], s1[0]), H1 = pack_f16(s0[1], s1[1]);
-          // residuals (exact); wide mode scales them by 2^11 before they are rounded to f16
-          constexpr float LOW = WIDE ? kLowPieceScale : 1.0f;
-          const f32x2 r0 = f32x2{sub_f16_lo(s0[0], H0), sub_f16_lo(s0[1], H1)} * LOW;
-          const f32x2 r1 = f32x2{sub_f16_hi(s1[0], H0), sub_f16_hi(s1[1], H1)} * LOW;
-          ah[rp][qp] = H0;
-          ah[rp + 1][qp] = H1;
-          al[rp][qp] = pack_f16(r0[0], r1[0]);
-          al[rp + 1][qp] = pack_f16(r0[1], r1[1]);
-        }
-      // The inputs of chunk c+2 go into the registers just freed, a few requests per MFMA block:
-      // requested in one burst right here, by all the workgroup's waves at once, they queue up in the
-      // CU's address unit and the waves sit in their load instructions instead of issuing MFMAs.
-      constexpr int XB = 2 * NCT >= 4 ? 4 : 2 * NCT;  // blocks that carry input requests
-      // 2*NCT blocks (column tile ct = blk >> 1, operand blk & 1: B0 / B1) of 12 MFMAs: three
-      // partial products per operand pair, smallest first.  MFMA and VALU instructions do not
-      // overlap except for one VALU instruction directly behind an MFMA
-      // (tools/experiments/coissue2.hip), so the conversion of the next chunk's gains is
-      // woven between the MFMAs of blocks 0 and 1.
+      u32x4 ah[NRT], al[NRT];  // A fragments: the inputs' high and low pieces
+      split_inputs<WIDE>(xc, x_scale, ah, al);
       __builtin_amdgcn_sched_barrier(0);  // the splitting above stays above
-      constexpr int NBLK = 2 * NCT;
-      // (h, l) of a block are read one block ahead into alternating registers; wide mode reads the scaled high piece
-      // as its block starts, behind the four MFMAs that do not need it (one register set: the kernel sits at the
-      // register limit)
-      u32x4 b[2][2], b2;
-      auto load_b = [&](int blk, u32x4 (&bb)[2]) {
-#pragma unroll
-        for (int q = 0; q < 2; q++) bb[q] = bfrag[buf][((blk & 1) * NCT + (blk >> 1)) * 3 + q][lane];
-      };
-      load_b(0, b[0]);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // (block 0's reads; each block below places the NEXT block's)
-#pragma unroll
-      for (int blk = 0; blk < NBLK; blk++) {
-        u32x4(&bc)[2] = b[blk & 1];
-        const int ct = blk >> 1;
-        if constexpr (WIDE) b2 = bfrag[buf][((blk & 1) * NCT + (blk >> 1)) * 3 + 2][lane];
-        if (blk + 1 < NBLK) load_b(blk + 1, b[(blk + 1) & 1]);
-        // (the two small products first, the large one last; wide mode: the one whose operand is read last second)
-        f32x4(&tt)[NRT][NCT] = (blk & 1) == 0 ? tot0 : tot1;
-        if constexpr (WIDE) {
-#pragma unroll
-          for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[1], tt[r][ct]);
-#pragma unroll
-          for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(al[r], b2, tt[r][ct]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(al[r], bc[0], tt[r][ct]);
-#pragma unroll
-          for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[1], tt[r][ct]);
-        }
-#pragma unroll
-        for (int r = 0; r < NRT; r++) tt[r][ct] = mfma_f16(ah[r], bc[0], tt[r][ct]);
-        if (blk < XB) load_x_part(sc, left > 2, xc, blk * (8 / XB), 8 / XB);
-        const bool conv0 = blk == NBLK - 2, conv1 = blk == NBLK - 1;
-        if (conv0) store_b(D, S, E, buf ^ 1, 0);  // next chunk's gains (after the last chunk:
-        if (conv1) store_b(D, S, E, buf ^ 1, 1);  // written, never read)
-        // issue order: the LDS reads first, then every MFMA followed by VALU instructions
-        if constexpr (WIDE) {
-          if (blk + 1 < NBLK) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        } else {
-          if (blk + 1 < NBLK) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-        }
-        if (conv0 || conv1) {
-#pragma unroll
-          for (int k = 0; k < 12; k++) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-          }
-        } else if (blk < XB) {
-#pragma unroll
-          for (int k = 0; k < 8 / XB; k++) {  // MFMAs, then one request (address arithmetic + load)
-            __builtin_amdgcn_sched_group_barrier(0x008, 12 / (8 / XB), 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          }
-        } else {
-          __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
-        }
-      }
+      chunk_mfmas<NCT, WIDE>(bfrag[buf], lane, ah, al, tot0, tot1,
+                             [&](int q0, int n) __attribute__((always_inline)) { load_x_part(sc, left > 2, xc, q0, n); },
+                             [&](int part) __attribute__((always_inline)) { convert(D, S, E, buf ^ 1, part); });
     };
     // what follows a chunk: the end of its tile (exact-path objects, the check of the totals, the stores), and
     // the pipeline moves on
@@ -616,14 +497,7 @@ k_gain_mix_h2(GainMixParams P, int zero_row, float x_scale, const float *__restr
         }
         // an input beyond the f16 range (or not finite) shows as non-finite totals: the wave's tile is redone
         // exactly, unscaled, behind the chunk loop
-        bool bad = false;
-#pragma unroll
-        for (int r = 0; r < NRT; r++)
-#pragma unroll
-          for (int c = 0; c < NCT; c++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) bad |= !(__builtin_fabsf(tot0[r][c][e]) < INFINITY) || !(__builtin_fabsf(tot1[r][c][e]) < INFINITY);
-        if (__ballot(bad)) {
+        if (__ballot(totals_not_finite<NCT>(tot0, tot1))) {
           if (lane == 0) redo_tiles[w] |= 1ull << ka;
           clear_totals();
         } else {

@@ -537,9 +537,9 @@ __device__ __forceinline__ uint32_t h2_bits(hg_h2 h) { return __builtin_bit_cast
 // two sets of inputs do not fit the register file beside the 96 accumulators, the operand pieces the kinks need, and
 // the rows on their way).  The rows go through a wave-private piece of LDS, a chunk's worth at a time: a step first
 // turns the rows staged a step ago into the operand fragments of the NEXT chunk (all three sets; fragments alternate
-// between two buffers), then stages the rows that have arrived meanwhile.  The scaled high piece (h 2^-11, gain_h2.h)
+// between two buffers), then stages the rows that have arrived meanwhile.  The scaled high piece (h 2^-11, gain_split.h)
 // is made from h where it is used.
-// WIDE: the low pieces of the inputs scaled by 2^11 (gain_h2.h), their partner made from the gains' high pieces as they are
+// WIDE: the low pieces of the inputs scaled by 2^11 (gain_split.h), their partner made from the gains' high pieces as they are
 // read; the plain form saves those multiplies (16 + 4 per block of 12 MFMAs).  Both forms are in the kernel; the probe's word
 // (wide_cur: bit 0 of the gate word, k_hinge_gate) picks at run time.
 template <int NCT, int NW>
@@ -556,7 +556,7 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
   constexpr int KS = NW / 2;         // kink sets: one (4 waves: 256-sample tiles) or two (8 waves: 512) on either side of the centre
   constexpr int NR = 2 + KS;         // rows a slot asks for: its kink rows and the two gain rows of its line
   constexpr int RING = 4;
-  constexpr int OP = TS + 4;
+  constexpr int OP = kSplitOutPitch;
   // fragments (1 KB each: 64 lanes x 8 f16), two sets (even / odd chunks) of: the line {B0, B1} x column tiles x {h, l}, the
   // kink sets (column tiles x {h, l} each)
   constexpr int FL = 4 * NCT, FH = 2 * NCT, FSET = FL + KS * FH, NFRAGS = 2 * FSET;
@@ -594,12 +594,8 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
   // what does not shows as non-finite totals: exact redo below)
   if (threadIdx.x < 16 * NCT) inv_gcol[threadIdx.x] = 2.0f / gcol[blockIdx.z * 16 * NCT + threadIdx.x];
   __syncthreads();
-  if (level_cur) {  // input scale of THIS call from the level K0 probed (gain_h2.h)
-    const unsigned lv = *level_cur;
-    if (lv) {
-      const int E = max(-60, min(20, (int)(lv >> 23) - 127));
-      x_scale = __uint_as_float((unsigned)(127 + 7 - E) << 23);
-    }
+  if (level_cur) {
+    x_scale = probed_input_scale(level_cur, x_scale);
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
       *level_next = 0;
       if (wide_next) *wide_next = 0u;
@@ -642,39 +638,8 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
     const ObjHdr hd = P.ps.hdr[m];
     const int base = hd.off, n = hd.cnt;
     const float *row = P.in + (size_t)m * P.in_stride + tile_s0;
-    const bool is_b = kg & 1;
-    const bool slot0 = kg < 2;
-    int k = upper_bound_rec_window(P.ps.rec + base, n, hd.first, hd.last, tile_t0);
-    int cur = 0;
-    while (cur < tile_len) {
-      const SegDesc dk = describe_segment(P.ps, base, n, k, tile_t0, tile_t1);
-      const int r1 = min(seg_r1(dk.info), tile_len);
-      if (r1 > cur) {
-        const bool ramp = dk.info & kSegRamp;
-        float a[NRT], gv[NCT];
-#pragma unroll
-        for (int r = 0; r < NRT; r++) {
-          const int s = li * NRT + r;
-          const float x = row[min(s, tile_len - 1)];
-          const float p = (float)(dk.d0 + s) * dk.scale;  // gain_interpolator.hpp:272
-          float coef = ramp ? (is_b ? p : 1.0f - p) : (is_b ? 0.0f : 1.0f);
-          coef = (slot0 && s >= cur && s < r1) ? coef : 0.0f;
-          a[r] = (x * coef) * sx;
-        }
-        const int grow = dk.row + ((ramp && is_b && slot0) ? 1 : 0);
-        const float *gp = gain + (size_t)grow * rowlen + col0 + li;
-#pragma unroll
-        for (int c = 0; c < NCT; c++) gv[c] = gp[c * 16] * gsc[c];
-#pragma unroll
-        for (int r = 0; r < NRT; r++)
-#pragma unroll
-          for (int c = 0; c < NCT; c++)
-            tot0[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], gv[c], tot0[r][c], 0, 0, 0);
-        cur = r1;
-      }
-      if (!(dk.info & kSegMulti)) break;
-      k++;
-    }
+    const int k = upper_bound_rec_window(P.ps.rec + base, n, hd.first, hd.last, tile_t0);
+    exact_segments<NCT>(P.ps, base, n, k, row, tile_t0, tile_t1, tile_len, li, kg, gsc, sx, col0, tot0);
   };
 
   float inv_x = 1.0f / x_scale;  // exact: a power of two
@@ -907,21 +872,7 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
         if (w == 0) ring_load(L, c + RD);  // (stored behind the line's MFMAs)
 #endif
         __builtin_amdgcn_sched_barrier(0);  // every gain row is requested before any input
-        // operand split of the inputs (gain_h2.h, wide form): 2 x 2 blocks, an f16 pair packs two SLOTS of one row tile
-#pragma unroll
-        for (int qp = 0; qp < 4; qp++)
-#pragma unroll
-          for (int rp = 0; rp < NRT; rp += 2) {
-            const f32x2 s0 = f32x2{X[2 * qp][rp], X[2 * qp][rp + 1]} * x_scale;
-            const f32x2 s1 = f32x2{X[2 * qp + 1][rp], X[2 * qp + 1][rp + 1]} * x_scale;
-            const uint32_t H0 = pack_f16(s0[0], s1[0]), H1 = pack_f16(s0[1], s1[1]);
-            const f32x2 r0 = f32x2{sub_f16_lo(s0[0], H0), sub_f16_lo(s0[1], H1)} * LOW;
-            const f32x2 r1 = f32x2{sub_f16_hi(s1[0], H0), sub_f16_hi(s1[1], H1)} * LOW;
-            ah[rp][qp] = H0;
-            ah[rp + 1][qp] = H1;
-            al[rp][qp] = pack_f16(r0[0], r1[0]);
-            al[rp + 1][qp] = pack_f16(r0[1], r1[1]);
-          }
+        split_inputs<WIDE>(X, x_scale, ah, al);  // the inputs' high and low pieces
         __builtin_amdgcn_sched_barrier(0);  // the splitting above stays above
         EARHIP_HG_MARK(1);
         // ======== the line: 2 NCT blocks of 12 MFMAs (operand B0 / B1 of a column tile: the three partial products, small
@@ -1108,14 +1059,7 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
       for (int i = 0; i < cnt[1]; i++) single_object(ovf[i], x_scale, true);
     }
     // an operand beyond the f16 range (or not finite) shows as non-finite totals: redo the wave's tile exactly, unscaled
-    bool bad = false;
-#pragma unroll
-    for (int r = 0; r < NRT; r++)
-#pragma unroll
-      for (int c = 0; c < NCT; c++)
-#pragma unroll
-        for (int e = 0; e < 4; e++) bad |= !(__builtin_fabsf(tot0[r][c][e]) < INFINITY) || !(__builtin_fabsf(tot1[r][c][e]) < INFINITY);
-    if (__ballot(bad)) {
+    if (__ballot(totals_not_finite<NCT>(tot0, tot1))) {
       clear_totals();
       inv_x = 1.0f;
       col_scaled = false;
@@ -1144,53 +1088,14 @@ k_gain_mix_hg(GainMixParams P, HingeLists hl, float x_scale, const float *__rest
   }
 #endif
   if (tile_len <= 0) return;
-  // D fragment of row tile r: rows 4 kg + e = samples 16 kg + 4 e + r; (s - c) counts from the WORKGROUP tile's centre
-  // (where the line is anchored: LinEntry::p0)
+  // (s - c) of the lane's rows counts from the WORKGROUP tile's centre (where the line is anchored: LinEntry::p0)
   const float wf0 = (float)(wave_s0 + kg * 16 - T / 2);
   float inv_gc[NCT];
 #pragma unroll
   for (int c = 0; c < NCT; c++) inv_gc[c] = col_scaled ? inv_gcol[c * 16 + li] : 1.0f;
   float *op = P.out + (size_t)blockIdx.y * P.part_stride + tile_s0;
-  const bool whole = P.vec_ok && tile_len == TS;  // (wave-uniform)
   float *ot = reinterpret_cast<float *>(fmem) + w * 16 * OP;
-#pragma unroll
-  for (int c = 0; c < NCT; c++) {
-    if (whole) {  // transposed through wave-private LDS: whole 256-byte rows per store instruction (gain_h2.h)
-#pragma unroll
-      for (int e = 0; e < 4; e++) {
-        f32x4 v;
-#pragma unroll
-        for (int r = 0; r < NRT; r++)
-          v[r] = (__builtin_fmaf(wf0 + (float)(4 * e + r), tot1[r][c][e], tot0[r][c][e]) * inv_x) * inv_gc[c];
-        *reinterpret_cast<f32x4 *>(ot + li * OP + kg * 16 + e * 4) = v;
-      }
-#pragma unroll
-      for (int jn = 0; jn < 4; jn++) {
-        const int cl = 4 * jn + kg, col = col0 + c * 16 + cl;
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(ot + cl * OP + li * 4);
-        if (col < P.ncols) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(op + (size_t)col * P.out_stride + li * 4));
-      }
-      continue;
-    }
-    const int col = col0 + c * 16 + li;
-    if (col >= P.ncols) continue;
-    float *o = op + (size_t)col * P.out_stride;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const int s = kg * 16 + e * 4;
-      f32x4 v;
-#pragma unroll
-      for (int r = 0; r < NRT; r++)
-        v[r] = (__builtin_fmaf(wf0 + (float)(4 * e + r), tot1[r][c][e], tot0[r][c][e]) * inv_x) * inv_gc[c];
-      if (P.vec_ok && s + 3 < tile_len) {
-        *reinterpret_cast<f32x4 *>(o + s) = v;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          if (s + i < tile_len) o[s + i] = v[i];
-      }
-    }
-  }
+  write_tile<NCT>(tot0, tot1, wf0, inv_x, inv_gc, ot, op, P.out_stride, col0, P.ncols, li, kg, tile_len, P.vec_ok);
   };  // body
   // (three forms of the body in one kernel; the words are wave-uniform: scalar branches)
   if (span && hinge_span_exceeded(*span, P.M)) body(std::true_type{}, std::true_type{});

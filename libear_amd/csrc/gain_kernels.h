@@ -179,7 +179,7 @@ struct LevelProbe {
 };
 // An object whose probed level lies this many binades below the call's is "quiet": the split-operand
 // kernels scale every input of a call by ONE power of two; with the low piece of an input kept as
-// (residual x 2^11) (gain_h2.h) both pieces are normal f16 numbers — 2^-22 relative precision — over 21
+// (residual x 2^11) (gain_split.h, kLowPieceScale) both pieces are normal f16 numbers — 2^-22 relative precision — over 21
 // binades below the level the prescale aims at (measured: 6.5e-8 relative RMS of the products down to 2^-18,
 // 1.4e-7 at 2^-20, 5e-7 at 2^-22; round 2, with the plain residual: 2.5e-7 at 2^-10, 1e-6 at 2^-12).  An
 // object quieter than that — more than 120 dB below the loudest — alone on a loudspeaker would be off by

@@ -55,7 +55,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "gain_h2.h"
+#include "gain_split.h"
 
 #ifndef EARHIP_P2_ABL
 #define EARHIP_P2_ABL 0  // (timing-only ablations, NOTES round 5: 1 no input requests, 2 no gain-row requests inside the chunk loop)
@@ -510,7 +510,7 @@ k_piece_build(PointStore ps, int M, int ntiles, int tile_samples, int64_t t_call
 // just finished.  (A workgroup per tile spent ~9 us of a tile's 117 outside its chunk loop on the ADM scene: the dependent
 // trips list -> gain rows / inputs -> first MFMA with nothing else on the CU, the stores, the next workgroup's launch.)
 // x_scale, g_scale: exact powers of two (gain_h2.h).
-// WIDE: the low pieces of the inputs are kept scaled (kLowPieceScale, gain_h2.h) — 16 more multiplies, a third fragment of
+// WIDE: the low pieces of the inputs are kept scaled (kLowPieceScale, gain_split.h) — 16 more multiplies, a third fragment of
 // every column tile to write and to read.  Both forms are in the kernel; the probe's word (wide_cur) picks at run time, without
 // a probe the wide form runs.
 // (the 4-wave forms with three column tiles sit at the register limit: a workgroup per tile, nothing carried)
@@ -546,6 +546,7 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
   if (threadIdx.x < 16 * NCT) inv_gcol[threadIdx.x] = 1.0f / gcol[blockIdx.z * 16 * NCT + threadIdx.x];
   if (threadIdx.x < CH) ring[RING][threadIdx.x] = 0ull;
   __syncthreads();
+  // (own copy of gain_split.h's probed_input_scale: this kernel keeps the parent's text after an unexplained GPU fault, see below)
   if (level_cur) {  // input scale of THIS call from the level K0 probed (gain_h2.h)
     const unsigned lv = *level_cur;
     if (lv) {
@@ -593,6 +594,9 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
       for (int c = 0; c < NCT; c++) tot[r][c] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   };
 
+  // (own copy of gain_split.h's exact_segments.  This kernel keeps its own copies of the four blocks the other split-operand kernels
+  // share — input scale, exact path, non-finite test, write-out: with them shared every k_gain_mix_p2 got another instruction stream, and a suite run on that build
+  // ended in a GPU fault in a test whose only changed kernel was this one; as it stands its assembly is the parent's)
   // ---- exact path: one object, all its pieces inside this wave's 64 samples, f32 MFMA with k = {a, b}
   // of ONE object (k slots 2, 3 idle), accumulated into tot in units of 1 / (sx sg)
   // (sg: the gains are scaled by their column's scale, like the split operands — or not at all)
@@ -673,6 +677,7 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
         tot[r][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], gv[c], tot[r][c], 0, 0, 0);
   };
 
+  // (own copy of gain_split.h's write_tile, without the slope total: the same fault, see single_object)
   // the tile is done: scale and store.  inv_x: the inverse of the input scale the totals carry (exact: a power of two);
   // col_scaled: they are in units of 1 / (the column's gain scale) as well
   auto store_tile = [&](float inv_x, bool col_scaled) {
@@ -892,7 +897,7 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
       const uint32_t H = pack_f16(v[0], v[1]);
       h[i] = H;
       l[i] = pack_f16(sub_f16_lo(v[0], H), sub_f16_hi(v[1], H));  // residuals: exact in fp32
-      hs[i] = WIDE ? scale_f16x2_down(H) : 0u;                // h 2^-11: partner of the inputs' scaled low piece (gain_h2.h)
+      hs[i] = WIDE ? scale_f16x2_down(H) : 0u;                // h 2^-11: partner of the inputs' scaled low piece (gain_split.h)
     }
     u32x4 *f = &bfrag[buf][bfr][0];
     const int col = lane & 15;
@@ -983,7 +988,7 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
           ah[rp][qp] = H0;
           ah[rp + 1][qp] = H1;
           constexpr float LOW = WIDE ? kLowPieceScale : 1.0f;
-          const f32x2 r0 = f32x2{sub_f16_lo(s0[0], H0), sub_f16_lo(s0[1], H1)} * LOW;  // exact residuals (wide: scaled, gain_h2.h)
+          const f32x2 r0 = f32x2{sub_f16_lo(s0[0], H0), sub_f16_lo(s0[1], H1)} * LOW;  // exact residuals (wide: scaled, gain_split.h)
           const f32x2 r1 = f32x2{sub_f16_hi(s1[0], H0), sub_f16_hi(s1[1], H1)} * LOW;
           al[rp][qp] = pack_f16(r0[0], r1[0]);
           al[rp + 1][qp] = pack_f16(r0[1], r1[1]);
@@ -1147,7 +1152,7 @@ k_gain_mix_p2(GainMixParams P, PieceLists pl, float x_scale, const float *__rest
       for (int i = 0; i < novf; i++) single_object(ovf[i], x_scale, true);
     // an input beyond the f16 range (or not finite) shows as non-finite totals: redo the wave's tile
     // exactly, unscaled (every part redoes its share of the pieces)
-    bool bad = false;
+    bool bad = false;  // (own copy of gain_split.h's totals_not_finite, one set of totals: the same fault, see single_object)
 #pragma unroll
     for (int r = 0; r < NRT; r++)
 #pragma unroll

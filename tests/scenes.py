@@ -315,3 +315,48 @@ def solo_curves(curves, n_out, solo_speakers, seed=92):
                 f[:, solo_speakers] = 0.0
         out.append((t, d, f))
     return out
+
+
+def probed_samples(obj, total):
+    """the samples k_level_probe reads of this object's row in a call of `total` samples (gain_kernels.h: 16 runs of 4 float4s)"""
+    nvec, per, nrun = total >> 2, 4, 16
+    stretch = nvec // nrun
+    out = set()
+    for g in range(nrun):
+        h = ((obj * 2654435761) & 0xffffffff) ^ (g * 40503)
+        room = stretch - per + 1 if stretch > per else 1
+        for sub in range(per):
+            at = min(g * stretch + ((h * room) >> 32) + sub, nvec - 1)
+            out.update(range(4 * at, 4 * at + 4))
+    return out
+
+
+SPLIT_PATHS = dict(m=128, block=256, nblocks=5, start=37)
+
+
+def split_paths_scene(kind, n_out, bursts, tile=256):
+    """The scene that sends a split-operand gain kernel through its rare paths: 128 objects, one call of 5 blocks of 256 (the
+    renderer starts it at sample SPLIT_PATHS["start"], with the curves shifted likewise: the last 512-sample tile is ragged), curves
+    of the kind the kernel is built for — `grid` a point every `tile` samples (the planner gives the grid kernel 512-sample tiles only
+    when no curve point lies inside one), `pieces` ADM-like ramp-then-hold, `hinge` always ramping — with two
+    objects on off-grid ADM curves (the exact path inside tiles), inputs at 1e-3 of full scale and, with `bursts`, three samples 1e4
+    above that in two tiles, where the level probe does not read (the tiles overflow the f16 range and are redone exactly).
+    Returns (curves from time 0, inputs)."""
+    m, block, nblocks = SPLIT_PATHS["m"], SPLIT_PATHS["block"], SPLIT_PATHS["nblocks"]
+    total = block * nblocks
+    if kind == "grid":
+        curves = dense_curves(m, n_out, tile, (total + tile - 1) // tile, seed=5)
+    elif kind == "pieces":
+        curves = adm_curves(m, n_out, total, period=700, ramp=150, seed=m)
+    else:
+        curves = adm_curves(m, n_out, total, period=240, ramp=240, seed=m)
+    odd = adm_curves(2, n_out, total, period=700, ramp=150, seed=3)
+    curves[17], curves[90] = odd[0], odd[1]
+    x = (audio(m, total, seed=23) * np.float32(1e-3)).astype(np.float32)
+    if bursts:
+        for tile in (1, 3):
+            obj, s0 = (tile * 7) % m, tile * block + 201
+            while probed_samples(obj, total) & set(range(s0, s0 + 3)):
+                s0 += 8
+            x[obj, s0:s0 + 3] *= np.float32(1e4)
+    return curves, x

@@ -661,21 +661,9 @@ def test_grid_kernel_several_tiles_per_workgroup(layout, tile, wgs):
     curves[17], curves[90] = odd[0], odd[1]
     x = (scenes.audio(m, total, seed=23) * np.float32(1e-3)).astype(np.float32)
 
-    def probed(obj):  # the samples k_level_probe reads of this object's row (gain_kernels.h: 16 runs of 4 float4s)
-        nvec, per, nrun = total >> 2, 4, 16
-        stretch = nvec // nrun
-        out = set()
-        for g in range(nrun):
-            h = ((obj * 2654435761) & 0xffffffff) ^ (g * 40503)
-            room = stretch - per + 1 if stretch > per else 1
-            for sub in range(per):
-                at = min(g * stretch + ((h * room) >> 32) + sub, nvec - 1)
-                out.update(range(4 * at, 4 * at + 4))
-        return out
-
     for b0 in (3, 17, 18, 33, 40):  # bursts in samples the level probe does not read: their tiles overflow the f16 range
         obj, s0 = (b0 * 7) % m, b0 * block + 201
-        while probed(obj) & set(range(s0, s0 + 3)):
+        while scenes.probed_samples(obj, total) & set(range(s0, s0 + 3)):
             s0 += 8
         x[obj, s0:s0 + 3] *= np.float32(1e4)
     want = run_oracle(curves, x, n, block, dec, 255)
@@ -695,6 +683,101 @@ def test_grid_kernel_several_tiles_per_workgroup(layout, tile, wgs):
     # and with the whole call on its usual number of workgroups: the same values
     got2, _ = _with_env({"EARHIP_H2_TILE": tile}, render)
     assert np.array_equal(got, got2)
+
+
+# the split-operand kernels whose rare paths are the shared blocks of gain_split.h, forced by context option: (curves, options, the
+# kernel and the tile the plan reports).  The grid kernel's curves have their points on the grid of the tile asked for: the planner
+# gives it 512-sample tiles (the 8-wave kernels) only when no curve point lies inside one.
+SPLIT_KERNELS = [("grid", {"EARHIP_MFMA": None, "EARHIP_H2_TILE": "256"}, 3, 256), ("grid", {"EARHIP_MFMA": None, "EARHIP_H2_TILE": "512"}, 3, 512),
+                 ("hinge", {"EARHIP_MFMA": "6", "EARHIP_HG_TILE": "256"}, 5, 256), ("hinge", {"EARHIP_MFMA": "6", "EARHIP_HG_TILE": "512"}, 5, 512)]
+SPLIT_IDS = ["grid-256", "grid-512", "hinge-256", "hinge-512"]
+_split_oracle = {}
+
+
+def split_paths_case(kind, tile, layout, bursts, two_bus):
+    """(curves, inputs, decorrelators, the oracle's render) of scenes.split_paths_scene, the oracle side computed once per scene"""
+    n = len(LAYOUTS[layout])
+    key = (kind, tile, layout, bursts, two_bus)
+    if key not in _split_oracle:
+        curves, x = scenes.split_paths_scene(kind, n, bursts, tile)
+        dec = decorrelators(layout) if two_bus else None
+        want = run_oracle(curves, x, n, scenes.SPLIT_PATHS["block"], dec, 255 if two_bus else 0)
+        want.setflags(write=False)
+        _split_oracle[key] = (curves, x, dec, want)
+    return _split_oracle[key]
+
+
+@pytest.mark.parametrize("layout", ["0+5+0", "9+10+3"])
+@pytest.mark.parametrize("kind,opts,kernel,tile", SPLIT_KERNELS, ids=SPLIT_IDS)
+def test_split_kernels_exact_paths_vs_oracle(kind, opts, kernel, tile, layout):
+    """The rare paths of the grid and the hinge kernel, each forced, in one call of 5 blocks of 256 that starts at sample 37 (the
+    last 512-sample tile is ragged; the grid kernel's curves have a point every 256 or every 512 samples, so that its 4-wave and its
+    8-wave kernels both run): two objects off the grid (the exact path inside tiles, beside the split operands of the
+    others) and bursts 10^4 above the probed level in two tiles (their totals overflow: the overflow redo, per wave).  5 channels on
+    two buses are one column tile, 24 are three (on the 4-wave grid form: k_gain_mix_h2_t1).  Per channel, the project's bound for
+    these kernels."""
+    from libear_amd import capi
+    sp = scenes.SPLIT_PATHS
+    n = len(LAYOUTS[layout])
+    curves, x, dec, want = split_paths_case(kind, tile, layout, True, True)
+
+    def render():
+        c = capi.Context(0)  # (the kernel choice is read when a context is created)
+        try:
+            r = capi.Renderer(c, sp["m"], n, sp["block"], dec, 255, max_blocks=sp["nblocks"])
+            set_renderer_curves(r, [(t + sp["start"], d, f) for t, d, f in curves], True)
+            r.reset(sp["start"])
+            out = r.process(x)
+            plan = r.last_plan()
+            r.close()
+        finally:
+            c.close()
+        return out, plan
+
+    got, plan = _with_env(opts, render)
+    err = scenes.rel_rms_per_channel(got, want)
+    print(kind, opts, layout, plan, err)
+    assert plan["kernel"] == kernel and plan["tile"] == tile, plan
+    assert np.isfinite(got).all()
+    assert err <= 1e-6, (err, plan)
+
+
+@pytest.mark.parametrize("layout", ["0+5+0", "9+10+3"])
+@pytest.mark.parametrize("kind,opts,kernel,tile", SPLIT_KERNELS, ids=SPLIT_IDS)
+def test_split_kernels_unaligned_rows_vs_oracle(kind, opts, kernel, tile, layout):
+    """Output rows the kernels cannot store as vectors: the same kernels, curves and inputs (no bursts) rendered on the direct bus
+    alone from device buffers whose output row stride is n + 1 — the gain kernel writes the output rows itself (one object split:
+    GSPLIT = 1), finds them unaligned and sends EVERY object through its exact path and the scalar stores.  The column behind
+    the rows' end stays as it was.  (One bus: 5 channels are one column tile, 24 are two.)"""
+    import torch
+    from libear_amd import capi
+    sp = scenes.SPLIT_PATHS
+    n, total = len(LAYOUTS[layout]), sp["block"] * sp["nblocks"]
+    curves, x, _, want = split_paths_case(kind, tile, layout, False, False)
+
+    def render():
+        c = capi.Context(0)
+        try:
+            r = capi.Renderer(c, sp["m"], n, sp["block"], None, 0, max_blocks=sp["nblocks"])
+            set_renderer_curves(r, [(t + sp["start"], d, f) for t, d, f in curves], False)
+            r.reset(sp["start"])
+            xin = torch.from_numpy(x).cuda()
+            out = torch.full((n, total + 1), 7.5, dtype=torch.float32, device="cuda")
+            r.process_device(sp["nblocks"], xin.data_ptr(), total, out.data_ptr(), total + 1)
+            c.synchronize()
+            plan = r.last_plan()
+            r.close()
+        finally:
+            c.close()
+        return out.cpu().numpy(), plan
+
+    got, plan = _with_env(dict(opts, EARHIP_GSPLIT="1"), render)
+    err = scenes.rel_rms_per_channel(got[:, :total], want)
+    print(kind, opts, layout, plan, err)
+    assert plan["kernel"] == kernel and plan["tile"] == tile and plan["gsplit"] == 1, plan
+    assert np.isfinite(got).all()
+    assert err <= 1e-6, (err, plan)
+    assert np.all(got[:, total] == 7.5)
 
 
 @pytest.mark.parametrize("tile", [None, "256", "512"])

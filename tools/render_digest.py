@@ -1,6 +1,7 @@
 """SHA-256 of the outputs of a fixed list of renders that between them pass the branches of the gain stage's launch code:
     python tools/render_digest.py            (EARHIP_LIB=<another build of libearhip.so>: the same list through that build)
     python tools/render_digest.py k2         (the second list: the decorrelator stage and the transforms' launch layer, at the end)
+    python tools/render_digest.py paths      (the third list: the rare paths of the split-operand gain kernels, at the end)
 One line per case: its name, what the renderer reports about the call (gain kernel, tile, tiles, object splits, list layout, whether
 the device handed the call to the stand-by lists or ran the robust form) and the digest of the output rows.  Two builds whose host
 code enqueues the same kernels on the same data print the same lines; a refactor of the launch code is compared this way.
@@ -226,12 +227,66 @@ def run_transforms():
     ctx.close()
 
 
+# ---- the third list (argument "paths"): the rare paths of the split-operand gain kernels (gain_split.h) --------------------
+# scenes.split_paths_scene (tests/test_gpu_render.py, test_split_kernels_*) with each kernel forced, on one and on several column
+# tiles: through the host form with bursts above the probed level (the exact path inside tiles, the overflow redo, a ragged last
+# tile), and without them on the direct bus alone from device buffers whose output rows are unaligned (every object on the exact
+# path, scalar stores).
+PATH_KERNELS = [("grid", {"H2_TILE": 256}), ("grid", {"H2_TILE": 512}), ("pieces", {"MFMA": 5, "P2_TILE": 256}),
+                ("pieces", {"MFMA": 5, "P2_TILE": 512}), ("hinge", {"MFMA": 6, "HG_TILE": 256}), ("hinge", {"MFMA": 6, "HG_TILE": 512})]
+
+
+def run_paths(kind, opts, n_out, unaligned):
+    sp = scenes.SPLIT_PATHS
+    m, block, nblocks, t0 = sp["m"], sp["block"], sp["nblocks"], sp["start"]
+    total = block * nblocks
+    tile = list(opts.values())[-1]  # (the grid kernel's curves: their points on the grid of the tile asked for)
+    curves, x = scenes.split_paths_scene(kind, n_out, not unaligned, tile)
+    dec = None if unaligned else np.random.default_rng(5).uniform(-0.1, 0.1, (n_out, 512)).astype(np.float32)
+    ctx = capi.Context(0)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    if unaligned:
+        ctx.set_option("GSPLIT", 1)  # (the gain kernel writes the output rows itself)
+    r = capi.Renderer(ctx, m, n_out, block, dec, 0 if unaligned else 255, max_blocks=nblocks)
+    r.reset(t0)
+    for i, (t, d, f) in enumerate(curves):
+        r.set_object_points(i, t + t0, d, None if unaligned else f)
+    outs = []
+    for _ in range(2):  # (the second call: the other level words, the state of the first)
+        if unaligned:
+            import torch
+            xin = torch.from_numpy(x).cuda()
+            o = torch.full((n_out, total + 1), 7.5, dtype=torch.float32, device="cuda")
+            r.process_device(nblocks, xin.data_ptr(), total, o.data_ptr(), total + 1)
+            ctx.synchronize()
+            outs.append(o.cpu().numpy())
+        else:
+            outs.append(r.process(x))
+        if not outs[1:]:
+            plan = r.last_plan()
+            what = (f"kernel {plan['kernel']} tile {plan['tile']} ntiles {plan['ntiles']} gsplit {plan['gsplit']} paired {r.last_list_layout()} "
+                    f"standby {int(r.hinge_standby())} robust {int(r.hinge_robust())} wide {r.wide_form()} regrows {r.scratch_regrows()}")
+    r.close()
+    ctx.close()
+    name = f"paths_{kind}_tile{tile}_{n_out}ch" + ("_unaligned" if unaligned else "")
+    assert all(np.all(np.isfinite(o)) for o in outs), name
+    print(f"{name:42s} {what}\n    {sha(outs[0])} {sha(outs[1])}")
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["k2"]:
         for name, block, opts, kw in K2_CASES:
             run_k2(name, block, opts, **kw)
         run_transforms()
         print(f"{len(K2_CASES)} renders, the transforms")
+    elif sys.argv[1:] == ["paths"]:
+        import torch  # noqa: F401  (before the library touches the device: one HIP runtime per process, torch's — as bench.py does)
+        for unaligned in (False, True):
+            for kind, opts in PATH_KERNELS:
+                for n_out in (5, 24):
+                    run_paths(kind, opts, n_out, unaligned)
+        print(f"{4 * len(PATH_KERNELS)} cases")
     else:
         for name, curves, opts, kw in CASES:
             run(name, curves, opts, **kw)
