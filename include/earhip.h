@@ -1218,6 +1218,79 @@ int earhip_iir_process(earhip_iir *iir, size_t nsamples, const float *const *in,
 #define EARHIP_IIR_HIGH_SHELF 4
 int earhip_iir_design(int kind, double sample_rate, double f0, double q, double gain_db, double out[5]);
 
+/* ------------------------------------------------------------------------
+ * (P) Polyphase sample-rate converter — a rational rate change on the output bus, on the device: 44.1 or 96 kHz assets to a
+ * 48 kHz bed, a 48 kHz render delivered at 44.1 kHz or monitored at 96 kHz.  libear has no counterpart.
+ *
+ * The operation, exactly (a caller can reproduce it).  The rate is L / M (up by L = `up`, down by M = `down`, gcd(L, M) = 1),
+ * with T = `taps_per_phase` taps per phase and a prototype filter h[0 .. L T) given in float64.  The device holds
+ *     c[p][k] = (float)h[p + k L],   p in [0, L), k in [0, T).
+ * There is ONE input clock N, counted in samples since create or reset, a 64-bit host integer; x[i] is input sample i of a
+ * channel's stream and x[i] = +0.0f for i < 0.  Output j of the stream belongs to input index i_j = floor(j M / L) and phase
+ * p_j = (j M) mod L:
+ *     acc = +0.0f;  for k = 0, 1, .. T - 1 in this order:  acc = fmaf(c[p_j][k], x[i_j - k], acc);   y[j] = acc
+ * (float32, every multiply-add fused: ONE rounding each; subnormals are kept).  This is scipy.signal.upfirdn(h, x, L, M) sample
+ * for sample, in float32 and in that order.  Every channel is converted alike and alone.
+ * OUTPUT COUNT.  Output j exists once input i_j has been fed: after N inputs exactly ceil(N L / M) outputs have been produced
+ * in total, and a call produces the difference between the totals before and after it.  That difference may be 0 (L / M =
+ * 1 / 2: the second of two one-sample calls).  earhip_src_next_out tells it in advance.
+ * FIXED WINDOWS.  Every output is a fixed function of a fixed window of T inputs in a fixed order, so
+ *   - the same samples give the same BITS however the stream is cut into calls (the project's rule for non-recursive stages);
+ *   - the device form and a plain C++ host form (std::fmaf in the order above) give the same bits;
+ *   - a non-finite input sample s makes exactly the outputs with i_j - T + 1 <= s <= i_j non-finite, and no others;
+ *   - there are no atomics anywhere.
+ * LATENCY.  A linear-phase prototype delays by (L T - 1) / 2 prototype samples = (L T - 1) / (2 L) input samples =
+ * (L T - 1) / (2 M) output samples (earhip_src_info); there is no flush call: feed that many zeros to get the tail.
+ * LIMITS (anything outside is EARHIP_INVALID_ARGUMENT, checked before any device work): channels in [1, 64]; L, M in
+ * [1, 1024] with gcd(L, M) = 1; T in [1, 256]; L T <= 32768; every tap finite, as a float32 too; max_samples >= 1.
+ *
+ * Out of scope: attaching the stage to a renderer as groups L, M and N attach (feed it the rows a process call wrote:
+ * earhip_src_process_device on the same context follows the call's kernels on the stream; a stage that changes the sample
+ * count does not fit the renderer's taps), time-varying ratios, float64 accumulation, PCM frames in or out of the stage.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_src earhip_src;
+typedef struct earhip_src_config {
+  int channels;        /* [1, 64] */
+  int up;              /* L in [1, 1024] */
+  int down;            /* M in [1, 1024], gcd(L, M) = 1 */
+  int taps_per_phase;  /* T in [1, 256], L T <= 32768 */
+  const double *taps;  /* h[L T]; copied */
+  size_t max_samples;  /* >= 1: the longest process call, in input samples */
+} earhip_src_config;
+typedef struct earhip_src_properties {
+  int up, down, taps_per_phase;
+  int tile_out;       /* outputs of one tile of the kernel */
+  int tile_in;        /* ceil(tile_out M / L): a tile's length in input samples */
+  int table_in_lds;   /* 1: the kernel keeps c in LDS; 0: it reads c through the caches (large tables) */
+  int window_in_lds;  /* 1: the kernel stages a tile's inputs in LDS; 0: it reads the rows directly (M / L beyond about 11) */
+  size_t max_out;     /* ceil(max_samples L / M): no call produces more */
+  double latency_prototype, latency_in, latency_out; /* (L T - 1) / 2, / (2 L), / (2 M) */
+} earhip_src_properties;
+/* Everything is made here — the table, the histories (the last T - 1 inputs per channel, double-buffered: a call reads one and
+ * writes the other), device rows and pinned staging for the host form: a process call allocates nothing, and
+ * earhip_src_process_device synchronises nothing. */
+int earhip_src_create(earhip_ctx *ctx, const earhip_src_config *config, earhip_src **out);
+int earhip_src_destroy(earhip_src *src);
+int earhip_src_reset(earhip_src *src); /* histories to zero, clock to 0 */
+int earhip_src_info(const earhip_src *src, earhip_src_properties *info);
+/* what a call of nsamples inputs would produce now (nsamples > max_samples: EARHIP_INVALID_ARGUMENT) */
+int earhip_src_next_out(const earhip_src *src, size_t nsamples, size_t *n_out);
+/* planar float32 rows in device memory: input c at in_dev + c * in_stride (nsamples each, any nsamples >= 0), output c at
+ * out_dev + c * out_stride (*n_out each; n_out may be NULL); the rows of in and out must not overlap.  nsamples > max_samples,
+ * or an out_capacity (samples per output row) smaller than the call's outputs, is EARHIP_INVALID_ARGUMENT and nothing is
+ * consumed.  A call with no input does nothing; a call with input and no output only advances the clock and the history.
+ * Enqueues on the context's stream, allocates nothing, does not synchronise. */
+int earhip_src_process_device(earhip_src *src, size_t nsamples, const float *in_dev, size_t in_stride, float *out_dev,
+                              size_t out_stride, size_t out_capacity, size_t *n_out);
+/* host rows in[channels] of nsamples, out[channels] of out_capacity: H2D + the above + D2H; synchronises */
+int earhip_src_process(earhip_src *src, size_t nsamples, const float *const *in, float *const *out, size_t out_capacity,
+                       size_t *n_out);
+/* A pure host function, no context and no device: a Kaiser-windowed sinc of length L T with its cutoff at `cutoff / max(L, M)`
+ * of the prototype's Nyquist frequency, cutoff in (0, 1], normalised to unit DC gain and then multiplied by L — that is
+ * L * scipy.signal.firwin(L * T, cutoff / max(L, M), window=("kaiser", beta)).  out[L T].  A ratio or T outside the limits
+ * above, beta < 0, a cutoff outside (0, 1] or a non-finite argument is EARHIP_INVALID_ARGUMENT. */
+int earhip_src_design(int up, int down, int taps_per_phase, double beta, double cutoff, double *out);
+
 #ifdef __cplusplus
 }
 #endif

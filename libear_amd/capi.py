@@ -1401,3 +1401,95 @@ class IirBank:
         if self.h:
             load().earhip_iir_destroy(self.h)
             self.h = C.c_void_p()
+
+
+# (P) polyphase sample-rate converter
+
+class _SrcConfig(C.Structure):
+    _fields_ = [("channels", C.c_int), ("up", C.c_int), ("down", C.c_int), ("taps_per_phase", C.c_int),
+                ("taps", C.c_void_p), ("max_samples", C.c_size_t)]
+
+
+class _SrcProperties(C.Structure):
+    _fields_ = [("up", C.c_int), ("down", C.c_int), ("taps_per_phase", C.c_int), ("tile_out", C.c_int), ("tile_in", C.c_int),
+                ("table_in_lds", C.c_int), ("window_in_lds", C.c_int), ("max_out", C.c_size_t),
+                ("latency_prototype", C.c_double), ("latency_in", C.c_double), ("latency_out", C.c_double)]
+
+
+def _src_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise InvalidArgument(INVALID_ARGUMENT, f"{name} must be an integer")
+    if not -2 ** 31 <= int(v) < 2 ** 31:
+        raise InvalidArgument(INVALID_ARGUMENT, f"{name} is out of range")
+    return int(v)
+
+
+def src_design(up, down, taps_per_phase, beta=10.0, cutoff=1.0):
+    """the prototype h[up * taps_per_phase] (float64) of a rate change by up / down: a Kaiser-windowed sinc with its cutoff at
+    cutoff / max(up, down) of the prototype's Nyquist, unit DC gain, times up.  A pure host function"""
+    up, down, T = _src_int("up", up), _src_int("down", down), _src_int("taps_per_phase", taps_per_phase)
+    out = np.zeros(max(up * T, 1) if 0 < up <= 1024 and 0 < T <= 256 else 1, np.float64)
+    load().earhip_src_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]
+    check(load().earhip_src_design(up, down, T, float(beta), float(cutoff), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class SampleRateConverter:
+    """(P) a rational rate change by up / down on planar float32 rows: y = scipy.signal.upfirdn(taps, x, up, down) in float32,
+    every output one chain of taps_per_phase fused multiply-adds; the same bits however the stream is cut into calls."""
+
+    def __init__(self, ctx, channels, up, down, taps_per_phase, taps, max_samples=48000):
+        channels, up, down = _src_int("channels", channels), _src_int("up", up), _src_int("down", down)
+        T = _src_int("taps_per_phase", taps_per_phase)
+        if isinstance(max_samples, bool) or not isinstance(max_samples, (int, np.integer)) or int(max_samples) < 1:
+            raise InvalidArgument(INVALID_ARGUMENT, "max_samples must be an integer >= 1")
+        h = np.ascontiguousarray(np.asarray(taps, np.float64).reshape(-1))
+        if 0 < up <= 1024 and 0 < T <= 256 and h.size != up * T:
+            raise InvalidArgument(INVALID_ARGUMENT, "taps must hold up * taps_per_phase values")
+        self.ctx, self.channels, self.up, self.down, self.taps_per_phase = ctx, channels, up, down, T
+        self.max_samples = int(max_samples)
+        cfg = _SrcConfig(channels, up, down, T, C.c_void_p(h.ctypes.data) if h.size else None, self.max_samples)
+        self.h = C.c_void_p()
+        check(load().earhip_src_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(self.h)))
+        self.max_out = self.info()["max_out"]
+
+    def info(self):
+        """dict: up, down, taps_per_phase, tile_out, tile_in, table_in_lds, window_in_lds, max_out, latency_prototype /_in /_out"""
+        v = _SrcProperties()
+        check(load().earhip_src_info(self.h, C.byref(v)))
+        return {name: getattr(v, name) for name, _ in _SrcProperties._fields_}
+
+    def next_out(self, nsamples):
+        """the outputs a call of nsamples inputs would produce now"""
+        n = C.c_size_t(0)
+        check(load().earhip_src_next_out(self.h, C.c_size_t(nsamples), C.byref(n)))
+        return n.value
+
+    def process(self, x):
+        """x [channels][n] host array, any n -> [channels][n_out]"""
+        x = _f32(x)
+        if x.ndim != 2 or x.shape[0] != self.channels:
+            raise InvalidArgument(INVALID_ARGUMENT, "x must be [channels][n]")
+        n = x.shape[1]
+        cap = self.next_out(n)
+        out = np.empty((self.channels, cap), np.float32)
+        got = C.c_size_t(0)
+        check(load().earhip_src_process(self.h, C.c_size_t(n), _chan_ptrs(x), _chan_ptrs(out), C.c_size_t(cap), C.byref(got)))
+        assert got.value == cap
+        return out
+
+    def process_device(self, nsamples, in_ptr, in_stride, out_ptr, out_stride, out_capacity):
+        """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); enqueues on the context's stream; returns the
+        number of outputs written per row"""
+        got = C.c_size_t(0)
+        check(load().earhip_src_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                               C.c_void_p(out_ptr), C.c_size_t(out_stride), C.c_size_t(out_capacity), C.byref(got)))
+        return got.value
+
+    def reset(self):
+        check(load().earhip_src_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_src_destroy(self.h)
+            self.h = C.c_void_p()
