@@ -737,6 +737,15 @@ int earhip_render_wide_form(earhip_render *r, int *wide);
  * workgroup tile of the gain kernel, [2] number of such tiles, [3] grid-level object splits.
  * For tests and benchmarks that must know which kernel instantiation they measured. */
 int earhip_render_last_plan(const earhip_render *r, int out[4]);
+/* The decorrelator stage's plan: [0] the partition size of the decorrelator FIRs in samples (the block size, or 512 for
+ * blocks of 1024, 2048, 4096 whose FIRs fit 512 taps: option K2_OWN_BLOCK), [1] the number of partitions (ceil(n_taps /
+ * [0]): one launch each per call), and of the last process call (of its last span, where it ran as two:
+ * earhip_render_last_tail_blocks) [2] the kernel form — 0 the workgroup kernel instantiated for the transform size (powers
+ * of two from 128), 1 the workgroup kernel with the transform's shape taken at run time (every other size), 2 the wave
+ * kernel (512-sample partitions, one partition; option K2_WG) — and [3] the blocks (partitions) per run of that kernel
+ * (option RUN; 0: no call yet).  All zeros for a renderer of one bus, which has no decorrelator stage.  For tests that
+ * must know which form of the stage they checked. */
+int earhip_render_last_decor_plan(const earhip_render *r, int out[4]);
 /* Layout of the piece lists of the last call (kernel 4, or the lists standing by behind kernel 5): *paired = 1 paired
  * (an object's base and delta piece share one input request; curves that hold most of the time), 0 packed (every chunk
  * sums its products among itself before it touches the running total: curves that ramp most of the time ALWAYS get this

@@ -969,6 +969,13 @@ class Renderer:
         check(load().earhip_render_last_plan(self.h, out))
         return {"kernel": out[0], "tile": out[1], "ntiles": out[2], "gsplit": out[3]}
 
+    def last_decor_plan(self):
+        """the decorrelator stage's plan: partition size and count of the FIRs, and of the last call the kernel form (0 workgroup
+        kernel of a fixed size, 1 run-time shape, 2 wave kernel) and the blocks per run; zeros on one bus"""
+        out = (C.c_int * 4)()
+        check(load().earhip_render_last_decor_plan(self.h, out))
+        return {"Bk": out[0], "NP": out[1], "form": out[2], "run": out[3]}
+
     def attach_loudness(self, meter):
         """every process call of every form feeds its float32 output samples to `meter` (a Loudness of n_out channels on this
         context) on the device; None detaches (include/earhip.h: earhip_render_attach_loudness)"""

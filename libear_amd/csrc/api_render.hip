@@ -949,4 +949,16 @@ int earhip_render_last_plan(const earhip_render *r, int out[4]) {
   });
 }
 
+int earhip_render_last_decor_plan(const earhip_render *r, int out[4]) {
+  return guarded([&] {
+    require(r != nullptr && out != nullptr, "NULL argument");
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (r->K != 2) return;
+    out[0] = r->decor.Bk;
+    out[1] = r->decor.NP;
+    out[2] = r->decor.last_form;
+    out[3] = r->decor.last_R;
+  });
+}
+
 }  // extern "C"

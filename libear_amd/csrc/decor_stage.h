@@ -12,6 +12,13 @@
 
 namespace earhip {
 
+// whether transform size L has an instantiation of the workgroup kernel (launch_decor: else the run-time shape kernel)
+static bool decor_fixed_size(int L) {
+  bool fixed = false;
+  fft_size_switch<128>(L, [&](auto) { fixed = true; }, [] {});
+  return fixed;
+}
+
 // the workgroup-per-run kernel at transform size L
 static void launch_decor(int L, const DecorParams &P, dim3 grid, hipStream_t s) {
   fft_size_switch<128>(
@@ -31,6 +38,7 @@ struct DecorStage : DecorPlan {
   DevBuf<float> ztail, zdly, zhist;  // all-zero state, never written: what the first call after a reset reads
   bool fresh = true;          // no call since create / reset: the state is zero
   int cur = 0;  // which state buffer holds the current state
+  int last_form = 0, last_R = 0;  // of the last run: 0 workgroup template, 1 run-time shape, 2 wave kernel; blocks per run (0: no run yet)
 
   void create(earhip_ctx *ctx, const earhip_render_config &cfg, int block) {
     static_cast<DecorPlan &>(*this) =
@@ -106,6 +114,8 @@ struct DecorStage : DecorPlan {
     P.T = kblocks;
     const int R = wave_k2 && !run_len_set ? wave_run_len(kblocks, N, ctx->num_cus, kDecorWaves) : run_len;
     P.R = R;
+    last_form = wave_k2 ? 2 : decor_fixed_size(Lk) ? 0 : 1;
+    last_R = R;
     P.D = D;
     P.hist_len = (NP - 1) * Bk;
     P.hist_in = fresh ? zhist.p : hist[cur].p;
