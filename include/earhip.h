@@ -318,7 +318,8 @@ int earhip_design_decorrelators_for_layout(const char *layout, int without_lfe, 
  * sqrt(diffuse) split into the direct and diffuse vectors that feed (F).  A BATCH of
  * positions per call (one device thread each, double precision): what a renderer needs
  * per (object, metadata block).  Not implemented, as in libear's own calculate(): Cartesian
- * positions, divergence, channel lock, zone exclusion, screen scaling.
+ * positions, divergence, channel lock, zone exclusion, screen scaling — of these the _objects
+ * forms below carry divergence, channel lock and zone exclusion.
  * The _extent forms add libear's polar extent panner (src/object_based/polar_extent.cpp:
  * 12-302 with its core, polar_extent_scalar.cpp:25-108): width and height in degrees, depth in
  * distance units, each may be NULL (0); one wave per position sums the point source panner's
@@ -363,6 +364,82 @@ int earhip_panner_calculate_extent_device(earhip_panner *p, size_t npos, const d
                                           const double *width, const double *height,
                                           const double *depth, const double *gain,
                                           const double *diffuse, float *direct, float *diffuse_out);
+/* The _objects forms: the _extent forms plus channelLock, polar objectDivergence and zoneExclusion
+ * of an audioBlockFormat.  libear refuses the three (gain_calculator_objects.cpp:37-44); this comment
+ * is their specification, after ITU-R BS.2127-0 7.3.6, 7.3.7 and 7.3.12.  Per object, in EAR's order:
+ *   1. p = the Cartesian position of (azimuth, elevation, distance).
+ *   2. Channel lock (channel_lock[i] non-zero).  Candidates: the non-LFE loudspeakers at the positions
+ *      the panner was created with, on the unit sphere; d_c = |p - s_c|.  With a maxDistance
+ *      (lock_max_distance[i]; +inf or a NULL array: none) only d_c < maxDistance + 1e-10 stay; none
+ *      left: p is unchanged.  Of those with d_c < min d + 1e-10 the first in the layout's lock priority
+ *      order (earhip_objects_lock_priority) wins, and p becomes its position at distance 1.
+ *   3. Divergence v = divergence[i] in [0, 1] with azimuthRange r = azimuth_range[i] degrees (NULL: 45).
+ *      v == 0: the one position, weight 1.  Else with (az, el, d) the polar coordinates of p (all 0 at the
+ *      origin) and the axes x' = cart(az - 90, 0, 1), y' = cart(az, el, 1), z' = cart(az, el + 90, 1):
+ *      p_k = q_k.x x' + q_k.y y' + q_k.z z' for q = cart(0, 0, d), cart(+r, 0, d), cart(-r, 0, d), with
+ *      power weights (1 - v) / (1 + v), v / (1 + v), v / (1 + v).
+ *   4. Each p_k through the polar extent panner with the object's width, height and depth: g_k.
+ *   5. g = sqrt((sum_k w_k g_k^2) D), D the downmix matrix of the object's excluded set
+ *      (earhip_objects_zone_downmix; excluded[i]: bit c set = channel c of the FULL layout is excluded,
+ *      LFE bits are ignored; earhip_objects_excluded_channels turns zones into such a mask).
+ *   6. LFE columns zero, gain, the sqrt(1 - diffuse) / sqrt(diffuse) split.
+ * If no region of the layout takes one of the p_k the object's rows are zero and it counts once in
+ * earhip_panner_missed (the host form: EARHIP_INTERNAL_ERROR).  Any of channel_lock,
+ * lock_max_distance, divergence, azimuth_range, excluded may be NULL (0, none, 0, 45, 0).  A row whose
+ * lock flag is 0, whose divergence is 0 and whose mask has no non-LFE bit takes the _extent forms'
+ * kernels and has their bits.  Layouts have at most 24 channels.
+ * The host form refuses, with EARHIP_INVALID_ARGUMENT and a message that names the index: a divergence
+ * outside [0, 1] or NaN, a negative or NaN maxDistance, a non-finite azimuth_range, a mask bit at or
+ * beyond the layout's channel count.  The _device form cannot look at the values: it clamps a
+ * divergence to [0, 1] (NaN: 0), a NaN maxDistance lets no loudspeaker qualify (the position stays),
+ * mask bits beyond the layout are ignored, and a non-finite azimuth_range gives positions no region takes (zero rows, counted as missed). */
+int earhip_panner_calculate_objects(earhip_panner *p, size_t npos, const double *azimuth,
+                                    const double *elevation, const double *distance,
+                                    const double *width, const double *height, const double *depth,
+                                    const double *gain, const double *diffuse,
+                                    const unsigned char *channel_lock,
+                                    const double *lock_max_distance, const double *divergence,
+                                    const double *azimuth_range, const uint32_t *excluded,
+                                    float *direct, float *diffuse_out);
+int earhip_panner_calculate_objects_device(earhip_panner *p, size_t npos, const double *azimuth,
+                                           const double *elevation, const double *distance,
+                                           const double *width, const double *height,
+                                           const double *depth, const double *gain,
+                                           const double *diffuse, const unsigned char *channel_lock,
+                                           const double *lock_max_distance,
+                                           const double *divergence, const double *azimuth_range,
+                                           const uint32_t *excluded, float *direct,
+                                           float *diffuse_out);
+/* Pure host functions: no context, no device.
+ * The lock priority order of a layout: the full-layout indices of its non-LFE loudspeakers, ascending
+ * by (|nominal elevation|, nominal elevation, |nominal azimuth|, nominal azimuth); order: one int per
+ * non-LFE loudspeaker. */
+int earhip_objects_lock_priority(const char *layout, int *order);
+/* an exclusion zone (PolarExclusionZone / CartesianExclusionZone of include/ear/metadata.hpp) */
+typedef struct earhip_exclusion_zone {
+  int cartesian; /* nonzero: the six Cartesian bounds count, else the four polar ones */
+  double min_azimuth, max_azimuth, min_elevation, max_elevation;
+  double min_x, max_x, min_y, max_y, min_z, max_z;
+} earhip_exclusion_zone;
+/* The loudspeakers the union of zones excludes, at their NOMINAL positions on the unit sphere, tol = 1e-6.
+ * Polar: min_elevation - tol < el < max_elevation + tol, and |el| > 90 - tol or the azimuth in range:
+ * with end' = max_azimuth moved by whole turns into [min_azimuth, min_azimuth + 360] (the two congruent:
+ * min_azimuth when max_azimuth <= min_azimuth, else min_azimuth + 360, so -180 .. 180 is the full circle)
+ * and x = the azimuth moved into [min_azimuth - tol, min_azimuth - tol + 360): x <= end' + tol.
+ * Cartesian: min - tol < c < max + tol for each coordinate.  *mask: bits of the full layout. */
+int earhip_objects_excluded_channels(const char *layout, int n_zones,
+                                     const earhip_exclusion_zone *zones, uint32_t *mask);
+/* The downmix matrix of an excluded set, matrix: [n_channels][n_channels] double, row i = where the signal
+ * of channel i goes; LFE rows and columns are identity.  Non-LFE loudspeakers, nominal positions on the
+ * unit sphere: layer 0 for el < -10, 1 for el < 10, 2 for el < 60, else 3; fb = +1, 0, -1 for y > 1e-6,
+ * within 1e-6 of 0, < -1e-6.  For loudspeaker i every loudspeaker j (itself included) gets the key
+ * (LP[layer_i][layer_j], |fb_i - fb_j|, llround(|s_i - s_j| 1e6), llround(|y_i - y_j| 1e6)) with
+ * LP = {{0,1,2,3},{3,0,1,2},{3,2,0,1},{3,2,1,0}}; sorted by key, equal keys form a group.  An empty set
+ * or one holding every non-LFE loudspeaker: identity.  Else the row of an excluded i has 1/m on the m
+ * non-excluded members of the first group of i that has any.  A mask bit at or beyond the channel count
+ * is EARHIP_INVALID_ARGUMENT. */
+int earhip_objects_zone_downmix(const char *layout, uint32_t mask, double *matrix);
+
 /* positions of the LAST *_device call that no region of the layout took (libear dereferences an empty
  * optional there, src/object_based/gain_calculator_objects.cpp:46; the host-pointer forms turn it into
  * EARHIP_INTERNAL_ERROR themselves): their gain rows are zero.  Synchronises the stream. */

@@ -483,6 +483,40 @@ class Panner:
         check(load().earhip_panner_calculate_extent_device(self.h, C.c_size_t(n), vp(az), vp(el), vp(dist), vp(width), vp(height),
                                                            vp(depth), vp(gain), vp(diffuse), vp(direct), vp(diffuse_out)))
 
+    def calculate_objects(self, az, el, dist=None, gain=None, diffuse=None, width=None, height=None, depth=None,
+                          channel_lock=None, lock_max_distance=None, divergence=None, azimuth_range=None, excluded=None):
+        """calculate() plus channelLock (flags, and maxDistance: inf = none), polar objectDivergence (value in [0, 1],
+        azimuthRange in degrees, None: 45) and zoneExclusion (bit masks over the full layout, see
+        objects_excluded_channels); arrays [n] or scalars, None = absent -> (direct, diffuse) float32 [n][n_out]"""
+        f64 = C.POINTER(C.c_double)
+        az = np.ascontiguousarray(np.atleast_1d(az), np.float64)
+        n = az.size
+
+        def arr(v, dtype=np.float64):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (n,)))
+
+        def opt(v, t=f64):
+            return None if v is None else _ptr(v, t)
+        a = [arr(v) for v in (el, dist, width, height, depth, gain, diffuse)]
+        lock, mask = arr(channel_lock, np.uint8), arr(excluded, np.uint32)
+        lock_max, div, rng = arr(lock_max_distance), arr(divergence), arr(azimuth_range)
+        d = np.empty((n, self.n_out), np.float32)
+        f = np.empty((n, self.n_out), np.float32)
+        check(load().earhip_panner_calculate_objects(self.h, C.c_size_t(n), _ptr(az, f64), *[opt(v) for v in a],
+                                                     opt(lock, C.POINTER(C.c_ubyte)), opt(lock_max), opt(div), opt(rng),
+                                                     opt(mask, C.POINTER(C.c_uint32)), _ptr(d), _ptr(f)))
+        return d, f
+
+    def calculate_objects_device(self, n, az, el, dist, gain, diffuse, direct, diffuse_out, width=None, height=None, depth=None,
+                                 channel_lock=None, lock_max_distance=None, divergence=None, azimuth_range=None, excluded=None):
+        """device addresses (ints; None = absent; channel_lock: uint8, excluded: uint32, the others float64): enqueues on
+        the context's stream, does not synchronise.  The values are not validated: see include/earhip.h."""
+        def vp(a):
+            return None if a is None else C.c_void_p(int(a))
+        check(load().earhip_panner_calculate_objects_device(
+            self.h, C.c_size_t(n), vp(az), vp(el), vp(dist), vp(width), vp(height), vp(depth), vp(gain), vp(diffuse),
+            vp(channel_lock), vp(lock_max_distance), vp(divergence), vp(azimuth_range), vp(excluded), vp(direct), vp(diffuse_out)))
+
     def missed(self):
         """positions of the last calculate_device call that no region of the layout took (synchronises)"""
         n = C.c_uint(0)
@@ -493,6 +527,41 @@ class Panner:
         if self.h:
             load().earhip_panner_destroy(self.h)
             self.h = C.c_void_p()
+
+
+class ExclusionZone(C.Structure):
+    """earhip_exclusion_zone"""
+    _fields_ = [("cartesian", C.c_int)] + [(k, C.c_double) for k in (
+        "min_azimuth", "max_azimuth", "min_elevation", "max_elevation", "min_x", "max_x", "min_y", "max_y", "min_z", "max_z")]
+
+
+def objects_lock_priority(layout):
+    """(I) full-layout indices of a layout's non-LFE loudspeakers in channel-lock priority order (pure host)"""
+    n = sum(1 for c in layout_channels(layout) if not c[3])
+    order = (C.c_int * n)()
+    check(load().earhip_objects_lock_priority(layout.encode(), order))
+    return list(order)
+
+
+def objects_excluded_channels(layout, zones):
+    """(I) the bit mask (full layout) of the loudspeakers a list of zones excludes (pure host).  A zone is a dict of
+    keyword bounds: min_azimuth, max_azimuth, min_elevation, max_elevation, or min_x .. max_z (a Cartesian zone)"""
+    zs = (ExclusionZone * max(len(zones), 1))()
+    for z, given in zip(zs, zones):
+        z.cartesian = int(any(k.endswith(("_x", "_y", "_z")) for k in given))
+        for k, v in given.items():
+            setattr(z, k, float(v))
+    mask = C.c_uint32(0)
+    check(load().earhip_objects_excluded_channels(layout.encode(), len(zones), zs, C.byref(mask)))
+    return mask.value
+
+
+def objects_zone_downmix(layout, mask):
+    """(I) the zone-exclusion downmix matrix [n][n] float64 of an excluded set (bit mask over the full layout; pure host)"""
+    n = len(layout_channels(layout))
+    out = np.empty((n, n), np.float64)
+    check(load().earhip_objects_zone_downmix(layout.encode(), C.c_uint32(int(mask)), _ptr(out, C.POINTER(C.c_double))))
+    return out
 
 
 class DSMetadata(C.Structure):

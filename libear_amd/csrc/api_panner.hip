@@ -209,54 +209,67 @@ __device__ inline int pan_outputs(const PanParams &P, const double (&real)[kMaxP
 #include "extent_kernels.h"
 namespace earhip {
 
-// One thread per position: direct / diffuse [npos][n_full] float; *missed counts positions no region took.
-// Positions that libear spreads over the sphere — an extent, or a distance under 1, which widens even a
-// zero extent (polar_extent.cpp:62-70) — are prepared here (everything that is scalar double work in libear)
-// and left as a job for k_pan_objects_extent (a wave each).  jobs == NULL: every distance is 1 and there is
-// no extent.
-static __global__ void __launch_bounds__(128)
-k_pan_objects(PanParams P, size_t npos, const double *az, const double *el, const double *dist, const double *width,
-              const double *height, const double *depth, const double *gain, const double *diffuse, float *direct,
-              float *diff, unsigned *missed, ExtentJob *jobs, unsigned *job_count) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npos) return;
-  const Vec3 p = polar_to_cart(az[i], el[i], dist ? dist[i] : 1.0);
-  ExtentPasses X;
+// The scalar part of one position (everything that is scalar double work in libear): the renderings of
+// PolarExtent::handle with the share of the spread part in each (may_spread false: a distance of 1 and no extent,
+// nothing is spread), and, where a rendering needs them, the point source panner's outputs pv[0 .. n_pv).
+// false: no region took the position.
+__device__ inline bool pan_prepare(const PanParams &P, Vec3 p, bool may_spread, double width, double height, double depth,
+                                   ExtentPasses &X, bool &spread_any, double (&pv)[kMaxPanOut], int &n_pv) {
   X.n_pass = 1;
   X.spread[0] = X.spread[1] = 0.0;
-  if (jobs) extent_passes(p, width ? width[i] : 0.0, height ? height[i] : 0.0, depth ? depth[i] : 0.0, X);
-  bool spread_any = false, need_point = false;
+  if (may_spread) extent_passes(p, width, height, depth, X);
+  spread_any = false;
+  bool need_point = false;
   for (int k = 0; k < X.n_pass; k++) {
     spread_any = spread_any || X.spread[k] > 1e-10;
     need_point = need_point || (1.0 - X.spread[k]) > 1e-10;
   }
-  double real[kMaxPanOut];
-  double pv[kMaxPanOut];
-  int n_pv = 0;
-  float *d = direct + i * P.n_full, *f = diff + i * P.n_full;
+  n_pv = 0;
   if (need_point) {
-    if (!pan_full(P.table, p, real)) {
-      for (int c = 0; c < P.n_full; c++) d[c] = f[c] = 0.0f;
-      atomicAdd(missed, 1u);
-      return;
-    }
+    double real[kMaxPanOut];
+    if (!pan_full(P.table, p, real)) return false;
     n_pv = pan_outputs(P, real, pv);
   }
+  return true;
+}
+
+// what a wave needs to render position `pos` at p (extent_render)
+__device__ inline void extent_job_fill(ExtentJob &J, int pos, Vec3 p, const ExtentPasses &X, const double (&pv)[kMaxPanOut],
+                                       int n_pv) {
+  J.pos = pos;
+  J.n_pass = X.n_pass;
+  for (int k = 0; k < 2; k++) {
+    J.spread[k] = X.spread[k];
+    // (:270-272: at least half the fade width in each dimension)
+    if (k < X.n_pass && X.spread[k] > 1e-10)
+      extent_setup(p, fmax(X.w[k], kExtentFade / 2.0), fmax(X.h[k], kExtentFade / 2.0), J.W[k]);
+  }
+  const double n = sqrt(p.x * p.x + p.y * p.y + p.z * p.z);
+  J.dir[0] = n < 1e-10 ? 0.0f : (float)(p.x / n);
+  J.dir[1] = n < 1e-10 ? 1.0f : (float)(p.y / n);
+  J.dir[2] = n < 1e-10 ? 0.0f : (float)(p.z / n);
+  for (int c = 0; c < kMaxPanOut; c++) J.psq[c] = c < n_pv ? pv[c] * pv[c] : 0.0;
+}
+
+// Position i at p by one thread: rows i of direct / diffuse [npos][n_full] float; *missed counts positions no region
+// took.  Positions that libear spreads over the sphere — an extent, or a distance under 1, which widens even a
+// zero extent (polar_extent.cpp:62-70) — are prepared here and left as a job for k_pan_objects_extent (a wave each).
+// jobs == NULL: every distance is 1 and there is no extent.
+__device__ inline void pan_object(const PanParams &P, size_t i, Vec3 p, double width, double height, double depth,
+                                  const double *gain, const double *diffuse, float *direct, float *diff, unsigned *missed,
+                                  ExtentJob *jobs, unsigned *job_count) {
+  ExtentPasses X;
+  bool spread_any;
+  double pv[kMaxPanOut];
+  int n_pv;
+  float *d = direct + i * P.n_full, *f = diff + i * P.n_full;
+  if (!pan_prepare(P, p, jobs != nullptr, width, height, depth, X, spread_any, pv, n_pv)) {
+    for (int c = 0; c < P.n_full; c++) d[c] = f[c] = 0.0f;
+    atomicAdd(missed, 1u);
+    return;
+  }
   if (spread_any) {
-    ExtentJob &J = jobs[atomicAdd(job_count, 1u)];
-    J.pos = (int)i;
-    J.n_pass = X.n_pass;
-    for (int k = 0; k < 2; k++) {
-      J.spread[k] = X.spread[k];
-      // (:270-272: at least half the fade width in each dimension)
-      if (k < X.n_pass && X.spread[k] > 1e-10)
-        extent_setup(p, fmax(X.w[k], kExtentFade / 2.0), fmax(X.h[k], kExtentFade / 2.0), J.W[k]);
-    }
-    const double n = sqrt(p.x * p.x + p.y * p.y + p.z * p.z);
-    J.dir[0] = n < 1e-10 ? 0.0f : (float)(p.x / n);
-    J.dir[1] = n < 1e-10 ? 1.0f : (float)(p.y / n);
-    J.dir[2] = n < 1e-10 ? 0.0f : (float)(p.z / n);
-    for (int c = 0; c < kMaxPanOut; c++) J.psq[c] = c < n_pv ? pv[c] * pv[c] : 0.0;
+    extent_job_fill(jobs[atomicAdd(job_count, 1u)], (int)i, p, X, pv, n_pv);
     return;
   }
   for (int c = 0; c < P.n_full; c++) d[c] = f[c] = 0.0f;
@@ -276,6 +289,22 @@ k_pan_objects(PanParams P, size_t npos, const double *az, const double *el, cons
     f[o] = (float)(v * sf);
   }
 }
+
+// One thread per position (pan_object).
+static __global__ void __launch_bounds__(128)
+k_pan_objects(PanParams P, size_t npos, const double *az, const double *el, const double *dist, const double *width,
+              const double *height, const double *depth, const double *gain, const double *diffuse, float *direct,
+              float *diff, unsigned *missed, ExtentJob *jobs, unsigned *job_count) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npos) return;
+  const Vec3 p = polar_to_cart(az[i], el[i], dist ? dist[i] : 1.0);
+  pan_object(P, i, p, width ? width[i] : 0.0, height ? height[i] : 0.0, depth ? depth[i] : 0.0, gain, diffuse, direct, diff,
+             missed, jobs, job_count);
+}
+
+}  // namespace earhip
+#include "objects_kernels.h"
+namespace earhip {
 
 // HOA decoder design and the extent panner's point grid: panning values of unit vectors in double,
 // [npos][n_pv] (2 for 0+2+0)
@@ -514,6 +543,83 @@ double hoa_norm(HoaNorm t, int n, int am) {
   return f[n][am] * sn3d;
 }
 
+// ---- channel lock and zone exclusion: the small tables of a layout (include/earhip.h group I, the objects forms)
+struct ObjSpeaker {
+  int full;       // index in the full layout
+  double az, el;  // nominal position
+  Vec3 nominal;   // ... on the unit sphere
+};
+// the non-LFE loudspeakers of a layout, in layout order
+std::vector<ObjSpeaker> objects_speakers(const LayoutEntry &L) {
+  std::vector<ObjSpeaker> sp;
+  for (int c = 0; c < L.n; c++)
+    if (!L.channels[c].is_lfe)
+      sp.push_back({c, L.channels[c].azimuth, L.channels[c].elevation,
+                    polar_to_cart(L.channels[c].azimuth, L.channels[c].elevation, 1.0)});
+  require((int)sp.size() <= kObjMaxOut && L.n <= 32, "too many loudspeakers");
+  return sp;
+}
+// rank[s]: the place of loudspeaker s in the lock priority order: ascending (|el|, el, |az|, az), nominal
+std::vector<int> objects_lock_rank(const std::vector<ObjSpeaker> &sp) {
+  std::vector<int> order(sp.size()), rank(sp.size());
+  for (size_t s = 0; s < sp.size(); s++) order[s] = (int)s;
+  std::sort(order.begin(), order.end(), [&](int a, int b) {
+    const double ka[4] = {std::fabs(sp[a].el), sp[a].el, std::fabs(sp[a].az), sp[a].az};
+    const double kb[4] = {std::fabs(sp[b].el), sp[b].el, std::fabs(sp[b].az), sp[b].az};
+    return std::lexicographical_compare(ka, ka + 4, kb, kb + 4);
+  });
+  for (size_t r = 0; r < order.size(); r++) rank[order[r]] = (int)r;
+  return rank;
+}
+// groups[i][g]: the g-th nearest group of loudspeakers of loudspeaker i as a set of bits, itself first
+void objects_zone_groups(const std::vector<ObjSpeaker> &sp, unsigned (&groups)[kObjMaxOut][kObjMaxOut]) {
+  static const int LP[4][4] = {{0, 1, 2, 3}, {3, 0, 1, 2}, {3, 2, 0, 1}, {3, 2, 1, 0}};
+  const int n = (int)sp.size();
+  std::vector<int> layer(n), fb(n);
+  for (int i = 0; i < n; i++) {
+    layer[i] = sp[i].el < -10.0 ? 0 : sp[i].el < 10.0 ? 1 : sp[i].el < 60.0 ? 2 : 3;
+    fb[i] = sp[i].nominal.y > 1e-6 ? 1 : sp[i].nominal.y < -1e-6 ? -1 : 0;
+  }
+  std::memset(groups, 0, sizeof(groups));
+  struct Key {
+    long long k[4];
+    int j;
+  };
+  for (int i = 0; i < n; i++) {
+    std::vector<Key> keys;
+    for (int j = 0; j < n; j++) {
+      const Vec3 d = vsub(sp[i].nominal, sp[j].nominal);
+      keys.push_back({{LP[layer[i]][layer[j]], std::abs(fb[i] - fb[j]), std::llround(std::sqrt(vdot(d, d)) * 1e6),
+                       std::llround(std::fabs(d.y) * 1e6)}, j});
+    }
+    std::stable_sort(keys.begin(), keys.end(),
+                     [](const Key &a, const Key &b) { return std::lexicographical_compare(a.k, a.k + 4, b.k, b.k + 4); });
+    int g = -1;
+    for (int q = 0; q < n; q++) {
+      if (q == 0 || !std::equal(keys[q].k, keys[q].k + 4, keys[q - 1].k)) g++;
+      groups[i][g] |= 1u << keys[q].j;
+    }
+  }
+}
+// is azimuth az inside the range that runs anticlockwise from lo to hi (tol 1e-6)
+bool objects_az_in_range(double az, double lo, double hi) {
+  const double tol = 1e-6;
+  double d = std::fmod(hi - lo, 360.0);
+  if (d < 0.0) d += 360.0;
+  if (d == 0.0 && hi > lo) d = 360.0;
+  const double start = lo - tol;
+  double x = std::fmod(az - start, 360.0);
+  if (x < 0.0) x += 360.0;
+  return start + x <= lo + d + tol;
+}
+// mask over the full layout -> set of bits over the non-LFE loudspeakers; the full set excludes nothing
+unsigned objects_excluded_set(const std::vector<ObjSpeaker> &sp, uint32_t mask) {
+  unsigned em = 0;
+  for (size_t s = 0; s < sp.size(); s++)
+    if (mask >> sp[s].full & 1u) em |= 1u << s;
+  return em == (1u << sp.size()) - 1u ? 0u : em;
+}
+
 }  // namespace
 }  // namespace earhip
 
@@ -531,7 +637,12 @@ struct earhip_panner {
   // what the thread-per-position kernel leaves for the wave-per-position one (grown at first use; a call is
   // cut into launches of at most kExtentBatch positions, so at most that many records)
   DevBuf<ExtentJob> jobs;
-  DevBuf<unsigned> job_count;
+  DevBuf<unsigned> job_count;  // [2]: records in jobs, records in ojobs
+  // channel lock, divergence and zone exclusion (objects_kernels.h): the layout's tables, and what the front pass leaves
+  // for the wave-per-object kernel
+  LockTable lock_table;
+  ZoneTable zone_table;
+  DevBuf<ObjectsJob> ojobs;
   // staging of the host-pointer entry point (grown at first use)
   DevBuf<double> d_in;
   DevBuf<float> d_out;
@@ -675,6 +786,19 @@ int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, c
     for (int c = 0; c < kMaxPanOut; c++) p->P.real_of_full[c] = -1;
     const int n_pv = p->P.stereo ? 2 : n_real;
     for (int k = 0; k < n_pv; k++) p->P.real_of_full[p->P.stereo ? p->P.stereo_index[k] : p->P.full_index[k]] = k;
+    {  // the outputs as lock candidates (real positions) and their zone groups (nominal positions)
+      const std::vector<ObjSpeaker> sp = objects_speakers(L);
+      require((int)sp.size() == n_pv, "internal: panner outputs and loudspeakers differ");
+      const std::vector<int> rank = objects_lock_rank(sp);
+      std::memset(&p->lock_table, 0, sizeof(p->lock_table));
+      p->lock_table.n = p->zone_table.n = n_pv;
+      for (int k = 0; k < n_pv; k++) {
+        const Vec3 v = azimuth ? polar_to_cart(azimuth[sp[k].full], elevation[sp[k].full], 1.0) : sp[k].nominal;
+        p->lock_table.rank[k] = rank[k];
+        p->lock_table.pos[k][0] = v.x, p->lock_table.pos[k][1] = v.y, p->lock_table.pos[k][2] = v.z;
+      }
+      objects_zone_groups(sp, p->zone_table.groups);
+    }
     p->regions.alloc(regions.size());
     EARHIP_HIP(hipMemcpy(p->regions.p, regions.data(), sizeof(PanRegion) * regions.size(), hipMemcpyHostToDevice));
     p->P.table.n_regions = (int)regions.size();
@@ -827,7 +951,7 @@ static void launch_pan(earhip_panner *p, size_t npos, const double *az, const do
     return;
   }
   p->jobs.reserve(std::min(npos, kExtentBatch));
-  p->job_count.reserve(1);
+  p->job_count.reserve(2);
   auto at = [](const double *q, size_t o) { return q ? q + o : q; };
   for (size_t o = 0; o < npos; o += kExtentBatch) {
     const size_t n = std::min(kExtentBatch, npos - o);
@@ -841,6 +965,46 @@ static void launch_pan(earhip_panner *p, size_t npos, const double *az, const do
     hipLaunchKernelGGL(k_pan_objects_extent, dim3((unsigned)((n + kExtentWaves - 1) / kExtentWaves)), dim3(64 * kExtentWaves),
                        0, s, p->P, p->E, p->jobs.p, p->job_count.p, at(gain, o), at(diffuse, o), direct + o * N,
                        diffuse_out + o * N);
+    EARHIP_HIP(hipGetLastError());
+  }
+}
+
+// the objects forms: the front pass, then the two wave-per-object kernels over what it left.  Without any of the three
+// arrays there is nothing for them to do: the extent forms' launches.
+static void launch_objects(earhip_panner *p, size_t npos, const double *az, const double *el, const double *dist,
+                           const double *width, const double *height, const double *depth, const double *gain,
+                           const double *diffuse, const unsigned char *lock, const double *lock_max, const double *divergence,
+                           const double *az_range, const uint32_t *excluded, float *direct, float *diffuse_out) {
+  if (!lock && !divergence && !excluded) {
+    launch_pan(p, npos, az, el, dist, width, height, depth, gain, diffuse, direct, diffuse_out);
+    return;
+  }
+  hipStream_t s = p->ctx->stream;
+  const bool may_spread = dist || width || height || depth;
+  p->jobs.reserve(std::min(npos, kExtentBatch));
+  p->ojobs.reserve(std::min(npos, kExtentBatch));
+  p->job_count.reserve(2);
+  auto at = [](const double *q, size_t o) { return q ? q + o : q; };
+  for (size_t o = 0; o < npos; o += kExtentBatch) {
+    const size_t n = std::min(kExtentBatch, npos - o);
+    const size_t N = (size_t)p->P.n_full;
+    const dim3 waves((unsigned)((n + kExtentWaves - 1) / kExtentWaves)), wg(64 * kExtentWaves);
+    EARHIP_HIP(hipMemsetAsync(p->job_count.p, 0, 2 * sizeof(unsigned), s));
+    hipLaunchKernelGGL(k_pan_objects_front, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, p->P, p->lock_table, n, az + o,
+                       el + o, at(dist, o), at(width, o), at(height, o), at(depth, o), at(gain, o), at(diffuse, o),
+                       lock ? lock + o : lock, at(lock_max, o), at(divergence, o), at(az_range, o),
+                       excluded ? excluded + o : excluded, may_spread, direct + o * N, diffuse_out + o * N, p->missed.p,
+                       p->jobs.p, p->job_count.p, p->ojobs.p);
+    EARHIP_HIP(hipGetLastError());
+    // (both launched for the worst case — every object a job of that kind; surplus waves leave at once)
+    if (may_spread) {
+      hipLaunchKernelGGL(k_pan_objects_extent, waves, wg, 0, s, p->P, p->E, p->jobs.p, p->job_count.p, at(gain, o),
+                         at(diffuse, o), direct + o * N, diffuse_out + o * N);
+      EARHIP_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pan_objects_meta, waves, wg, 0, s, p->P, p->E, p->zone_table, p->ojobs.p, p->job_count.p + 1,
+                       at(width, o), at(height, o), at(depth, o), at(gain, o), at(diffuse, o), may_spread, direct + o * N,
+                       diffuse_out + o * N, p->missed.p);
     EARHIP_HIP(hipGetLastError());
   }
 }
@@ -920,6 +1084,134 @@ int earhip_panner_calculate(earhip_panner *p, size_t npos, const double *azimuth
                             float *diffuse_out) {
   return earhip_panner_calculate_extent(p, npos, azimuth, elevation, distance, nullptr, nullptr, nullptr, gain, diffuse, direct,
                                         diffuse_out);
+}
+
+int earhip_panner_calculate_objects_device(earhip_panner *p, size_t npos, const double *azimuth, const double *elevation,
+                                           const double *distance, const double *width, const double *height,
+                                           const double *depth, const double *gain, const double *diffuse,
+                                           const unsigned char *channel_lock, const double *lock_max_distance,
+                                           const double *divergence, const double *azimuth_range, const uint32_t *excluded,
+                                           float *direct, float *diffuse_out) {
+  return guarded([&] {
+    require(p != nullptr, "panner must not be NULL");
+    require(azimuth && elevation && direct && diffuse_out, "azimuth, elevation and the outputs must not be NULL");
+    require(npos < ((size_t)1 << 28), "too many positions");
+    p->ctx->use();
+    EARHIP_HIP(hipMemsetAsync(p->missed.p, 0, sizeof(unsigned), p->ctx->stream));
+    if (npos == 0) return;
+    launch_objects(p, npos, azimuth, elevation, distance, width, height, depth, gain, diffuse, channel_lock, lock_max_distance,
+                   divergence, azimuth_range, excluded, direct, diffuse_out);
+  });
+}
+
+int earhip_panner_calculate_objects(earhip_panner *p, size_t npos, const double *azimuth, const double *elevation,
+                                    const double *distance, const double *width, const double *height, const double *depth,
+                                    const double *gain, const double *diffuse, const unsigned char *channel_lock,
+                                    const double *lock_max_distance, const double *divergence, const double *azimuth_range,
+                                    const uint32_t *excluded, float *direct, float *diffuse_out) {
+  return guarded([&] {
+    require(npos < ((size_t)1 << 28), "too many positions");
+    // (the values first: they are refused whatever the panner is)
+    for (size_t i = 0; i < npos; i++) {
+      const std::string at = "[" + std::to_string(i) + "]";
+      if (divergence && !(divergence[i] >= 0.0 && divergence[i] <= 1.0)) fail_invalid("divergence" + at + " must be in [0, 1]");
+      if (lock_max_distance && !(lock_max_distance[i] >= 0.0))
+        fail_invalid("lock_max_distance" + at + " must not be negative or NaN");
+      if (azimuth_range && !std::isfinite(azimuth_range[i])) fail_invalid("azimuth_range" + at + " must be finite");
+    }
+    require(p != nullptr, "panner must not be NULL");
+    require(azimuth && elevation && direct && diffuse_out, "azimuth, elevation and the outputs must not be NULL");
+    const size_t N = (size_t)p->P.n_full;
+    for (size_t i = 0; excluded && i < npos; i++)
+      if (N < 32 && (excluded[i] >> N) != 0)
+        fail_invalid("excluded[" + std::to_string(i) + "] has a bit set beyond the layout's " + std::to_string(N) + " channels");
+    if (npos == 0) return;
+    earhip_ctx *ctx = p->ctx;
+    ctx->use();
+    // staging: 11 arrays of doubles, then the lock flags and the masks in whole doubles
+    constexpr int kIn = 11;
+    const size_t lock_at = kIn * npos, mask_at = lock_at + (npos + 7) / 8, total = mask_at + (npos + 1) / 2;
+    p->p_in.reserve(total);
+    p->d_in.reserve(total);
+    p->p_out.reserve(2 * npos * N);
+    p->d_out.reserve(2 * npos * N);
+    const double *src[kIn] = {azimuth, elevation, distance, width, height, depth, gain, diffuse, lock_max_distance, divergence,
+                              azimuth_range};
+    const double *dev[kIn];
+    for (int k = 0; k < kIn; k++) {
+      if (src[k]) std::memcpy(p->p_in.p + k * npos, src[k], sizeof(double) * npos);
+      dev[k] = src[k] ? p->d_in.p + k * npos : nullptr;
+    }
+    if (channel_lock) std::memcpy(p->p_in.p + lock_at, channel_lock, npos);
+    if (excluded) std::memcpy(p->p_in.p + mask_at, excluded, sizeof(uint32_t) * npos);
+    const unsigned char *dev_lock = channel_lock ? reinterpret_cast<const unsigned char *>(p->d_in.p + lock_at) : nullptr;
+    const uint32_t *dev_mask = excluded ? reinterpret_cast<const uint32_t *>(p->d_in.p + mask_at) : nullptr;
+    EARHIP_HIP(hipMemcpyAsync(p->d_in.p, p->p_in.p, sizeof(double) * total, hipMemcpyHostToDevice, ctx->stream));
+    EARHIP_HIP(hipMemsetAsync(p->missed.p, 0, sizeof(unsigned), ctx->stream));
+    launch_objects(p, npos, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev_lock, dev[8], dev[9], dev[10],
+                   dev_mask, p->d_out.p, p->d_out.p + npos * N);
+    EARHIP_HIP(hipMemcpyAsync(p->p_out.p, p->d_out.p, sizeof(float) * 2 * npos * N, hipMemcpyDeviceToHost, ctx->stream));
+    EARHIP_HIP(hipMemcpyAsync(p->p_missed.p, p->missed.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(direct, p->p_out.p, sizeof(float) * npos * N);
+    std::memcpy(diffuse_out, p->p_out.p + npos * N, sizeof(float) * npos * N);
+    if (*p->p_missed.p != 0) fail_internal("point source panner: a position was not handled by any region");
+  });
+}
+
+int earhip_objects_lock_priority(const char *layout, int *order) {
+  return guarded([&] {
+    require(order != nullptr, "NULL argument");
+    const std::vector<ObjSpeaker> sp = objects_speakers(layout_entry(layout));
+    const std::vector<int> rank = objects_lock_rank(sp);
+    for (size_t s = 0; s < sp.size(); s++) order[rank[s]] = sp[s].full;
+  });
+}
+
+int earhip_objects_excluded_channels(const char *layout, int n_zones, const earhip_exclusion_zone *zones, uint32_t *mask) {
+  return guarded([&] {
+    require(mask != nullptr && n_zones >= 0 && (zones != nullptr || n_zones == 0), "NULL argument");
+    const std::vector<ObjSpeaker> sp = objects_speakers(layout_entry(layout));
+    const double tol = 1e-6;
+    uint32_t m = 0;
+    for (const ObjSpeaker &c : sp)
+      for (int k = 0; k < n_zones; k++) {
+        const earhip_exclusion_zone &z = zones[k];
+        bool inside;
+        if (z.cartesian)
+          inside = z.min_x - tol < c.nominal.x && c.nominal.x < z.max_x + tol && z.min_y - tol < c.nominal.y &&
+                   c.nominal.y < z.max_y + tol && z.min_z - tol < c.nominal.z && c.nominal.z < z.max_z + tol;
+        else
+          inside = z.min_elevation - tol < c.el && c.el < z.max_elevation + tol &&
+                   (std::fabs(c.el) > 90.0 - tol || objects_az_in_range(c.az, z.min_azimuth, z.max_azimuth));
+        if (inside) m |= 1u << c.full;
+      }
+    *mask = m;
+  });
+}
+
+int earhip_objects_zone_downmix(const char *layout, uint32_t mask, double *matrix) {
+  return guarded([&] {
+    require(matrix != nullptr, "NULL argument");
+    const LayoutEntry &L = layout_entry(layout);
+    const std::vector<ObjSpeaker> sp = objects_speakers(L);
+    const size_t N = (size_t)L.n;
+    if (N < 32 && (mask >> N) != 0) fail_invalid("mask has a bit set beyond the layout's " + std::to_string(N) + " channels");
+    for (size_t r = 0; r < N; r++)
+      for (size_t c = 0; c < N; c++) matrix[r * N + c] = r == c ? 1.0 : 0.0;
+    const unsigned em = objects_excluded_set(sp, mask);
+    if (em == 0) return;
+    unsigned groups[kObjMaxOut][kObjMaxOut];
+    objects_zone_groups(sp, groups);
+    for (size_t i = 0; i < sp.size(); i++) {
+      if (!(em >> i & 1u)) continue;
+      unsigned to = 0;
+      for (size_t g = 0; g < sp.size() && to == 0; g++) to = groups[i][g] & ~em;
+      matrix[sp[i].full * N + sp[i].full] = 0.0;
+      for (size_t j = 0; j < sp.size(); j++)
+        if (to >> j & 1u) matrix[sp[i].full * N + sp[j].full] = 1.0 / __builtin_popcount(to);
+    }
+  });
 }
 
 }  // extern "C"

@@ -166,16 +166,9 @@ __device__ inline float extent_weight(const ExtentWeighting &W, float x, float y
   return from_cos(rx * W.right_circle_centre[0] + ty * W.right_circle_centre[1]);
 }
 
-// direct / diffuse [npos][n_full] float for the jobs k_pan_objects left.  Wave w of the launch takes jobs[w];
-// waves past *job_count leave at once.
-static __global__ void __launch_bounds__(64 * kExtentWaves)
-k_pan_objects_extent(PanParams P, ExtentTable E, const ExtentJob *jobs, const unsigned *job_count, const double *gain,
-                     const double *diffuse, float *direct, float *diff) {
-  const int lane = threadIdx.x & 63;
-  const unsigned wi = __builtin_amdgcn_readfirstlane(blockIdx.x * kExtentWaves + (threadIdx.x >> 6));
-  if (wi >= *job_count) return;  // (whole waves)
-  const ExtentJob &J = jobs[wi];
-  const size_t i = (size_t)J.pos;
+// One job rendered by a wave: what lane s (< E.n_pv) returns is the panner's output s of PolarExtent::handle
+// (:290-302), lanes past E.n_pv return 0.  Every lane of the wave calls it.
+__device__ inline double extent_render(const ExtentTable &E, const ExtentJob &J, int lane) {
   const int S = E.n_pv;
   const int n_pass = J.n_pass;
   // lane c looks at chunk c: the angle between its mean direction and the object's
@@ -244,8 +237,14 @@ k_pan_objects_extent(PanParams P, ExtentTable E, const ExtentJob *jobs, const un
     fin = n_pass == 2 ? fin + v * v : v;
   }
   if (n_pass == 2) fin = sqrt(fin / 2.0);  // (:297-299)
-  // lane c writes channel c of the full layout: the panner output that feeds it (none: an LFE channel), gain,
-  // sqrt(1 - diffuse) / sqrt(diffuse) (gain_calculator_objects.cpp:47-56)
+  return fin;
+}
+
+// lane c writes channel c of the full layout for position i: the panner output that feeds it (none: an LFE
+// channel) out of the lanes' fin, gain, sqrt(1 - diffuse) / sqrt(diffuse) (gain_calculator_objects.cpp:47-56).
+// Every lane of the wave calls it.
+__device__ inline void extent_write(const PanParams &P, double fin, size_t i, int lane, const double *gain,
+                                    const double *diffuse, float *direct, float *diff) {
   const int src = lane < P.n_full ? P.real_of_full[lane] : -1;
   const double got = __shfl(fin, src < 0 ? 0 : src);
   if (lane < P.n_full) {
@@ -254,6 +253,18 @@ k_pan_objects_extent(PanParams P, ExtentTable E, const ExtentJob *jobs, const un
     direct[i * P.n_full + lane] = (float)(v * sqrt(1.0 - df));
     diff[i * P.n_full + lane] = (float)(v * sqrt(df));
   }
+}
+
+// direct / diffuse [npos][n_full] float for the jobs k_pan_objects left.  Wave w of the launch takes jobs[w];
+// waves past *job_count leave at once.
+static __global__ void __launch_bounds__(64 * kExtentWaves)
+k_pan_objects_extent(PanParams P, ExtentTable E, const ExtentJob *jobs, const unsigned *job_count, const double *gain,
+                     const double *diffuse, float *direct, float *diff) {
+  const int lane = threadIdx.x & 63;
+  const unsigned wi = __builtin_amdgcn_readfirstlane(blockIdx.x * kExtentWaves + (threadIdx.x >> 6));
+  if (wi >= *job_count) return;  // (whole waves)
+  const ExtentJob &J = jobs[wi];
+  extent_write(P, extent_render(E, J, lane), (size_t)J.pos, lane, gain, diffuse, direct, diff);
 }
 
 }  // namespace earhip
