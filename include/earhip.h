@@ -73,7 +73,8 @@ int earhip_ctx_set_strict(earhip_ctx *ctx, int strict);
  * changes it — no process call reads the environment.  An option takes effect for calls / objects made after it is
  * set.  Unknown key, or a value that is not an integer ("abc", "1x"): EARHIP_INVALID_ARGUMENT, nothing changed (a context
  * is not created from an environment that holds such a value).
- *   gain stage:   MFMA (0 VALU | 1 exact-f32 MFMA | 3 default | 4 grid kernel | 5 piece lists | 6 hinge kernel),
+ *   gain stage:   MFMA (0 VALU | 1 exact-f32 MFMA | 3 default | 4 grid kernel (curves off its grid: up to 1024 objects per workgroup,
+ *                 beyond them the exact-f32 kernel) | 5 piece lists | 6 hinge kernel),
  *                 H2_TILE, P2_TILE, HG_TILE (256 | 512), P2_PAIRS, HINGE (0 | 1), H2_WGS, P2_WGS (workgroups of the launch;
  *                 P2_WGS 0: one per tile), H2_PAIR (1: the 8-wave grid kernel's plain and wide forms as a pair of launches instead of one kernel that
  *                 branches on the device's mode word: rounds 1-5), H2_RUNS (1: a workgroup of the grid kernel takes a contiguous run of tiles instead of

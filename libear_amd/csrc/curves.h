@@ -781,8 +781,23 @@ inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, in
   // gains allow): f16x2 when the gains can be scaled into f16 range — its cost does not depend on the
   // curves and is below the f32 slot kernel's even for static gains.  Curve sets with non-finite gains
   // stay on the f32 slot kernel.
-  const bool split = mfma && M >= 32 && gain_scale > 0.0f && ctx->use_mfma != 5 && ctx->use_mfma != 6 &&
-                     (ctx->use_mfma == 4 || (ctx->use_mfma == 3 && aligned));
+  bool split = mfma && M >= 32 && gain_scale > 0.0f && ctx->use_mfma != 5 && ctx->use_mfma != 6 &&
+               (ctx->use_mfma == 4 || (ctx->use_mfma == 3 && aligned));
+  // grid-level object splits of the kernels that take all objects of their split per workgroup (below): few tiles (block mode)
+  // split the objects across workgroups
+  auto object_splits = [&](int ntiles) {
+    int g = 1;
+    const int nz = cp.mnz * cp.mgroups;
+    while (g < max_gsplit && ntiles * nz * g < 2 * ctx->num_cus && M / (g * 2) >= 64) g *= 2;
+    return g;
+  };
+  // Forced (4) onto curves OFF its grid, this kernel sends every object with a point inside a tile through its exact path: product
+  // after product onto the tile's running totals, a chain as long as the workgroup's share of the objects — what the planner's own
+  // choice never meets (at most M / 64 objects off the grid, aligned_tile).  Always-ramping curves, the whole list through one
+  // workgroup (GSPLIT = 1): 1.37 / 1.44 / 1.30 times libear's own distance from a float64 render at 1536 / 4096 / 8192 objects
+  // (1.01e-6 / 1.65e-6 / 2.24e-6), where every other kernel stays below it.  So, as for the paired lists above: up to 1024 objects per
+  // workgroup; beyond, the exact f32 slot kernel, whose waves split the list (below) — 0.68 / 0.72 times libear's at 1536 / 8192.
+  if (split && !aligned && M / object_splits((nsamples + 255) / 256) > 1024) split = false;
   // long calls on a 512 grid: 8-wave workgroups on 512-sample tiles (two rounds of workgroups or more:
   // 512 blocks of 512: K1 0.215 vs 0.236 ms; one round, 256 blocks: 0.127 vs 0.120)
   // (EARHIP_H2_TILE=256|512 forces one of them where the curves allow it: tests, tuning)
@@ -881,10 +896,7 @@ inline MixLaunch plan_mix(const earhip_ctx *ctx, const ColumnPlan &cp, int M, in
     // split; few tiles (block mode): split the objects across workgroups
     L.wsplit = 1;
     L.tpw = 1;
-    int g = 1;
-    const int nz = cp.mnz * cp.mgroups;
-    while (g < max_gsplit && L.ntiles * nz * g < 2 * ctx->num_cus && M / (g * 2) >= 64) g *= 2;
-    L.gsplit = g;
+    L.gsplit = object_splits(L.ntiles);
     return L;
   }
   if (strict) {

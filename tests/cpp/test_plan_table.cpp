@@ -131,6 +131,25 @@ static std::vector<Case> cases() {
   add(exact_grid("f32grid_M16")).M = 16;
   add(exact_grid("f32grid_no_scale")).st.gain_scale = 0.0f;
   for (int ncols : {5, 24}) add(exact_grid("f32grid_cols")).ncols = ncols;
+  // ---- above 1024 objects: the plans tests/many_objects_cases.py writes down for its short calls on one bus of 10 columns (one
+  // call of 1024 samples on the 512-sample grid, one of 768 on the 256-sample grid), every forced kernel, with and without
+  // object splits across workgroups; and the 16-bit object index on 6 columns
+  for (int max_gsplit : {16, 1})
+    for (int M : {1536, 2048, 4096, 4097, 8192, 8193})
+      for (int nsamples : {1024, 768})
+        for (int mfma : {1, 3, 4, 5, 6}) {
+          auto set = [&](Case &c) { c.M = M, c.ncols = 10, c.nsamples = nsamples, c.max_gsplit = max_gsplit, c.use_mfma = mfma; };
+          Case &g = add(on_grid(max_gsplit == 16 ? "many_grid" : "many_grid_gsplit1"));
+          set(g), g.st.ramp_share = 1.0, g.st.pair_waste256 = 0.0, g.st.hinge_exact_share = 0.0;
+          g.st.aligned_tile = nsamples % 512 ? 256 : 512, g.st.grid512_strict = nsamples % 512 == 0;
+          set(add(holding(max_gsplit == 16 ? "many_holding" : "many_holding_gsplit1"))), v.back().st.hinge_exact_share = 0.0;
+          set(add(ramping(max_gsplit == 16 ? "many_ramping" : "many_ramping_gsplit1")));
+        }
+  for (int M : {kMaxPieceObjects, kMaxPieceObjects + 1})
+    for (int mfma : {1, 3, 5}) {
+      Case &c = add(holding("many_holding_index16"));
+      c.M = M, c.ncols = 6, c.nsamples = 512, c.use_mfma = mfma, c.st.hinge_exact_share = 0.0;
+    }
   return v;
 }
 
