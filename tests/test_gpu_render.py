@@ -691,7 +691,16 @@ def test_grid_kernel_several_tiles_per_workgroup(layout, tile, wgs):
 SPLIT_KERNELS = [("grid", {"EARHIP_MFMA": None, "EARHIP_H2_TILE": "256"}, 3, 256), ("grid", {"EARHIP_MFMA": None, "EARHIP_H2_TILE": "512"}, 3, 512),
                  ("hinge", {"EARHIP_MFMA": "6", "EARHIP_HG_TILE": "256"}, 5, 256), ("hinge", {"EARHIP_MFMA": "6", "EARHIP_HG_TILE": "512"}, 5, 512)]
 SPLIT_IDS = ["grid-256", "grid-512", "hinge-256", "hinge-512"]
+# the piece-list kernel keeps its own copies of those blocks (gain_p2.h): both tile sizes, packed and paired lists
+SPLIT_KERNELS += [("pieces", {"EARHIP_MFMA": "5", "EARHIP_P2_TILE": str(t), "EARHIP_P2_PAIRS": str(p)}, 4, t) for t in (256, 512) for p in (0, 1)]
+SPLIT_IDS += [f"pieces-{t}-{'paired' if p else 'packed'}" for t in (256, 512) for p in (0, 1)]
 _split_oracle = {}
+
+
+def split_lists_expected(kind, opts):
+    """last_list_layout() of a SPLIT_KERNELS row: paired or packed lists as asked for, the hinge kernel's (packed) stand by, the grid
+    kernel builds none"""
+    return {"grid": None, "hinge": False}.get(kind, opts.get("EARHIP_P2_PAIRS") == "1")
 
 
 def split_paths_case(kind, tile, layout, bursts, two_bus):
@@ -710,7 +719,7 @@ def split_paths_case(kind, tile, layout, bursts, two_bus):
 @pytest.mark.parametrize("layout", ["0+5+0", "9+10+3"])
 @pytest.mark.parametrize("kind,opts,kernel,tile", SPLIT_KERNELS, ids=SPLIT_IDS)
 def test_split_kernels_exact_paths_vs_oracle(kind, opts, kernel, tile, layout):
-    """The rare paths of the grid and the hinge kernel, each forced, in one call of 5 blocks of 256 that starts at sample 37 (the
+    """The rare paths of the grid, the hinge and the piece-list kernel, each forced, in one call of 5 blocks of 256 that starts at sample 37 (the
     last 512-sample tile is ragged; the grid kernel's curves have a point every 256 or every 512 samples, so that its 4-wave and its
     8-wave kernels both run): two objects off the grid (the exact path inside tiles, beside the split operands of the
     others) and bursts 10^4 above the probed level in two tiles (their totals overflow: the overflow redo, per wave).  5 channels on
@@ -728,7 +737,7 @@ def test_split_kernels_exact_paths_vs_oracle(kind, opts, kernel, tile, layout):
             set_renderer_curves(r, [(t + sp["start"], d, f) for t, d, f in curves], True)
             r.reset(sp["start"])
             out = r.process(x)
-            plan = r.last_plan()
+            plan = dict(r.last_plan(), lists=r.last_list_layout(), wide=r.wide_form())
             r.close()
         finally:
             c.close()
@@ -738,6 +747,8 @@ def test_split_kernels_exact_paths_vs_oracle(kind, opts, kernel, tile, layout):
     err = scenes.rel_rms_per_channel(got, want)
     print(kind, opts, layout, plan, err)
     assert plan["kernel"] == kernel and plan["tile"] == tile, plan
+    # (a call this short runs the wide form, whatever the device would pick: api_core.hip, acquire_call_words)
+    assert plan["lists"] == split_lists_expected(kind, opts) and plan["wide"] is True, plan
     assert np.isfinite(got).all()
     assert err <= 1e-6, (err, plan)
 
@@ -765,7 +776,7 @@ def test_split_kernels_unaligned_rows_vs_oracle(kind, opts, kernel, tile, layout
             out = torch.full((n, total + 1), 7.5, dtype=torch.float32, device="cuda")
             r.process_device(sp["nblocks"], xin.data_ptr(), total, out.data_ptr(), total + 1)
             c.synchronize()
-            plan = r.last_plan()
+            plan = dict(r.last_plan(), lists=r.last_list_layout(), wide=r.wide_form())
             r.close()
         finally:
             c.close()
@@ -775,6 +786,7 @@ def test_split_kernels_unaligned_rows_vs_oracle(kind, opts, kernel, tile, layout
     err = scenes.rel_rms_per_channel(got[:, :total], want)
     print(kind, opts, layout, plan, err)
     assert plan["kernel"] == kernel and plan["tile"] == tile and plan["gsplit"] == 1, plan
+    assert plan["lists"] == split_lists_expected(kind, opts) and plan["wide"] is True, plan
     assert np.isfinite(got).all()
     assert err <= 1e-6, (err, plan)
     assert np.all(got[:, total] == 7.5)
