@@ -1378,6 +1378,74 @@ int earhip_src_process(earhip_src *src, size_t nsamples, const float *const *in,
  * above, beta < 0, a cutoff outside (0, 1] or a non-finite argument is EARHIP_INVALID_ARGUMENT. */
 int earhip_src_design(int up, int down, int taps_per_phase, double beta, double cutoff, double *out);
 
+/* ------------------------------------------------------------------------
+ * (Q) Ambisonic encoder for Objects, and a rotation of the HOA bus — the way INTO the scene-based domain: Objects positions
+ * become the gain vectors of an Ambisonics bus (for a scene-based ADM pack, an AmbiX / FuMa file, or binaural monitoring through
+ * the SH domain), where earhip_hoa_decode_matrix (group I) is the way out of it.  libear has no counterpart; the conventions
+ * are those of its hoa::sph_harm (src/hoa/hoa.hpp:99-112) and therefore of the decoder: D_norm * enc_norm does not depend on
+ * the normalization.
+ *
+ * CHANNELS.  Input channel c of the bus is the pair (n, m) = (orders[c], degrees[c]), 1 <= n_coef <= 64, 0 <= n <= 7,
+ * |m| <= n.  Any subset, order or repetition of channels is accepted (AmbiX: earhip_hoa_acn; FuMa W X Y Z: (0,0) (1,1) (1,-1)
+ * (1,0)).  normalization is "N3D", "SN3D" or "FuMa"; FuMa requires n <= 3.  An unknown normalization name is EARHIP_ADM_ERROR,
+ * as in the decoder; any other violation is EARHIP_INVALID_ARGUMENT.
+ *
+ * THE ENCODED VALUE, exactly (a caller can reproduce it).  A source at ADM polar azimuth az and elevation el (degrees, azimuth
+ * anticlockwise-positive: +90 is left) with linear gain g gives, with a = |m|,
+ *     out[i][c] = (float)( g * K(n, a) * P_n^a(x) * T_m(r) ),    x = sin(el * pi/180),   r = fmod(az, 360) * pi/180
+ * in float64, the product taken from left to right, ONE rounding to float32 at the end (pi/180 is the double nearest to it, fmod
+ * is exact, so any finite azimuth is reduced without error before the conversion to radians, as in group K).
+ *   P_n^a is the associated Legendre function WITHOUT the Condon-Shortley phase, by upward recurrence in n:
+ *     s = sqrt((1 - x) * (1 + x));   P_a^a = 1 * (1 s) * (3 s) * ... * ((2a - 1) s), one factor (2i - 1) * s at a time;
+ *     P_(a+1)^a = x * (2a + 1) * P_a^a;   P_l^a = (x * (2l - 1) * P_(l-1)^a - (l + a - 1) * P_(l-2)^a) / (l - a).
+ *   T_m(r) = sqrt2 * cos(m r) for m > 0, 1 for m = 0, -sqrt2 * sin(m r) for m < 0 (m r is the product of the integer m, as a
+ *     double, and r).
+ *   K(n, a): SN3D = sqrt((n - a)! / (n + a)!); N3D = sqrt(2n + 1) * SN3D; FuMa = f[n][a] * SN3D with f = 1/sqrt2 for (0,0);
+ *     1 for (1,0) (1,1) (2,0) (3,0); 2/sqrt3 for (2,1) (2,2); sqrt(45/32) for (3,1); 3/sqrt5 for (3,2); sqrt(8/5) for (3,3).
+ * So W = g (SN3D, N3D) or g / sqrt2 (FuMa), and N3D at az 90, el 0 has Y_1^-1 = sqrt3, Y_1^1 = 0.
+ * The host form and the device kernel run these operations in this order (one shared core, csrc/hoa_encode.h); they differ only
+ * in the math library behind sin, cos, sqrt and fmod, so an output of one is the other's float or its neighbour.
+ *
+ * earhip_hoa_acn fills (max_order + 1)^2 pairs in ACN order: channel k is n = floor(sqrt k), m = k - n^2 - n; 0 <= max_order
+ * <= 7.  Pure host.
+ * earhip_hoa_encode is a pure host function, no context and no device (like the host forms of group K it is a deliberate CPU
+ * computation on the calling thread, not a fall-back of the device form).  gain may be NULL (1).  out: [n][n_coef] float,
+ * row-major.  A non-finite azimuth, elevation or gain, or |el| > 90, is EARHIP_INVALID_ARGUMENT, the message naming the
+ * element's index; the rows before it are written, its row and those after it are not.
+ * earhip_hoa_encode_device takes SoA float64 device arrays of n elements (device-reachable host memory included; gain_dev may be
+ * NULL) and out_dev [n][n_coef] float; it runs ONE kernel on the context's stream, allocates nothing, does not synchronise and
+ * never computes on the CPU.  It cannot refuse an element: an element the host form refuses gets NaN in all its n_coef outputs
+ * and status 1, every other element status 0 (status_dev: int[n], may be NULL).  n == 0 is a no-op; n < 2^31.  The kernel
+ * gives a wave 64 positions: each lane evaluates its position's Legendre and trigonometric terms once, and the wave's 64 rows
+ * leave through LDS as full-width stores; no atomics, the same input gives the same bits.
+ * As gain curves: a direct-only renderer (group F, n_buses = 1, n_out = n_coef) is an Ambisonics bus as soon as its curves
+ * hold these rows (earhip_render_set_object_points).
+ *
+ * earhip_hoa_rotation_matrix (pure host): the matrix that turns the bus.  q: double[9], row-major, acting on ADM Cartesian
+ * column vectors (x right, y front, z up): a source at u moves to q u.  q must be orthonormal with determinant +1 (every entry
+ * of q q^T - I and det q - 1 within 1e-9), else EARHIP_INVALID_ARGUMENT.  out: [n_coef][n_coef] float, row-major, with the
+ * DEFINING PROPERTY: for every direction u,  enc(q u) = out * enc(u)  — for a channel list that holds every degree of each of
+ * its orders exactly once (a rotation mixes the 2n + 1 channels of an order among themselves); for any other list out[i][j] is
+ * still the coefficient of channel j's harmonic in the rotated harmonic of channel i.  Entries between channels of different
+ * order are exactly 0.  It is computed by quadrature over the 5200-point spherical t-design the decoder uses, in N3D,
+ *     R[i][j] = (1/5200) * sum_p Y_i(q x_p) Y_j(x_p),   out[i][j] = (float)( R[i][j] * (K(i) / K_N3D(i)) * (K_N3D(j) / K(j)) )
+ * (the design integrates products of harmonics up to order 7 to 2.3e-12; the property holds to 2.4e-11 before the rounding to
+ * float).  How to apply it: a static rotation by earhip_interp_apply_constant (n_in = n_out = n_coef, point[j * n_coef + i] =
+ * out[i][j]: input channel j to output channel i); a head-tracked one as the interpolation points of earhip_gain_interp_*
+ * (group A'), one matrix per head pose at its sample time.
+ *
+ * Out of scope: extent or diffuse in the SH domain, per-order weights (max-rE, in-phase), orders above 7, near-field
+ * compensation, attaching anything to a renderer, a device form of the rotation matrix (64 x 64 host arithmetic per head pose).
+ * ---------------------------------------------------------------------- */
+int earhip_hoa_acn(int max_order, int *orders, int *degrees);
+int earhip_hoa_encode(int n_coef, const int *orders, const int *degrees, const char *normalization, size_t n,
+                      const double *azimuth, const double *elevation, const double *gain, float *out);
+int earhip_hoa_encode_device(earhip_ctx *ctx, int n_coef, const int *orders, const int *degrees, const char *normalization,
+                             size_t n, const double *azimuth_dev, const double *elevation_dev, const double *gain_dev,
+                             float *out_dev, int *status_dev);
+int earhip_hoa_rotation_matrix(int n_coef, const int *orders, const int *degrees, const char *normalization, const double *q,
+                               float *out);
+
 #ifdef __cplusplus
 }
 #endif

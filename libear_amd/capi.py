@@ -817,6 +817,64 @@ def hoa_decode_matrix(ctx, layout, orders, degrees, normalization="SN3D", positi
     return out[:, :len(o)]
 
 
+# (Q) Ambisonic encoder for Objects and the rotation of the HOA bus
+
+def _hoa_channels(orders, degrees):
+    o = np.ascontiguousarray(orders, np.int32).reshape(-1)
+    d = np.ascontiguousarray(degrees, np.int32).reshape(-1)
+    if len(o) != len(d):
+        raise InvalidArgument(INVALID_ARGUMENT, "orders and degrees must be the same size")
+    ip = C.POINTER(C.c_int)
+    return len(o), o, d, o.ctypes.data_as(ip), d.ctypes.data_as(ip)
+
+
+def hoa_acn(order):
+    """(orders, degrees) of the (order + 1)^2 channels in ACN order (AmbiX)"""
+    n = (max(int(order), 0) + 1) ** 2
+    o, d = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ip = C.POINTER(C.c_int)
+    check(load().earhip_hoa_acn(int(order), o.ctypes.data_as(ip), d.ctypes.data_as(ip)))
+    return o, d
+
+
+def hoa_encode(orders, degrees, az, el, gain=None, normalization="SN3D"):
+    """Objects positions (ADM polar degrees) -> the gain rows of an Ambisonics bus, float32 [n][n_coef], on the calling
+    thread (no device needed).  Raises on the first element that is not finite or has |el| > 90, the message naming it."""
+    f64 = C.POINTER(C.c_double)
+    nc, _o, _d, op, dp = _hoa_channels(orders, degrees)
+    az = np.ascontiguousarray(np.atleast_1d(az), np.float64)
+    n = az.size
+    el = np.ascontiguousarray(np.broadcast_to(np.asarray(el, np.float64), (n,)))
+    g = None if gain is None else np.ascontiguousarray(np.broadcast_to(np.asarray(gain, np.float64), (n,)))
+    out = np.zeros((n, max(nc, 1)), np.float32)
+    check(load().earhip_hoa_encode(nc, op, dp, normalization.encode(), C.c_size_t(n), _ptr(az, f64), _ptr(el, f64),
+                                   None if g is None else _ptr(g, f64), _ptr(out)))
+    return out[:, :nc]
+
+
+def hoa_encode_device(ctx, n, az, el, gain, out, orders, degrees, normalization="SN3D", status=None):
+    """the same on the device: float64 tensors (or device addresses) of n elements, gain may be None (1), out a float32
+    tensor [n][n_coef], status an int32 tensor [n] (may be None): 1 and a row of NaN for an element hoa_encode refuses.
+    Enqueues one kernel on the context's stream and does not synchronise."""
+    nc, _o, _d, op, dp = _hoa_channels(orders, degrees)
+    check(load().earhip_hoa_encode_device(ctx.h, nc, op, dp, normalization.encode(), C.c_size_t(n),
+                                          _dev_ptr(az, n, "float64"), _dev_ptr(el, n, "float64"),
+                                          _dev_ptr(gain, n, "float64"), _dev_ptr(out, n * nc, "float32"),
+                                          _dev_ptr(status, n, "int32")))
+
+
+def hoa_rotation_matrix(orders, degrees, q, normalization="SN3D"):
+    """float32 [n_coef][n_coef] R with encode(q u) = R encode(u); q: a proper rotation, 3 x 3, acting on ADM Cartesian
+    column vectors (x right, y front, z up)"""
+    nc, _o, _d, op, dp = _hoa_channels(orders, degrees)
+    q = np.ascontiguousarray(q, np.float64)
+    if q.size != 9:
+        raise InvalidArgument(INVALID_ARGUMENT, "q must have 9 entries")
+    out = np.zeros((max(nc, 1), max(nc, 1)), np.float32)
+    check(load().earhip_hoa_rotation_matrix(nc, op, dp, normalization.encode(), _ptr(q, C.POINTER(C.c_double)), _ptr(out)))
+    return out[:nc, :nc]
+
+
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4
 _PCM = {"s16": (PCM_S16, np.int16, 1), "s24": (PCM_S24, np.uint8, 3), "s32": (PCM_S32, np.int32, 1),
         "f32": (PCM_F32, np.float32, 1)}

@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "layout_table.h"
+#include "hoa_encode.h"
 #include "tdesign_5200.h"
 
 namespace earhip {
@@ -509,39 +510,13 @@ std::vector<PanRegion> build_regions(const LayoutEntry &L, int &n_real, const do
 }
 
 // ---- spherical harmonics (src/hoa/hoa.hpp:16-112; Boost.Math's Legendre functions and factorials from
-// their definitions)
-double factorial_d(int n) {
-  double f = 1.0;
-  for (int i = 2; i <= n; i++) f *= i;
-  return f;
-}
-// associated Legendre function P_n^m(x) without the Condon-Shortley phase, upward recurrence in n
-double legendre_nm(int n, int m, double x) {
-  const double root = std::sqrt((1.0 - x) * (1.0 + x));
-  double p0 = 1.0;
-  for (int i = 1; i <= m; i++) p0 *= (2.0 * i - 1.0) * root;  // P_m^m
-  if (n == m) return p0;
-  double p1 = x * (2.0 * m + 1.0) * p0;                         // P_(m+1)^m
-  for (int l = m + 2; l <= n; l++) {
-    const double p2 = (x * (2.0 * l - 1.0) * p1 - (l + m - 1.0) * p0) / (l - m);
-    p0 = p1;
-    p1 = p2;
-  }
-  return p1;
-}
-enum HoaNorm { kN3D, kSN3D, kFuMa };
-double hoa_norm(HoaNorm t, int n, int am) {
-  const double sn3d = std::sqrt(factorial_d(n - am) / factorial_d(n + am));
-  if (t == kSN3D) return sn3d;
-  if (t == kN3D) return std::sqrt(2.0 * n + 1.0) * sn3d;
-  // FuMa: defined up to order 3 (hoa.hpp:56-72)
-  static const double f[4][4] = {{0.70710678118654752440, 0, 0, 0},
-                                 {1.0, 1.0, 0, 0},
-                                 {1.0, 1.15470053837925152902, 1.15470053837925152902, 0},
-                                 {1.0, 1.18585412256314232322, 1.34164078649987381784, 1.26491106406735172760}};
-  if (n > 3) fail_invalid("FuMa normalisation is defined up to order 3");
-  return f[n][am] * sn3d;
-}
+// their definitions): hoa_encode.h, shared with the encoder of group Q
+using hoa::HoaNorm;
+using hoa::hoa_norm;
+using hoa::kFuMa;
+using hoa::kN3D;
+using hoa::kSN3D;
+using hoa::legendre_nm;
 
 // ---- channel lock and zone exclusion: the small tables of a layout (include/earhip.h group I, the objects forms)
 struct ObjSpeaker {
