@@ -320,7 +320,9 @@ int earhip_design_decorrelators_for_layout(const char *layout, int without_lfe, 
  * positions per call (one device thread each, double precision): what a renderer needs
  * per (object, metadata block).  Not implemented, as in libear's own calculate(): Cartesian
  * positions, divergence, channel lock, zone exclusion, screen scaling — of these the _objects
- * forms below carry divergence, channel lock and zone exclusion.
+ * forms below carry divergence, channel lock and zone exclusion; screen scaling and screen edge
+ * lock are a stage of their own in front of them (group R), Cartesian positions come in through
+ * group K.
  * The _extent forms add libear's polar extent panner (src/object_based/polar_extent.cpp:
  * 12-302 with its core, polar_extent_scalar.cpp:25-108): width and height in degrees, depth in
  * distance units, each may be NULL (0); one wave per position sums the point source panner's
@@ -1445,6 +1447,81 @@ int earhip_hoa_encode_device(earhip_ctx *ctx, int n_coef, const int *orders, con
                              float *out_dev, int *status_dev);
 int earhip_hoa_rotation_matrix(int n_coef, const int *orders, const int *degrees, const char *normalization, const double *q,
                                float *out);
+
+/* ------------------------------------------------------------------------
+ * (R) The screen of an Objects block: screenRef scaling and screenEdgeLock (ITU-R BS.2127-0 sections 7.3.3 and 7.3.4).  libear
+ * refuses screenRef (src/object_based/gain_calculator_objects.cpp:37-44) and so does every calculator of group I; this group is
+ * the stage that turns a reference screen and a reproduction screen into positions.  In the renderer's order both steps are
+ * transforms of the polar position that run before channel lock, divergence, extent and zone exclusion, so the stage stands in
+ * front of earhip_panner_calculate_objects[_device] as group K does: SoA float64 arrays, rewritten in place on the device, which
+ * the panner then reads.  A Cartesian block goes earhip_conversion_to_polar_device, this stage, the panner: three launches and
+ * no host round trip.  Distance is never changed by either step, so it is not an argument.  This comment is the specification.
+ *
+ * A SCREEN is earhip_screen: cartesian 0 is libear's PolarScreen (aspect_ratio, centre azimuth / elevation / distance,
+ * width_azimuth: the full width in degrees), anything else its CartesianScreen (aspect_ratio, centre x / y / z, width_x: the
+ * full width); the fields of the other kind are not read.  earhip_screen_default: polar, 1.78, (0, 0, 1), 58 degrees.
+ *
+ * EDGES (earhip_screen_edges, pure host, float64): edges[4] = left azimuth, right azimuth, bottom elevation, top elevation, in
+ * degrees.  With cart(az, el, d) = (sin(-az) cos(el) d, cos(-az) cos(el) d, sin(el) d), azim(v) = -atan2(v.x, v.y) and
+ * elev(v) = atan2(v.z, hypot(v.x, v.y)):
+ *   polar:     c = cart(az, el, d), W = d tan(width_azimuth / 2), H = W / aspect_ratio,
+ *              xv = W cart(az - 90, 0, 1), zv = H cart(az, el + 90, 1);
+ *   Cartesian: c = (x, y, z), W = width_x / 2, H = W / aspect_ratio, xv = (W, 0, 0), zv = (0, 0, H);
+ *   both:      left = azim(c - xv), right = azim(c + xv), bottom = elev(c - zv), top = elev(c + zv).
+ * The default screen's edges are 29, -29, -17.297..., 17.297....  EARHIP_INVALID_ARGUMENT, the message naming the field: a
+ * non-finite field; aspect_ratio <= 0; width_azimuth outside (0, 180) or width_x <= 0; a polar distance <= 0 or |elevation| >
+ * 90; edges that do not satisfy -180 < right < left < 180 and -90 < bottom < top < 90 (a screen across the rear seam or over a
+ * pole, where the scaling has no ordered breakpoints).
+ *
+ * APPLY, per element i.  A NULL reference is the default screen.  With a NULL reproduction both steps are the identity: every
+ * element is copied bit for bit and none is checked.  A NULL flag array means all 0, except a NULL screen_ref, which means all
+ * 1.  Lock codes: horizontal 0 none, 1 left, 2 right; vertical 0 none, 1 bottom, 2 top.
+ *   1. An element with screen_ref[i] == 0 and both lock codes 0 is copied bit for bit, whatever it holds (a NaN too; status 0).
+ *   2. Any other element is checked first: a non-finite azimuth or elevation, |azimuth| > 2^40 (group K's bound), |elevation| >
+ *      90 or a lock code above 2 is refused.  The host form returns EARHIP_INVALID_ARGUMENT, the message naming the index; the
+ *      elements before it are written, it and those after it are not.  The device form cannot refuse: such an element gets NaN
+ *      in both outputs and status[i] = 1, every other element status[i] = 0 (status: int[n], may be NULL).
+ *   3. SCALE, when screen_ref[i] is nonzero.  a = fmod(azimuth, 360), then one step of -+360 brings it into [-180, 180] (fmod is
+ *      exact, as in group K).  The new azimuth is the piecewise-linear map of a through the breakpoints (-180, ref.right,
+ *      ref.left, 180) -> (-180, rep.right, rep.left, 180); the new elevation that of the elevation through (-90, ref.bottom,
+ *      ref.top, 90) -> (-90, rep.bottom, rep.top, 90).  A segment is (x0, y0, slope), slope = (y1 - y0) / (x1 - x0) computed on
+ *      the host; the segment of x is the one whose x0 is the largest breakpoint <= x; the value is fma(slope, x - x0, y0), ONE
+ *      explicit fused multiply-add on host and device alike.  x >= 180 gives exactly 180 and x >= 90 exactly 90: the seam and
+ *      the poles map to themselves, and a reference edge maps to the reproduction edge exactly.
+ *   4. LOCK, after the scale: horizontal 1 / 2 sets the azimuth to rep.left / rep.right, vertical 1 / 2 the elevation to
+ *      rep.bottom / rep.top.
+ *   5. A component that is neither scaled nor locked keeps its input bits (the azimuth under a vertical lock alone is not even
+ *      reduced).
+ * Each output may alias its own input, so the stage can run in place.  n == 0 is a no-op; n < 2^31.
+ *
+ * earhip_screen_apply is a deliberate CPU computation on the calling thread, no context and no device, like the host forms of
+ * group K.  earhip_screen_apply_device takes the two screens in host memory and the arrays as device pointers (device-reachable
+ * host memory included); it runs ONE kernel on the context's stream (one thread per element, the six segments a by-value
+ * argument), allocates nothing, does not synchronise and never computes on the CPU.  The per-element arithmetic has no libm call
+ * but the exact fmod and its only contraction is explicit (one shared core, csrc/screen.h), so THE DEVICE FORM RETURNS THE HOST
+ * FORM'S BITS.
+ *
+ * Out of scope: screenRef for HOA, screenEdgeLock for DirectSpeakers (still refused), a reproduction screen on a layout,
+ * fusing the stage into the producer's kernels.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_screen {
+  int cartesian;                       /* 0: PolarScreen, else CartesianScreen */
+  double aspect_ratio;
+  double azimuth, elevation, distance; /* polar centrePosition */
+  double x, y, z;                      /* Cartesian centrePosition */
+  double width_azimuth;                /* polar: full width in degrees */
+  double width_x;                      /* Cartesian: full width */
+} earhip_screen;
+
+int earhip_screen_default(earhip_screen *out);
+int earhip_screen_edges(const earhip_screen *s, double edges[4]);
+int earhip_screen_apply(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *azimuth,
+                        const double *elevation, const unsigned char *screen_ref, const unsigned char *lock_horizontal,
+                        const unsigned char *lock_vertical, double *azimuth_out, double *elevation_out);
+int earhip_screen_apply_device(earhip_ctx *ctx, const earhip_screen *reference, const earhip_screen *reproduction, size_t n,
+                               const double *azimuth, const double *elevation, const unsigned char *screen_ref,
+                               const unsigned char *lock_horizontal, const unsigned char *lock_vertical, double *azimuth_out,
+                               double *elevation_out, int *status);
 
 #ifdef __cplusplus
 }

@@ -875,6 +875,70 @@ def hoa_rotation_matrix(orders, degrees, q, normalization="SN3D"):
     return out[:nc, :nc]
 
 
+# (R) the screen of an Objects block: screenRef scaling and screenEdgeLock
+
+class Screen(C.Structure):
+    """earhip_screen: a PolarScreen (cartesian 0) or a CartesianScreen"""
+    _fields_ = [("cartesian", C.c_int)] + [(k, C.c_double) for k in (
+        "aspect_ratio", "azimuth", "elevation", "distance", "x", "y", "z", "width_azimuth", "width_x")]
+
+    @classmethod
+    def polar(cls, aspect_ratio, azimuth, elevation, distance, width_azimuth):
+        return cls(0, aspect_ratio, azimuth, elevation, distance, 0.0, 0.0, 0.0, width_azimuth, 0.0)
+
+    @classmethod
+    def cart(cls, aspect_ratio, x, y, z, width_x):
+        return cls(1, aspect_ratio, 0.0, 0.0, 0.0, x, y, z, 0.0, width_x)
+
+
+def _screen_ref(s):
+    return None if s is None else C.byref(s)
+
+
+def screen_default():
+    """the default reference screen: polar, 1.78, straight ahead at distance 1, 58 degrees wide"""
+    s = Screen()
+    check(load().earhip_screen_default(C.byref(s)))
+    return s
+
+
+def screen_edges(screen):
+    """(left azimuth, right azimuth, bottom elevation, top elevation) of a screen, degrees (pure host)"""
+    e = (C.c_double * 4)()
+    check(load().earhip_screen_edges(C.byref(screen), e))
+    return tuple(e)
+
+
+def screen_apply(az, el, reproduction, reference=None, screen_ref=None, lock_horizontal=None, lock_vertical=None):
+    """screenRef scaling from `reference` (None: the default screen) to `reproduction` (None: no screen, everything passes
+    through), then screenEdgeLock, on the calling thread (no device needed).  Arrays [n] in degrees -> (azimuth, elevation).
+    screen_ref: flags, None = all set; lock_horizontal: 0 none, 1 left, 2 right; lock_vertical: 0 none, 1 bottom, 2 top; None =
+    none.  Raises on the first element it refuses, the message naming its index."""
+    f64, u8 = C.POINTER(C.c_double), C.POINTER(C.c_ubyte)
+    az = np.ascontiguousarray(np.atleast_1d(az), np.float64)
+    n = az.size
+    el = np.ascontiguousarray(np.broadcast_to(np.asarray(el, np.float64), (n,)))
+    flags = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.uint8), (n,)))
+             for v in (screen_ref, lock_horizontal, lock_vertical)]
+    az_out, el_out = np.empty(n, np.float64), np.empty(n, np.float64)
+    check(load().earhip_screen_apply(_screen_ref(reference), _screen_ref(reproduction), C.c_size_t(n), _ptr(az, f64),
+                                     _ptr(el, f64), *[None if v is None else _ptr(v, u8) for v in flags], _ptr(az_out, f64),
+                                     _ptr(el_out, f64)))
+    return az_out, el_out
+
+
+def screen_apply_device(ctx, n, az, el, az_out, el_out, reproduction, reference=None, screen_ref=None, lock_horizontal=None,
+                        lock_vertical=None, status=None):
+    """the same on the device: float64 tensors (or device addresses) of n elements, the flags uint8 tensors, status an int32
+    tensor [n] (may be None): 1 and NaN outputs for an element screen_apply refuses.  An output may be its own input (in
+    place).  Enqueues one kernel on the context's stream and does not synchronise."""
+    check(load().earhip_screen_apply_device(ctx.h, _screen_ref(reference), _screen_ref(reproduction), C.c_size_t(n),
+                                            _dev_ptr(az, n, "float64"), _dev_ptr(el, n, "float64"),
+                                            _dev_ptr(screen_ref, n, "uint8"), _dev_ptr(lock_horizontal, n, "uint8"),
+                                            _dev_ptr(lock_vertical, n, "uint8"), _dev_ptr(az_out, n, "float64"),
+                                            _dev_ptr(el_out, n, "float64"), _dev_ptr(status, n, "int32")))
+
+
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4
 _PCM = {"s16": (PCM_S16, np.int16, 1), "s24": (PCM_S24, np.uint8, 3), "s32": (PCM_S32, np.int32, 1),
         "f32": (PCM_F32, np.float32, 1)}

@@ -1,7 +1,7 @@
 // ear/screen.hpp — the reference screen of ADM metadata (libear include/ear/screen.hpp:8-24, default
-// src/screen.cpp:4-6).  Carried by the metadata for source compatibility; screen-related rendering (screenRef) is
-// refused by the gain calculators, as in libear.  libear's boost::variant is a struct that converts from either
-// alternative here.
+// src/screen.cpp:4-6).  The gain calculators refuse screenRef, as in libear; screen scaling and screen edge lock are
+// a stage in front of them, ear::hip::ScreenHandler (hip_screen.hpp), which reads these types and hands back metadata
+// with screenRef cleared.  libear's boost::variant is a struct that converts from either alternative here.
 #pragma once
 #include "layout.hpp"
 
