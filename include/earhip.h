@@ -310,6 +310,42 @@ int earhip_layout_channel_ranges(const char *layout, int index, double azimuth_r
  * out: [channels kept][512] (include/ear/decorrelate.hpp:26-28) */
 int earhip_design_decorrelators_for_layout(const char *layout, int without_lfe, float *out);
 
+/* A loudspeaker layout of the caller's own — libear's Layout(name, channels) is a public constructor and its gain
+ * calculators take any such layout, triangulating it with a convex hull (src/common/point_source_panner.cpp:484-487,
+ * src/common/convex_hull.cpp).  Here a layout is DEFINED once under a name; from then on every function of this header
+ * that takes a layout name accepts it (groups H, I, L and the decorrelator design; earhip_layout_count /
+ * earhip_layout_name keep listing the BS.2051 layouts only).  Pure host code: no context, no device.  Definitions are
+ * process-wide, thread-safe, never removed or changed, and at most 256.
+ * earhip_layout_define: name non-empty, at most 63 characters, not a BS.2051 name; n_channels in [1, 32], of which at
+ * least one and at most 22 are not LFE (the objects kernels' lock and zone tables: more is EARHIP_NOT_IMPLEMENTED).
+ * Defining a name again with bit-identical content is EARHIP_OK and does nothing; with other content
+ * EARHIP_INVALID_ARGUMENT.  All geometry runs here, so that a bad layout fails when it is defined and not at the first
+ * create: the augmented loudspeaker set at the nominal positions (the loudspeakers that are not LFE, the extra ones
+ * above / below the mid layer, the virtual bottom, the virtual top unless the layout has T+000 or UH+180), its convex
+ * hull with libear's tolerance of 1e-5, and a dry run of the panner's region builder.  Three augmented vertices on a
+ * line — two loudspeakers in one direction are that — is EARHIP_INVALID_ARGUMENT ("collinear points in convex hull");
+ * a facet of more than 4 vertices EARHIP_INTERNAL_ERROR, as in libear; more than 16 loudspeakers around a virtual one
+ * EARHIP_NOT_IMPLEMENTED (this library's limit).  A defined layout always takes the full polar panner: only the
+ * BS.2051 layout 0+2+0 takes libear's stereo downmix. */
+typedef struct earhip_layout_channel_def {
+  const char *name;          /* non-empty, <= 31 characters, unique within the layout */
+  double azimuth, elevation; /* NOMINAL position, degrees, ADM convention; finite, |elevation| <= 90, azimuth in [-180, 180] */
+  int has_ranges;            /* 0: the allowed ranges are the nominal position itself */
+  double azimuth_range[2], elevation_range[2]; /* as earhip_layout_channel_ranges returns them */
+  int is_lfe;
+} earhip_layout_channel_def;
+int earhip_layout_define(const char *name, int n_channels, const earhip_layout_channel_def *channels);
+/* *kind: 0 unknown, 1 an ITU-R BS.2051 layout, 2 a defined one */
+int earhip_layout_kind(const char *name, int *kind);
+/* The triangulation of a layout, BS.2051 (its table) or defined (its hull): the augmented vertices at their nominal
+ * positions, xyz_nominal [V][3]; mix_to [V], the channel of the full layout a vertex's gain goes to (an extra
+ * loudspeaker: the mid-layer one under / over it; a virtual one, which come last: -1); and the facets as
+ * {n, v0 .. v(n-1)}* 0 with each facet's vertices ascending.  The counts are always written (*n_facet_ints includes the
+ * closing 0); an array is written when its pointer is not NULL, and then its capacity (vertices; ints) must suffice.
+ * 0+2+0 has no triangulation of its own: EARHIP_INVALID_ARGUMENT. */
+int earhip_layout_hull(const char *name, int vertex_capacity, double *xyz_nominal, int *mix_to, int *n_vertices,
+                       int *n_virtual, int facet_capacity, int *facets, int *n_facet_ints);
+
 /* ------------------------------------------------------------------------
  * (I) Gain-vector producer for Objects content — replaces ear::GainCalculatorObjects
  * (include/ear/gain_calculators.hpp:45-56, src/object_based/gain_calculator_objects.cpp:24-57)
@@ -330,7 +366,7 @@ int earhip_design_decorrelators_for_layout(const char *layout, int without_lfe, 
  * The float sums run in a different order from libear's scalar core: results agree to 1e-5 of
  * a gain vector's norm, the bound libear's tests put between its own cores
  * (tests/extent_tests.cpp:140-169).  With all three NULL they are the plain forms.
- * layout: an ITU-R BS.2051 name (group H).  Positions are polar: azimuth, elevation in
+ * layout: an ITU-R BS.2051 name or the name of a defined layout (group H).  Positions are polar: azimuth, elevation in
  * degrees (ADM convention), distance; distance / gain / diffuse may be NULL (1, 1, 0).
  * direct, diffuse_out: [npos][n_channels] float, LFE columns zero.
  * ---------------------------------------------------------------------- */
@@ -347,6 +383,20 @@ int earhip_panner_create_positions(earhip_ctx *ctx, const char *layout, int n_ch
                                    earhip_panner **out);
 int earhip_panner_destroy(earhip_panner *p);
 int earhip_panner_num_channels(const earhip_panner *p, int *n_channels);
+/* A self-check of a panner, for set-up time (it synchronises): one device launch pans, in double, the 5200 directions
+ * of the HOA design's spherical t-design plus the real direction of each loudspeaker that is not LFE.  A triangulation
+ * is sound when missed == 0 (every direction lands in a region), max_power_error is rounding (0+2+0: up to 0.5, its
+ * downmix is -3 dB at the back by design) and min_own_gain is 1 (a loudspeaker's own direction gives that loudspeaker).
+ * Reductions run per wave, then per workgroup, then on the host in index order — no floating-point atomics: the
+ * same panner gives the same report bits.  Changes nothing of the panner (earhip_panner_missed included). */
+typedef struct earhip_panner_report {
+  int n_directions;
+  unsigned missed;
+  double max_power_error; /* max |sum g^2 - 1| over the directions a region took */
+  double min_own_gain;    /* min over the loudspeakers that are not LFE of their own gain at their real direction */
+  int n_regions, n_triplets, n_quads, n_ngons, largest_ngon;
+} earhip_panner_report;
+int earhip_panner_self_check(earhip_panner *p, earhip_panner_report *report);
 /* host pointers: H2D, kernel, D2H, synchronise */
 int earhip_panner_calculate(earhip_panner *p, size_t npos, const double *azimuth,
                             const double *elevation, const double *distance, const double *gain,
@@ -390,7 +440,7 @@ int earhip_panner_calculate_extent_device(earhip_panner *p, size_t npos, const d
  * earhip_panner_missed (the host form: EARHIP_INTERNAL_ERROR).  Any of channel_lock,
  * lock_max_distance, divergence, azimuth_range, excluded may be NULL (0, none, 0, 45, 0).  A row whose
  * lock flag is 0, whose divergence is 0 and whose mask has no non-LFE bit takes the _extent forms'
- * kernels and has their bits.  Layouts have at most 24 channels.
+ * kernels and has their bits.  Layouts have at most 22 loudspeakers that are not LFE (24 channels in BS.2051).
  * The host form refuses, with EARHIP_INVALID_ARGUMENT and a message that names the index: a divergence
  * outside [0, 1] or NaN, a negative or NaN maxDistance, a non-finite azimuth_range, a mask bit at or
  * beyond the layout's channel count.  The _device form cannot look at the values: it clamps a
@@ -489,7 +539,7 @@ int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int 
  * form AP_0001xxxx (after the checks and warnings of 1-2) is EARHIP_NOT_IMPLEMENTED, the message naming
  * the pack; libear would apply a downmix rule there.  Any other pack follows 3-6, as in libear.
  *
- * layout: an ITU-R BS.2051 name (group H); gains: [n][n_channels] float for the full layout, LFE
+ * layout: an ITU-R BS.2051 name or the name of a defined layout (group H); gains: [n][n_channels] float for the full layout, LFE
  * channels included.  ctx may be NULL: no device panner, and a channel that reaches step 6 as a
  * non-LFE channel is EARHIP_INVALID_ARGUMENT.  from / to: n_subst extra substitutions.
  * ---------------------------------------------------------------------- */

@@ -385,14 +385,14 @@ def design_decorrelators(names):
 
 
 def layout_names():
-    """(H) names of the BS.2051 layouts the library knows"""
+    """(H) names of the BS.2051 layouts the library knows (defined layouts are not listed: layout_kind)"""
     lib = load()
     lib.earhip_layout_name.restype = C.c_char_p
     return [lib.earhip_layout_name(i).decode() for i in range(lib.earhip_layout_count())]
 
 
 def layout_channels(layout):
-    """(H) [(name, azimuth, elevation, is_lfe)] of a BS.2051 layout, in layout order"""
+    """(H) [(name, azimuth, elevation, is_lfe)] of a layout (BS.2051 or defined), in layout order"""
     n = C.c_int(0)
     check(load().earhip_layout_num_channels(layout.encode(), C.byref(n)))
     out = []
@@ -413,6 +413,62 @@ def layout_channel_ranges(layout):
         check(load().earhip_layout_channel_ranges(layout.encode(), i, az, el))
         out.append(((az[0], az[1]), (el[0], el[1])))
     return out
+
+
+class LayoutChannelDef(C.Structure):
+    """earhip_layout_channel_def"""
+    _fields_ = [("name", C.c_char_p), ("azimuth", C.c_double), ("elevation", C.c_double), ("has_ranges", C.c_int),
+                ("azimuth_range", C.c_double * 2), ("elevation_range", C.c_double * 2), ("is_lfe", C.c_int)]
+
+
+def define_layout(name, channels):
+    """(H) defines a loudspeaker layout of the caller's own under `name`; every function that takes a layout name then
+    accepts it.  channels: a list, in layout order, of (name, azimuth, elevation[, is_lfe[, azimuth_range,
+    elevation_range]]) with the NOMINAL position in degrees and the ranges as (lo, hi) pairs (absent: the nominal
+    position itself).  Pure host: the hull and a dry run of the panner's regions run here, so a bad layout raises here.
+    Defining a name again with the same content does nothing; with other content it is an InvalidArgument."""
+    defs = (LayoutChannelDef * max(len(channels), 1))()
+    for d, ch in zip(defs, channels):
+        d.name, d.azimuth, d.elevation = ch[0].encode(), float(ch[1]), float(ch[2])
+        d.is_lfe = int(bool(ch[3])) if len(ch) > 3 else 0
+        if len(ch) > 4:
+            d.has_ranges = 1
+            d.azimuth_range[0], d.azimuth_range[1] = (float(v) for v in ch[4])
+            d.elevation_range[0], d.elevation_range[1] = (float(v) for v in ch[5])
+    check(load().earhip_layout_define(name.encode(), len(channels), defs))
+
+
+def layout_kind(name):
+    """(H) 0: unknown, 1: an ITU-R BS.2051 layout, 2: a defined layout"""
+    kind = C.c_int(0)
+    check(load().earhip_layout_kind(name.encode(), C.byref(kind)))
+    return kind.value
+
+
+def layout_hull(name):
+    """(H) the triangulation of a layout -> (xyz float64 [V][3], mix_to int32 [V], n_virtual, facets): the augmented
+    vertices at their nominal positions, the channel of the full layout each one's gain goes to (-1: the virtual
+    loudspeakers, which come last), and the hull's facets as ascending tuples of vertex indices"""
+    i32 = C.POINTER(C.c_int)
+    nv, nvirt, nints = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load().earhip_layout_hull(name.encode(), 0, None, None, C.byref(nv), C.byref(nvirt), 0, None, C.byref(nints)))
+    xyz = np.empty((nv.value, 3), np.float64)
+    mix_to = np.empty(nv.value, np.int32)
+    ints = np.empty(nints.value, np.int32)
+    check(load().earhip_layout_hull(name.encode(), nv.value, _ptr(xyz, C.POINTER(C.c_double)), _ptr(mix_to, i32), C.byref(nv),
+                                    C.byref(nvirt), nints.value, _ptr(ints, i32), C.byref(nints)))
+    facets, at = [], 0
+    while ints[at]:
+        facets.append(tuple(int(v) for v in ints[at + 1:at + 1 + ints[at]]))
+        at += 1 + int(ints[at])
+    return xyz, mix_to, nvirt.value, facets
+
+
+class PannerReport(C.Structure):
+    """earhip_panner_report"""
+    _fields_ = [("n_directions", C.c_int), ("missed", C.c_uint), ("max_power_error", C.c_double),
+                ("min_own_gain", C.c_double), ("n_regions", C.c_int), ("n_triplets", C.c_int), ("n_quads", C.c_int),
+                ("n_ngons", C.c_int), ("largest_ngon", C.c_int)]
 
 
 def design_decorrelators_for_layout(layout, without_lfe=False):
@@ -522,6 +578,13 @@ class Panner:
         n = C.c_uint(0)
         check(load().earhip_panner_missed(self.h, C.byref(n)))
         return n.value
+
+    def self_check(self):
+        """pans the 5200 directions of the HOA design's t-design and every loudspeaker's real direction in one launch
+        (synchronises) -> a PannerReport: missed, max_power_error, min_own_gain and the region counts"""
+        report = PannerReport()
+        check(load().earhip_panner_self_check(self.h, C.byref(report)))
+        return report
 
     def close(self):
         if self.h:

@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "common.h"
-#include "layout_table.h"
+#include "layout_registry.h"
 
 using namespace earhip;
 
@@ -52,14 +52,6 @@ std::vector<double> design_basic(int id, int size) {
   for (int i = 0; i < size; i++) h[i] = a[i].real() / size;
   return h;
 }
-// ear::getLayout (src/bs2051.cpp:13-22): unknown names are an error
-const LayoutEntry &find_layout(const char *name) {
-  require(name != nullptr, "layout name must not be NULL");
-  for (int i = 0; i < kNumLayouts; i++)
-    if (std::strcmp(kLayouts[i].name, name) == 0) return kLayouts[i];
-  throw Error{EARHIP_UNKNOWN_LAYOUT, std::string("unknown layout: ") + name};
-}
-
 void design_for_names(const std::vector<std::string> &names, float *out) {
   for (size_t c = 0; c < names.size(); c++) {
     int id = 0;

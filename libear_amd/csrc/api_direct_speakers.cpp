@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "common.h"
-#include "layout_table.h"
+#include "layout_registry.h"
 
 using namespace earhip;
 
@@ -21,13 +21,6 @@ const double kPi = 3.14159265358979323846264338327950288;
 
 // Warning::Code (libear_amd/host/ear/warnings.hpp; include/ear/warnings.hpp in libear)
 const int kFreqSpeakerLabelLfeMismatch = 1, kFreqNotLfe = 2;
-
-const LayoutEntry &find_layout(const char *name) {
-  require(name != nullptr, "layout name must not be NULL");
-  for (int i = 0; i < kNumLayouts; i++)
-    if (std::strcmp(kLayouts[i].name, name) == 0) return kLayouts[i];
-  throw Error{EARHIP_UNKNOWN_LAYOUT, std::string("unknown layout: ") + name};
-}
 
 // libear's polar -> Cartesian convention (src/common/geom.cpp:82-87)
 void cart(double az, double el, double dist, double (&v)[3]) {

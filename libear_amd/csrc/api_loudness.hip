@@ -5,7 +5,7 @@
 #include <memory>
 
 #include "common.h"
-#include "layout_table.h"
+#include "layout_registry.h"
 #include "loudness_kernels.h"
 #include "true_peak_kernels.h"
 
@@ -346,10 +346,7 @@ int earhip_loudness_gate(size_t n_steps, int n_channels, const double *energy, c
 int earhip_loudness_layout_weights(const char *layout, double *weights) {
   return guarded([&] {
     require(layout != nullptr && weights != nullptr, "layout and weights must not be NULL");
-    const LayoutEntry *L = nullptr;
-    for (int i = 0; i < kNumLayouts; i++)
-      if (std::strcmp(kLayouts[i].name, layout) == 0) L = &kLayouts[i];
-    if (!L) throw Error{EARHIP_UNKNOWN_LAYOUT, std::string("unknown layout: ") + layout};
+    const LayoutEntry *L = &find_layout(layout);
     for (int c = 0; c < L->n; c++)
       weights[c] = loudness_channel_weight(L->channels[c].azimuth, L->channels[c].elevation, L->channels[c].is_lfe);
   });

@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "common.h"
-#include "layout_table.h"
+#include "layout_registry.h"
 #include "hoa_encode.h"
 #include "tdesign_5200.h"
 
@@ -325,6 +325,61 @@ k_pan_points(PanParams P, size_t npos, const double *xyz, double *pv_out, unsign
   for (int c = 0; c < n_pv; c++) pv_out[i * n_pv + c] = pv[c];
 }
 
+// earhip_panner_self_check: what a workgroup found over its directions
+struct SelfCheckPartial {
+  unsigned missed;         // directions no region took
+  double max_power_error;  // max |sum pv^2 - 1| over the others
+  double min_own_gain;     // min over the loudspeaker directions of the loudspeaker's own gain (2.0: none in this workgroup)
+};
+constexpr int kSelfCheckThreads = 256;
+
+// One thread per direction: the first n_design rows of xyz are the t-design, row n_design + k is the real direction of
+// panner output k.  Each direction goes through pan_full / pan_outputs as in k_pan_points; the three results are reduced
+// over the wave with shuffles, over the workgroup through LDS, and written as partial[blockIdx.x] — no atomics, so the
+// host's pass over the partials in index order gives the same bits for the same panner.
+static __global__ void __launch_bounds__(kSelfCheckThreads)
+k_pan_self_check(PanParams P, int n_dirs, int n_design, const double *xyz, SelfCheckPartial *partial) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  unsigned missed = 0;
+  double err = 0.0, own = 2.0;
+  if (i < n_dirs) {
+    const Vec3 p = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+    double real[kMaxPanOut], pv[kMaxPanOut];
+    if (!pan_full(P.table, p, real)) {
+      missed = 1;
+    } else {
+      const int n_pv = pan_outputs(P, real, pv);
+      double power = 0.0;
+      for (int c = 0; c < n_pv; c++) power += pv[c] * pv[c];
+      err = fabs(power - 1.0);
+      // (a NaN would be dropped by fmax: let it through as an error no bound accepts)
+      if (!(err == err)) err = 1e300;
+      const int k = i - n_design;
+      if (k >= 0 && k < n_pv) own = pv[k] == pv[k] ? pv[k] : -1e300;
+    }
+  }
+  for (int off = 32; off >= 1; off >>= 1) {
+    missed += __shfl_xor(missed, off);
+    err = fmax(err, __shfl_xor(err, off));
+    own = fmin(own, __shfl_xor(own, off));
+  }
+  constexpr int kWaves = kSelfCheckThreads / 64;
+  __shared__ unsigned s_missed[kWaves];
+  __shared__ double s_err[kWaves], s_own[kWaves];
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0) s_missed[wave] = missed, s_err[wave] = err, s_own[wave] = own;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    SelfCheckPartial r = {s_missed[0], s_err[0], s_own[0]};
+    for (int w = 1; w < kWaves; w++) {
+      r.missed += s_missed[w];
+      r.max_power_error = fmax(r.max_power_error, s_err[w]);
+      r.min_own_gain = fmin(r.min_own_gain, s_own[w]);
+    }
+    partial[blockIdx.x] = r;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Set-up (host, double): flatten the regions of a layout
 // ------------------------------------------------------------------------------------------------
@@ -382,13 +437,6 @@ void poly_basis(const Vec3 (&q)[4], double (&rows)[9]) {  // point_source_panner
   for (int i = 0; i < 3; i++) rows[3 * i] = r[i].x, rows[3 * i + 1] = r[i].y, rows[3 * i + 2] = r[i].z;
 }
 
-const LayoutEntry &layout_entry(const char *name) {
-  require(name != nullptr, "layout name must not be NULL");
-  for (int i = 0; i < kNumLayouts; i++)
-    if (std::strcmp(kLayouts[i].name, name) == 0) return kLayouts[i];
-  throw Error{EARHIP_UNKNOWN_LAYOUT, std::string("unknown layout: ") + name};
-}
-
 // the regions of a layout with precomputed hull facets (configureFullPolarPanner, :478-561).
 // real_az / real_el (optional, one per channel of the full layout): the loudspeakers' real positions; the
 // layer logic and the facets follow the nominal ones, the geometry the real ones, as in libear
@@ -411,35 +459,16 @@ std::vector<PanRegion> build_regions(const LayoutEntry &L, int &n_real, const do
       if (25.0 < abs_az)
         throw Error{EARHIP_NOT_IMPLEMENTED, "M+SC and M-SC with azimuths wider than 25 degrees are not currently supported"};
     }
-  // extra loudspeakers above / below the mid-layer ones where a layer has none in that direction,
-  // each mixed into its mid-layer loudspeaker (extraPosVerticalNominal, :256-349)
+  // the augmented set (layout_registry.h): extra loudspeakers above / below the mid-layer ones where a layer has none
+  // in that direction, each mixed into its mid-layer loudspeaker (extraPosVerticalNominal, :256-349), then the
+  // virtual loudspeakers below and (unless the layout has one overhead) above (:442-455)
   std::vector<Vec3> verts;
   std::vector<int> mix_to;  // augmented vertex -> real loudspeaker
-  for (int c = 0; c < n_real; c++) verts.push_back(polar_to_cart(real[c].az, real[c].el, 1.0)), mix_to.push_back(c);
-  const double layers[2][3] = {{-30.0, -70.0, -10.0}, {30.0, 10.0, 70.0}};
-  for (auto &layer : layers) {
-    double az_range = -1.0, el_sum = 0.0;
-    int in_layer = 0;
-    for (auto &ch : real)
-      if (layer[1] <= ch.el_nom && ch.el_nom <= layer[2])
-        az_range = std::max(az_range, std::fabs(ch.az_nom)), el_sum += ch.el, in_layer++;
-    const double az_limit = in_layer ? az_range + 40.0 : 0.0;
-    const double layer_el = in_layer ? el_sum / in_layer : layer[0];
-    for (int c = 0; c < n_real; c++)
-      if (-10 <= real[c].el_nom && real[c].el_nom <= 10 && std::fabs(real[c].az) >= az_limit - 1e-5) {
-        verts.push_back(polar_to_cart(real[c].az, layer_el, 1.0));
-        mix_to.push_back(c);
-      }
-  }
-  // virtual loudspeakers below and (unless the layout has one overhead) above (:442-455)
   std::vector<int> virt;
-  bool overhead = false;
-  for (auto &ch : real) overhead = overhead || ch.name == "T+000" || ch.name == "UH+180";
-  virt.push_back((int)verts.size());
-  verts.push_back({0.0, 0.0, -1.0});
-  if (!overhead) {
-    virt.push_back((int)verts.size());
-    verts.push_back({0.0, 0.0, 1.0});
+  for (const AugVertex &v : augment_layout(L, real_az, real_el)) {
+    if (v.pole) virt.push_back((int)verts.size());
+    verts.push_back(v.pole ? Vec3{0.0, 0.0, (double)v.pole} : polar_to_cart(v.az, v.el, 1.0));
+    mix_to.push_back(v.mix_to);
   }
   auto is_virtual = [&](int v) { return std::find(virt.begin(), virt.end(), v) != virt.end(); };
   std::vector<std::vector<int>> facets;
@@ -453,7 +482,9 @@ std::vector<PanRegion> build_regions(const LayoutEntry &L, int &n_real, const do
         for (int v : f)
           if (v != vv && std::find(ring.begin(), ring.end(), v) == ring.end()) ring.push_back(v);
     std::sort(ring.begin(), ring.end());
-    require((int)ring.size() <= kMaxNgon && ring.size() >= 3, "unsupported n-gon size");
+    if ((int)ring.size() > kMaxNgon)
+      throw Error{EARHIP_NOT_IMPLEMENTED, "more than " + std::to_string(kMaxNgon) + " loudspeakers around a virtual loudspeaker"};
+    require(ring.size() >= 3, "unsupported n-gon size");
     for (int v : ring) require(!is_virtual(v), "invalid triangulation");
     PanRegion R;
     std::memset(&R, 0, sizeof(R));
@@ -624,7 +655,18 @@ struct earhip_panner {
   PinBuf<double> p_in;
   PinBuf<float> p_out;
   PinBuf<unsigned> p_missed;
+  int n_triplets = 0, n_quads = 0, n_ngons = 0, largest_ngon = 0;  // the regions by kind (earhip_panner_self_check)
 };
+
+static_assert(kMaxLayoutSpeakers == kObjMaxOut && kMaxLayoutChannels == kMaxPanOut, "layout_registry.h states the kernels' limits");
+
+// what a create with nominal positions does on the host (earhip_layout_define runs it, so that a layout the region
+// builder refuses fails when it is defined)
+void earhip::panner_dry_run(const LayoutEntry &L) {
+  int n_real = 0;
+  (void)build_regions(L, n_real);
+  (void)objects_speakers(L);
+}
 
 // PolarExtent's constructor (src/object_based/polar_extent.cpp:16-50, :96-176): the 37 rows of points and the
 // point source panner's gains at each of them (device, one thread per point, double), kept as float
@@ -730,7 +772,7 @@ int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, c
                           const double *elevation, earhip_panner **out, bool with_extent) {
   return guarded([&] {
     require(ctx != nullptr && out != nullptr, "NULL argument");
-    const LayoutEntry &L = layout_entry(layout);
+    const LayoutEntry &L = find_layout(layout);
     require((azimuth == nullptr) == (elevation == nullptr), "azimuth and elevation come together");
     if (azimuth) {
       require(n_channels == L.n, "one position per channel of the layout (LFE channels included)");
@@ -745,7 +787,7 @@ int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, c
     int n_real = 0;
     std::vector<PanRegion> regions;
     if (std::strcmp(L.name, "0+2+0") == 0) {  // configureStereoPolarPanner (:406-429): pans on the nominal 0+5+0
-      regions = build_regions(layout_entry("0+5+0"), n_real);
+      regions = build_regions(find_layout("0+5+0"), n_real);
       p->P.stereo = 1;
       for (int c = 0; c < L.n; c++) {
         if (std::strcmp(L.channels[c].name, "M+030") == 0) p->P.stereo_index[0] = c;
@@ -774,6 +816,10 @@ int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, c
       }
       objects_zone_groups(sp, p->zone_table.groups);
     }
+    for (const PanRegion &R : regions) {
+      p->n_triplets += R.kind == 0, p->n_quads += R.kind == 1, p->n_ngons += R.kind == 2;
+      if (R.kind == 2) p->largest_ngon = std::max(p->largest_ngon, R.n);
+    }
     p->regions.alloc(regions.size());
     EARHIP_HIP(hipMemcpy(p->regions.p, regions.data(), sizeof(PanRegion) * regions.size(), hipMemcpyHostToDevice));
     p->P.table.n_regions = (int)regions.size();
@@ -785,6 +831,19 @@ int earhip::panner_create(earhip_ctx *ctx, const char *layout, int n_channels, c
     if (with_extent) build_extent_table(*p);
     *out = p.release();
   });
+}
+
+// the design's directions as unit vectors (src/hoa/hoa.cpp:4-14), [kTDesignPoints][3]
+static std::vector<double> tdesign_directions(size_t extra_rows = 0) {
+  const size_t P = (size_t)kTDesignPoints;
+  std::vector<double> xyz(3 * (P + extra_rows));
+  for (size_t i = 0; i < P; i++) {
+    const double phi = kTDesign[i][0], theta = kTDesign[i][1];
+    xyz[3 * i] = std::sin(theta) * std::cos(phi);
+    xyz[3 * i + 1] = std::sin(theta) * std::sin(phi);
+    xyz[3 * i + 2] = std::cos(theta);
+  }
+  return xyz;
 }
 
 extern "C" {
@@ -811,6 +870,46 @@ int earhip_panner_num_channels(const earhip_panner *p, int *n_channels) {
   return guarded([&] {
     require(p != nullptr && n_channels != nullptr, "NULL argument");
     *n_channels = p->P.n_full;
+  });
+}
+
+// Does every direction land in a region, with unit power, and does a loudspeaker's own direction give that loudspeaker
+// alone?  One launch over the t-design and the loudspeakers' real directions (the lock table's: the panner's outputs at
+// the positions it was created with); a set-up-time call, it synchronises.
+int earhip_panner_self_check(earhip_panner *p, earhip_panner_report *report) {
+  return guarded([&] {
+    require(p != nullptr && report != nullptr, "NULL argument");
+    earhip_ctx *ctx = p->ctx;
+    ctx->use();
+    const int n_design = kTDesignPoints, n_out = p->lock_table.n, n_dirs = n_design + n_out;
+    std::vector<double> xyz = tdesign_directions((size_t)n_out);
+    for (int k = 0; k < n_out; k++)
+      for (int q = 0; q < 3; q++) xyz[3 * (size_t)(n_design + k) + q] = p->lock_table.pos[k][q];
+    const int n_wg = (n_dirs + kSelfCheckThreads - 1) / kSelfCheckThreads;
+    DevBuf<double> d_xyz;
+    DevBuf<SelfCheckPartial> d_partial;
+    d_xyz.alloc(xyz.size());
+    d_partial.alloc((size_t)n_wg);
+    EARHIP_HIP(hipMemcpyAsync(d_xyz.p, xyz.data(), sizeof(double) * xyz.size(), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_pan_self_check, dim3((unsigned)n_wg), dim3(kSelfCheckThreads), 0, ctx->stream, p->P, n_dirs, n_design,
+                       d_xyz.p, d_partial.p);
+    EARHIP_HIP(hipGetLastError());
+    std::vector<SelfCheckPartial> partial((size_t)n_wg);
+    EARHIP_HIP(hipMemcpyAsync(partial.data(), d_partial.p, sizeof(SelfCheckPartial) * (size_t)n_wg, hipMemcpyDeviceToHost, ctx->stream));
+    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    std::memset(report, 0, sizeof(*report));
+    report->n_directions = n_dirs;
+    report->min_own_gain = 2.0;
+    for (const SelfCheckPartial &w : partial) {
+      report->missed += w.missed;
+      report->max_power_error = std::max(report->max_power_error, w.max_power_error);
+      report->min_own_gain = std::min(report->min_own_gain, w.min_own_gain);
+    }
+    report->n_regions = p->P.table.n_regions;
+    report->n_triplets = p->n_triplets;
+    report->n_quads = p->n_quads;
+    report->n_ngons = p->n_ngons;
+    report->largest_ngon = p->largest_ngon;
   });
 }
 
@@ -848,13 +947,7 @@ int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int 
     const size_t P = (size_t)kTDesignPoints, C = (size_t)n_coef;
     const size_t S = pn->P.stereo ? 2 : (size_t)pn->P.table.n_real;
     // the design's directions (src/hoa/hoa.cpp:4-14)
-    std::vector<double> xyz(3 * P);
-    for (size_t i = 0; i < P; i++) {
-      const double phi = kTDesign[i][0], theta = kTDesign[i][1];
-      xyz[3 * i] = std::sin(theta) * std::cos(phi);
-      xyz[3 * i + 1] = std::sin(theta) * std::sin(phi);
-      xyz[3 * i + 2] = std::cos(theta);
-    }
+    const std::vector<double> xyz = tdesign_directions();
     // G_virt [P][S] on the device
     DevBuf<double> d_xyz, d_pv;
     d_xyz.alloc(3 * P);
@@ -1137,7 +1230,7 @@ int earhip_panner_calculate_objects(earhip_panner *p, size_t npos, const double 
 int earhip_objects_lock_priority(const char *layout, int *order) {
   return guarded([&] {
     require(order != nullptr, "NULL argument");
-    const std::vector<ObjSpeaker> sp = objects_speakers(layout_entry(layout));
+    const std::vector<ObjSpeaker> sp = objects_speakers(find_layout(layout));
     const std::vector<int> rank = objects_lock_rank(sp);
     for (size_t s = 0; s < sp.size(); s++) order[rank[s]] = sp[s].full;
   });
@@ -1146,7 +1239,7 @@ int earhip_objects_lock_priority(const char *layout, int *order) {
 int earhip_objects_excluded_channels(const char *layout, int n_zones, const earhip_exclusion_zone *zones, uint32_t *mask) {
   return guarded([&] {
     require(mask != nullptr && n_zones >= 0 && (zones != nullptr || n_zones == 0), "NULL argument");
-    const std::vector<ObjSpeaker> sp = objects_speakers(layout_entry(layout));
+    const std::vector<ObjSpeaker> sp = objects_speakers(find_layout(layout));
     const double tol = 1e-6;
     uint32_t m = 0;
     for (const ObjSpeaker &c : sp)
@@ -1168,7 +1261,7 @@ int earhip_objects_excluded_channels(const char *layout, int n_zones, const earh
 int earhip_objects_zone_downmix(const char *layout, uint32_t mask, double *matrix) {
   return guarded([&] {
     require(matrix != nullptr, "NULL argument");
-    const LayoutEntry &L = layout_entry(layout);
+    const LayoutEntry &L = find_layout(layout);
     const std::vector<ObjSpeaker> sp = objects_speakers(L);
     const size_t N = (size_t)L.n;
     if (N < 32 && (mask >> N) != 0) fail_invalid("mask has a bit set beyond the layout's " + std::to_string(N) + " channels");

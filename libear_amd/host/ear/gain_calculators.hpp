@@ -3,6 +3,8 @@
 // call a renderer wants: all metadata blocks of all objects in one launch; GainCalculatorHOA and
 // GainCalculatorDirectSpeakers over the same panner.
 #pragma once
+#include <cstdint>
+#include <cstdio>
 #include <map>
 #include <memory>
 #include <string>
@@ -14,11 +16,66 @@
 
 namespace ear {
   namespace detail {
-    /// which channels of the full BS.2051 layout the caller's layout keeps (Layout::withoutLfe drops the LFEs),
-    /// and the real positions of all channels of the full layout (the caller's where it has the channel)
-    inline std::vector<int> match_layout(const Layout &layout, std::vector<double> &az, std::vector<double> &el) {
-      const Layout full = getLayout(layout.name());
+    /// 64-bit FNV-1a
+    inline void fnv1a(uint64_t &h, const void *data, size_t n) {
+      const unsigned char *p = static_cast<const unsigned char *>(data);
+      for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001b3ull;
+    }
+
+    /// A layout that is not one of BS.2051 — libear's Layout(name, channels) is a public constructor — is defined in the
+    /// native registry (earhip_layout_define, group H) under "ear:" + 16 hex digits of a hash over each channel's name,
+    /// the bits of its nominal azimuth and elevation, its LFE flag and the ranges it was given, if any.  The layout's own
+    /// name is not part of it: an empty name, or one name for two layouts, works.  Returns the registry name.
+    inline std::string define_layout(const Layout &layout) {
+      const std::vector<Channel> &ch = layout.channels();
+      std::vector<earhip_layout_channel_def> defs(ch.size());
+      uint64_t h = 0xcbf29ce484222325ull;
+      for (size_t i = 0; i < ch.size(); i++) {
+        earhip_layout_channel_def &d = defs[i];
+        d = earhip_layout_channel_def();
+        d.name = ch[i].name().c_str();
+        d.azimuth = ch[i].polarPositionNominal().azimuth;
+        d.elevation = ch[i].polarPositionNominal().elevation;
+        d.is_lfe = ch[i].isLfe() ? 1 : 0;
+        // (a range that was never set reads as the REAL position, which is no part of a definition: the nominal one)
+        d.has_ranges = ch[i].hasAzimuthRange() || ch[i].hasElevationRange();
+        d.azimuth_range[0] = d.azimuth_range[1] = d.azimuth;
+        d.elevation_range[0] = d.elevation_range[1] = d.elevation;
+        if (ch[i].hasAzimuthRange()) d.azimuth_range[0] = ch[i].azimuthRange().first, d.azimuth_range[1] = ch[i].azimuthRange().second;
+        if (ch[i].hasElevationRange())
+          d.elevation_range[0] = ch[i].elevationRange().first, d.elevation_range[1] = ch[i].elevationRange().second;
+        const unsigned char flags[2] = {(unsigned char)d.is_lfe, (unsigned char)d.has_ranges};
+        fnv1a(h, ch[i].name().c_str(), ch[i].name().size() + 1);
+        fnv1a(h, &d.azimuth, sizeof(double));
+        fnv1a(h, &d.elevation, sizeof(double));
+        fnv1a(h, flags, sizeof(flags));
+        if (d.has_ranges) fnv1a(h, d.azimuth_range, sizeof(d.azimuth_range)), fnv1a(h, d.elevation_range, sizeof(d.elevation_range));
+      }
+      char name[32];
+      std::snprintf(name, sizeof(name), "ear:%016llx", (unsigned long long)h);
+      hip::check(earhip_layout_define(name, (int)defs.size(), defs.data()));
+      return name;
+    }
+
+    /// The native layout behind the caller's: `name` is what the native entry points take, az / el the real positions of
+    /// all of ITS channels, and the result says which of them the caller's layout keeps, in the caller's order.  A
+    /// BS.2051 name stands for that layout, of which the caller's may be a part (Layout::withoutLfe drops the LFEs; a
+    /// channel that is no part of it is refused); any other layout is defined as it is (define_layout).
+    inline std::vector<int> match_layout(const Layout &layout, std::string &name, std::vector<double> &az, std::vector<double> &el) {
+      int kind = 0;
+      hip::check(earhip_layout_kind(layout.name().c_str(), &kind));
       std::vector<int> keep;
+      if (kind != 1) {
+        name = define_layout(layout);
+        for (auto &c : layout.channels()) {
+          az.push_back(c.polarPosition().azimuth);
+          el.push_back(c.polarPosition().elevation);
+          keep.push_back((int)keep.size());
+        }
+        return keep;
+      }
+      name = layout.name();
+      const Layout full = getLayout(layout.name());
       for (auto &c : full.channels()) {
         az.push_back(c.polarPosition().azimuth);
         el.push_back(c.polarPosition().elevation);
@@ -36,13 +93,14 @@ namespace ear {
 
   class GainCalculatorObjects {
    public:
-    /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels
+    /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels, or a layout of the caller's own
     explicit GainCalculatorObjects(const Layout &layout, hip::Context &ctx = hip::default_context()) {
       std::vector<double> az, el;
-      keep_ = detail::match_layout(layout, az, el);
+      std::string name;
+      keep_ = detail::match_layout(layout, name, az, el);
       n_full_ = az.size();
       // the loudspeakers' real positions (Channel::polarPosition) shape the panner, the nominal ones its layers
-      hip::check(earhip_panner_create_positions(ctx.get(), layout.name().c_str(), (int)n_full_, az.data(), el.data(), &h_));
+      hip::check(earhip_panner_create_positions(ctx.get(), name.c_str(), (int)n_full_, az.data(), el.data(), &h_));
     }
     ~GainCalculatorObjects() { earhip_panner_destroy(h_); }
     GainCalculatorObjects(const GainCalculatorObjects &) = delete;
@@ -113,17 +171,18 @@ namespace ear {
   /// (audioPackFormatID AP_0001xxxx) throws not_implemented.
   class GainCalculatorDirectSpeakers {
    public:
-    /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels; additionalSubstitutions:
+    /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels, or a layout of the caller's own; additionalSubstitutions:
     /// speakerLabel -> nominal label, on top of (never instead of) LFE -> LFE1, LFEL -> LFE1, LFER -> LFE2
     explicit GainCalculatorDirectSpeakers(const Layout &layout,
                                           std::map<std::string, std::string> additionalSubstitutions = {},
                                           hip::Context &ctx = hip::default_context()) {
       std::vector<double> az, el;
-      keep_ = detail::match_layout(layout, az, el);
+      std::string name;
+      keep_ = detail::match_layout(layout, name, az, el);
       n_full_ = az.size();
       std::vector<const char *> from, to;
       for (auto &kv : additionalSubstitutions) from.push_back(kv.first.c_str()), to.push_back(kv.second.c_str());
-      hip::check(earhip_direct_speakers_create_positions(ctx.get(), layout.name().c_str(), (int)n_full_, az.data(),
+      hip::check(earhip_direct_speakers_create_positions(ctx.get(), name.c_str(), (int)n_full_, az.data(),
                                                          el.data(), (int)from.size(), from.data(), to.data(), &h_));
     }
     ~GainCalculatorDirectSpeakers() { earhip_direct_speakers_destroy(h_); }
@@ -199,8 +258,8 @@ namespace ear {
   class GainCalculatorHOA {
    public:
     explicit GainCalculatorHOA(const Layout &layout, hip::Context &ctx = hip::default_context())
-        : name_(layout.name()), ctx_(ctx) {
-      keep_ = detail::match_layout(layout, az_, el_);
+        : ctx_(ctx) {
+      keep_ = detail::match_layout(layout, name_, az_, el_);
       n_full_ = az_.size();
     }
     /// gains[coefficient][loudspeaker] (libear's column-major vector of vectors): must have that shape

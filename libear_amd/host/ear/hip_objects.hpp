@@ -16,10 +16,10 @@ namespace ear {
   namespace hip {
     class ObjectsGainCalculator {
      public:
-      /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels
-      explicit ObjectsGainCalculator(const Layout &layout, Context &ctx = default_context()) : name_(layout.name()) {
+      /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels, or a layout of the caller's own
+      explicit ObjectsGainCalculator(const Layout &layout, Context &ctx = default_context()) {
         std::vector<double> az, el;
-        keep_ = ear::detail::match_layout(layout, az, el);
+        keep_ = ear::detail::match_layout(layout, name_, az, el);
         n_full_ = az.size();
         check(earhip_panner_create_positions(ctx.get(), name_.c_str(), (int)n_full_, az.data(), el.data(), &h_));
       }

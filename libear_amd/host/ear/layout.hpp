@@ -45,6 +45,9 @@ namespace ear {
     }
     void azimuthRange(std::pair<double, double> r) { az_range_ = r, has_az_ = true; }
     void elevationRange(std::pair<double, double> r) { el_range_ = r, has_el_ = true; }
+    /// was the range given (libear keeps a boost::optional inside)?  Not part of libear's interface.
+    bool hasAzimuthRange() const { return has_az_; }
+    bool hasElevationRange() const { return has_el_; }
     /// reports a real position outside the allowed ranges through the callback (src/layout.cpp:54-75)
     void checkPosition(std::function<void(const std::string &)> callback) const {
       if (has_az_ && !inside_angle_range(pos_.azimuth, az_range_.first, az_range_.second)) {
