@@ -162,7 +162,9 @@ int earhip_interp_apply_constant(earhip_ctx *ctx, int n_in, int n_out,
  * (A') Whole-curve GainInterpolator with device-resident points — replaces
  * GainInterpolator<InterpType>::process (gain_interpolator.hpp:53-87) for
  * callers that keep the curve fixed across calls.  values: [npoints][n_in]
- * [n_out]; times must be sorted (duplicates = step).
+ * [n_out]; times must be sorted (duplicates = step).  n_in, n_out >= 1, no
+ * upper bound (the gain columns are tiled as for the renderer, group F; tested
+ * up to 97 outputs).
  * ---------------------------------------------------------------------- */
 typedef struct earhip_gain_interp earhip_gain_interp;
 int earhip_gain_interp_create(earhip_ctx *ctx, int n_in, int n_out,
@@ -655,7 +657,11 @@ typedef struct earhip_render earhip_render;
 
 typedef struct earhip_render_config {
   int n_objects;  /* M: input channels handled by this instance (this GPU's shard) */
-  int n_out;      /* N: loudspeakers */
+  int n_out;      /* N: loudspeakers, >= 1.  No upper bound: the gain stage tiles the n_buses * N gain columns in groups
+                     of 48 (24 in strict mode), as many as it takes.  Every BS.2051 layout is one group (at most 24 x 2
+                     columns); every gain kernel is held to the same accuracy bars at 25, 32 (the widest layout
+                     earhip_layout_define takes), 48, 49, 97 and 193 loudspeakers on two buses and 49 on one
+                     (tests/test_gpu_wide_bus.py).  An attached tap brings its own limit (FIR matrix: n_in in [1, 64]) */
   int block_size; /* B in [16, 4096], any factorisation (as libear's kissfft); the tuned
                      kernels are the powers of two from 64 (512 and 1024 above all) */
   int n_buses;    /* 1: direct bus only, written straight to the output

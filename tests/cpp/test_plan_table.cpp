@@ -150,6 +150,16 @@ static std::vector<Case> cases() {
       Case &c = add(holding("many_holding_index16"));
       c.M = M, c.ncols = 6, c.nsamples = 512, c.use_mfma = mfma, c.st.hinge_exact_share = 0.0;
     }
+  // ---- beyond one column group (tests/wide_bus_cases.py: 96 objects, 2 blocks of 512 on 25 x 2, 32 x 2 and 49 x 2 columns): every
+  // forced kernel on the three curve families, in block mode
+  for (int ncols : {50, 64, 98})
+    for (int mfma : {1, 3, 4, 5, 6}) {
+      auto set = [&](Case &c) { c.M = 96, c.ncols = ncols, c.nsamples = 1024, c.use_mfma = mfma; };
+      Case &g = add(on_grid("wide_grid"));
+      set(g), g.st.ramp_share = 1.0, g.st.pair_waste256 = 0.0, g.st.hinge_exact_share = 0.0, g.st.grid512_strict = true;
+      set(add(holding("wide_holding"))), v.back().st.hinge_exact_share = 0.0;
+      set(add(ramping("wide_ramping")));
+    }
   return v;
 }
 

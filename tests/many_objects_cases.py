@@ -166,9 +166,17 @@ def strict_case(family, M, layout, block, nb):
                 dict(kernel=VALU, tile=256, ntiles=-(-block * nb // 256), gsplit=1, layout=None))
 
 
-def n_out(case):
+def speakers(layout):
+    """the loudspeaker names of a case's `layout`: a BS.2051 layout's own, or, for a plain channel count N (tests/wide_bus_cases.py:
+    widths no BS.2051 layout has), made-up ones S000 .. — design_decorrelators takes any names"""
+    if isinstance(layout, int):
+        return [f"S{c:03d}" for c in range(layout)]
     from layouts import LAYOUTS
-    return len(LAYOUTS[case.layout])
+    return LAYOUTS[layout]
+
+
+def n_out(case):
+    return len(speakers(case.layout))
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------------
@@ -277,18 +285,18 @@ def bus_f64(curves, x, N, bus=0, chunk=4096):
 Scene = namedtuple("Scene", "curves x dec delay want truth answer magnitude")
 
 
-@functools.lru_cache(maxsize=3)
-def _scene(family, M, layout, buses, block, nblocks, seed):
+def build_scene(family, curves, x, names, buses, block, object_by_object=False):
+    """the CPU references of one scene on the loudspeakers `names`: the oracle's render of `curves` over the inputs `x`, and the
+    float64 evaluation (object_by_object: scenes.render_f64 instead of the vectorised bus_f64 — small scenes) or, for the roll
+    call, the int64 answer"""
     import numpy as np
     import _oracle
     import scenes
-    from layouts import LAYOUTS
-    N, total = len(LAYOUTS[layout]), block * nblocks
-    curves = make_curves(family, M, N, block, nblocks, seed)
-    x = integer_inputs(M, total) if family == "integer" else scenes.audio(M, total, seed=seed + 1)
+    M, total = x.shape
+    N = len(names)
     x.setflags(write=False)
     if buses == 2:
-        dec, delay = _oracle.design_decorrelators(LAYOUTS[layout]), _oracle.compensation_delay()
+        dec, delay = _oracle.design_decorrelators(names), _oracle.compensation_delay()
         o = _oracle.ObjectsRenderer(M, N, block, dec, delay)
     else:  # direct bus only: zero decorrelators, no delay => the output is the direct bus exactly
         dec, delay = None, 0
@@ -305,6 +313,10 @@ def _scene(family, M, layout, buses, block, nblocks, seed):
     answer = magnitude = truth = None
     if family == "integer":
         answer, magnitude = integer_answer(M, N, total)
+        if buses == 2:  # (the roll call on the direct bus beside a silent diffuse bus: the answer, delayed)
+            answer = np.concatenate([np.zeros((N, delay), np.int64), answer], axis=1)[:, :total]
+    elif object_by_object:
+        truth = scenes.render_f64([(t, d, f if buses == 2 else None) for t, d, f in curves], x, N, dec, delay)
     else:
         truth = bus_f64(curves, x, N, 0)
         if buses == 2:
@@ -312,6 +324,16 @@ def _scene(family, M, layout, buses, block, nblocks, seed):
             for c in range(N):
                 truth[c] = np.convolve(diffuse[c], dec[c].astype(np.float64))[:total] + np.concatenate([np.zeros(delay), truth[c]])[:total]
     return Scene(curves, x, dec, delay, want, truth, answer, magnitude)
+
+
+@functools.lru_cache(maxsize=3)
+def _scene(family, M, layout, buses, block, nblocks, seed):
+    import scenes
+    names = speakers(layout)
+    total = block * nblocks
+    curves = make_curves(family, M, len(names), block, nblocks, seed)
+    x = integer_inputs(M, total) if family == "integer" else scenes.audio(M, total, seed=seed + 1)
+    return build_scene(family, curves, x, names, buses, block)
 
 
 def scene(case):
