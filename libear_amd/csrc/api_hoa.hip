@@ -1,16 +1,20 @@
 // api_hoa.hip — the Ambisonic encoder for Objects and the rotation of the HOA bus (earhip group Q; libear has no
 // counterpart, the conventions are those of its hoa::sph_harm).  The arithmetic is hoa_encode.h, shared by the host form
 // (computed on the calling thread, like the host forms of group K) and the device form (hoa_kernels.h: a wave per 64
-// positions, enqueued on the context's stream).  The rotation matrix is host arithmetic over the decoder's t-design.
+// positions, enqueued on the context's stream).  The rotation matrix is host arithmetic over the decoder's t-design.  And
+// the HOA decode matrix of group I (libear's GainCalculatorHOA): host linear algebra over the same design, whose
+// directions the point source panner of api_panner.hip pans on the device.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
 #include "hoa_encode.h"
 #include "hoa_kernels.h"
+#include "panner.h"
 #include "tdesign_5200.h"
 
 using namespace earhip;
@@ -44,6 +48,92 @@ Table make_table(int n_coef, const int *orders, const int *degrees, const char *
 const size_t kMaxElements = (size_t)1 << 31;
 
 }  // namespace
+
+// the design's directions as unit vectors (src/hoa/hoa.cpp:4-14), [kTDesignPoints][3]
+std::vector<double> earhip::tdesign_directions(size_t extra_rows) {
+  const size_t P = (size_t)kTDesignPoints;
+  std::vector<double> xyz(3 * (P + extra_rows));
+  for (size_t i = 0; i < P; i++) {
+    const double phi = kTDesign[i][0], theta = kTDesign[i][1];
+    xyz[3 * i] = std::sin(theta) * std::cos(phi);
+    xyz[3 * i + 1] = std::sin(theta) * std::sin(phi);
+    xyz[3 * i + 2] = std::cos(theta);
+  }
+  return xyz;
+}
+
+// GainCalculatorHOAImpl (src/hoa/gain_calculator_hoa.cpp:8-72): AllRAD — the point source panner sampled
+// at the 5200 directions of a spherical t-design (device, one thread per direction), times the N3D
+// spherical harmonics at those directions (host, double: a cold 24 x 5200 x n_coef product), power
+// normalised and converted to the requested normalisation.
+int earhip_hoa_decode_matrix(earhip_ctx *ctx, const char *layout, int n_coef, const int *orders, const int *degrees,
+                             const char *normalization, float *out) {
+  return earhip_hoa_decode_matrix_positions(ctx, layout, 0, nullptr, nullptr, n_coef, orders, degrees, normalization, out);
+}
+
+int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth,
+                                       const double *elevation, int n_coef, const int *orders, const int *degrees,
+                                       const char *normalization, float *out) {
+  return guarded([&] {
+    require(ctx != nullptr && out != nullptr, "NULL argument");
+    require(n_coef >= 1 && orders != nullptr && degrees != nullptr, "orders and degrees must be the same size");
+    require(n_coef <= 4096, "too many coefficients");
+    for (int i = 0; i < n_coef; i++) {
+      require(orders[i] >= 0, "orders must not be negative");
+      require(std::abs(degrees[i]) <= orders[i], "magnitude of degree must not be greater than order");
+      require(orders[i] <= 64, "order too high");
+    }
+    const HoaNorm norm = parse_norm(normalization);
+    earhip_panner *pn = nullptr;
+    const int st = panner_create(ctx, layout, n_channels, azimuth, elevation, &pn, false);
+    if (st != EARHIP_OK) throw Error{st, earhip_last_error()};
+    std::unique_ptr<earhip_panner, int (*)(earhip_panner *)> guard(pn, earhip_panner_destroy);
+    const PanParams &pp = panner_params(pn);
+    const size_t P = (size_t)kTDesignPoints, C = (size_t)n_coef;
+    const size_t S = pp.stereo ? 2 : (size_t)pp.table.n_real;
+    // G_virt [P][S] on the device
+    const std::vector<double> xyz = tdesign_directions();
+    unsigned missed = 0;
+    const std::vector<double> G = panner_pan_points(pn, P, xyz.data(), &missed);
+    if (missed) fail_internal("point source panner: a design direction was not handled by any region");
+    // Y_virt [C][P], N3D (hoa.hpp:115-133)
+    std::vector<double> Y(C * P);
+    for (size_t i = 0; i < P; i++) {
+      const double az = -std::atan2(xyz[3 * i], xyz[3 * i + 1]);
+      const double el = std::atan2(xyz[3 * i + 2], std::hypot(xyz[3 * i], xyz[3 * i + 1]));
+      for (size_t c = 0; c < C; c++) {
+        const int n = orders[c], m = degrees[c], am = std::abs(m);
+        const double trig = m > 0 ? std::sqrt(2.0) * std::cos(m * az) : m < 0 ? -std::sqrt(2.0) * std::sin(m * az) : 1.0;
+        Y[c * P + i] = hoa_norm(kN3D, n, am) * legendre_nm(n, am, std::sin(el)) * trig;
+      }
+    }
+    // D = G_virt (Y_virt^T / P), then |D Y_virt|_F = sqrt(P), then N3D -> norm (gain_calculator_hoa.cpp:56-63)
+    std::vector<double> D(S * C, 0.0);
+    for (size_t sp = 0; sp < S; sp++)
+      for (size_t c = 0; c < C; c++) {
+        double acc = 0.0;
+        for (size_t i = 0; i < P; i++) acc += G[i * S + sp] * (Y[c * P + i] / (double)P);
+        D[sp * C + c] = acc;
+      }
+    double fro = 0.0;
+    for (size_t sp = 0; sp < S; sp++)
+      for (size_t i = 0; i < P; i++) {
+        double v = 0.0;
+        for (size_t c = 0; c < C; c++) v += D[sp * C + c] * Y[c * P + i];
+        fro += v * v;
+      }
+    const double k = std::sqrt((double)P) / std::sqrt(fro);
+    for (size_t i = 0; i < (size_t)pp.n_full * C; i++) out[i] = 0.0f;
+    for (size_t sp = 0; sp < S; sp++) {
+      const int row = pp.stereo ? pp.stereo_index[sp] : pp.full_index[sp];
+      for (size_t c = 0; c < C; c++) {
+        const int am = std::abs(degrees[c]);
+        const double conv = hoa_norm(kN3D, orders[c], am) / hoa_norm(norm, orders[c], am);
+        out[(size_t)row * C + c] = (float)(D[sp * C + c] * k * conv);
+      }
+    }
+  });
+}
 
 int earhip_hoa_acn(int max_order, int *orders, int *degrees) {
   return guarded([&] {
@@ -107,7 +197,7 @@ int earhip_hoa_rotation_matrix(int n_coef, const int *orders, const int *degrees
                        q[2] * (q[3] * q[7] - q[4] * q[6]);
     require(std::fabs(det - 1.0) <= 1e-9, "q must be a proper rotation (determinant +1 to 1e-9)");
     // the same channels in N3D; R = (1/P) sum_p y(q x_p) y(x_p)^T over the design's directions (ADM axes: the decoder's
-    // mapping of the design's angles, api_panner.hip)
+    // mapping of the design's angles, tdesign_directions)
     Table t3;
     fill_table(t3, n_coef, orders, degrees, kN3D);
     const size_t C = (size_t)n_coef;

@@ -206,6 +206,13 @@ namespace earhip {
 // leaves out the extent panner's point grid (for callers that only pan points: the HOA design, DirectSpeakers)
 int panner_create(earhip_ctx *ctx, const char *layout, int n_channels, const double *azimuth, const double *elevation,
                   earhip_panner **out, bool with_extent);
+// its parameters (panner.h), and npos host directions xyz [npos][3] through k_pan_points: the panner's outputs in double,
+// [npos][2 for 0+2+0, else the loudspeakers without LFE], and in *missed the directions no region took.  Waits.
+struct PanParams;
+const PanParams &panner_params(const earhip_panner *p);
+std::vector<double> panner_pan_points(earhip_panner *p, size_t npos, const double *xyz, unsigned *missed);
+// the directions of the HOA decoder's t-design as unit vectors (api_hoa.hip), [points + extra_rows][3], the extra rows zero
+std::vector<double> tdesign_directions(size_t extra_rows = 0);
 }  // namespace earhip
 
 struct earhip_loudness;

@@ -1,6 +1,6 @@
 // extent_kernels.h — libear's polar extent panner (src/object_based/polar_extent.cpp:12-302, core:
 // src/object_based/polar_extent_scalar.cpp:25-108 / polar_extent_simd.hpp:28-134) as a batch kernel: ONE WAVE
-// per (object, metadata block).  Included by api_panner.hip behind the point source panner's device code.
+// per (object, metadata block), over the point source panner of panner.h.
 //
 // libear spreads an object with width / height / depth over 1652 points on the sphere (37 rows, 5 degrees
 // apart), each with the point source panner's gains precomputed: a weight per point (1 inside a "stadium"
@@ -10,7 +10,7 @@
 // reference's one SIMD kernel (float, xsimd batches of 4-16 points); everything before it is scalar double
 // set-up per call.
 //
-// Here the work is split between two kernels.  k_pan_objects (a thread per position, api_panner.hip) does what
+// Here the work is split between two kernels.  k_pan_objects (a thread per position, panner_kernels.h) does what
 // is scalar in libear — extentMod, the share of the spread part, the basis at the object's direction, the
 // stadium's parameters, the point source panner's gains for extents under 10 degrees — and leaves a JOB record
 // per position that needs spreading.  k_pan_objects_extent takes ONE WAVE per job:
@@ -28,6 +28,9 @@
 // order of the float additions differs from the scalar core's (as it does between the reference's scalar and
 // SIMD cores, which its tests hold to 1e-5: tests/extent_tests.cpp:140-169).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include "panner.h"
 
 namespace earhip {
 

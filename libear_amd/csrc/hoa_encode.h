@@ -1,6 +1,6 @@
 // hoa_encode.h — real spherical harmonics in libear's conventions (src/hoa/hoa.hpp:16-112: associated Legendre functions
 // without the Condon-Shortley phase, N3D / SN3D / FuMa norms, sqrt2 cos / -sqrt2 sin azimuth factors) as __host__ __device__
-// double-precision code: the decoder's harmonics (api_panner.hip) and the encoder of earhip group Q (api_hoa.hip), whose host
+// double-precision code: the decoder's harmonics (earhip_hoa_decode_matrix, api_hoa.hip) and the encoder of earhip group Q (api_hoa.hip), whose host
 // form and device kernel run the one core below.  The Makefile builds with -ffp-contract=off, so no FMA is formed and the two
 // differ only in the math library behind sin, cos, sqrt and fmod.
 #pragma once

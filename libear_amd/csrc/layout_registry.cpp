@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "layout_registry.h"
+#include "panner.h"
 
 using namespace earhip;
 
@@ -102,12 +103,12 @@ void triangulate(Definition &d) {
       d.facets.push_back((int)f.size());
       d.facets.insert(d.facets.end(), f.begin(), f.end());
     }
+    d.facets.push_back(0);
+    d.entry.facets = d.facets.data();
+    panner_dry_run(d.entry);  // (panner.h)
   } catch (const LayoutFailure &e) {
     throw Error{e.status, e.msg};
   }
-  d.facets.push_back(0);
-  d.entry.facets = d.facets.data();
-  panner_dry_run(d.entry);
 }
 
 }  // namespace

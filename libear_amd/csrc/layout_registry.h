@@ -30,8 +30,6 @@ struct LayoutFailure {
 // the BS.2051 rows, then the definitions; throws earhip::Error{EARHIP_UNKNOWN_LAYOUT, "unknown layout: NAME"}
 // (layout_registry.cpp).  The entry and everything it points at live as long as the process.
 const LayoutEntry &find_layout(const char *name);
-// a dry run of the region builder on the nominal positions (api_panner.hip): throws what a create would
-void panner_dry_run(const LayoutEntry &L);
 
 // One vertex of the augmented set, in polar form: a real loudspeaker, an extra one above or below a mid-layer
 // loudspeaker (its gain is mixed into that loudspeaker), or a virtual one straight below / above.

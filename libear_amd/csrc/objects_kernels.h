@@ -1,6 +1,6 @@
 // objects_kernels.h — channelLock, objectDivergence and zoneExclusion of an Objects audioBlockFormat (ITU-R BS.2127-0
 // 7.3.6, 7.3.7, 7.3.12, in the form include/earhip.h group I specifies: libear refuses all three) around the point
-// source and polar extent panners.  Included by api_panner.hip behind k_pan_objects.
+// source and polar extent panners (panner_kernels.h, extent_kernels.h).
 //
 // Per object: the position may be replaced by the nearest loudspeaker's (lock), then becomes one or three positions
 // with power weights (divergence); each goes through the extent panner as it stands; the weighted powers are summed
@@ -13,6 +13,10 @@
 // them in turn (extent_render, lane s carrying panner output s), accumulates w_k fin^2, applies the downmix of the
 // object's excluded set and writes the rows (extent_write).
 #pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "panner_kernels.h"
 
 namespace earhip {
 
