@@ -1316,8 +1316,8 @@ int earhip_render_limiter_position(earhip_render *r, size_t *samples);
  * unspecified non-finite values until earhip_iir_reset.  Earlier samples are untouched, and so are outputs fed only by other
  * rows.  There are no guard passes.
  *
- * Out of scope: per-route delays, changing coefficients or gains while running, crossfaded sets, float32 state, a multi-GPU
- * stage (run it on the rank that owns whole channels, as the meter of group L), attaching the stage to a renderer as groups L, M
+ * Out of scope: per-route delays (the delay matrix of group S does them, in front of this stage), changing coefficients or
+ * gains while running, crossfaded sets, float32 state, a multi-GPU stage (run it on the rank that owns whole channels, as the meter of group L), attaching the stage to a renderer as groups L, M
  * and N attach (feed it the rows a process call wrote: earhip_iir_process_device on the same context follows the call's kernels
  * on the stream).
  * ---------------------------------------------------------------------- */
@@ -1578,6 +1578,89 @@ int earhip_screen_apply_device(earhip_ctx *ctx, const earhip_screen *reference, 
                                const double *azimuth, const double *elevation, const unsigned char *screen_ref,
                                const unsigned char *lock_horizontal, const unsigned char *lock_vertical, double *azimuth_out,
                                double *elevation_out, int *status);
+
+/* ------------------------------------------------------------------------
+ * (S) Delay matrix — delays that differ per channel on the output bus, on the device: time alignment of loudspeakers at
+ * unequal distances, a subwoofer against its mains, a lip-sync offset on the whole bus.  Group D (libear's DelayBuffer) delays
+ * every channel by one amount; this stage is a sparse matrix of delayed short FIRs in the time domain.
+ *
+ * The operation, exactly (a caller can reproduce it).  n_in input rows, n_out output rows, a list of R routes; route r is
+ * (in_r, out_r, D_r, T_r, h_r[0 .. T_r)): D_r a whole delay in samples, h_r T_r float32 taps.  A pure gain or polarity is
+ * T = 1; a fractional delay is a designed h (earhip_delaymix_fractional).  One sample clock n counts since create or reset;
+ * x_c[i] = +0.0f for i < 0.
+ *     acc = +0.0f
+ *     for the routes with out_r = k, in ASCENDING LIST INDEX:
+ *       for j = 0 .. T_r - 1 in this order:
+ *         acc = fmaf(h_r[j], x_{in_r}[n - D_r - j], acc)
+ *     out_k[n] = acc
+ * (float32, every multiply-add fused: ONE rounding each; subnormals are kept).  An output without a route is written as +0.0f.
+ * An input without a route is never read: a NaN in it reaches nothing, and the host form does not look at its pointer.
+ * FIXED WINDOWS.  Every output is a fixed function of fixed windows in a fixed order, so
+ *   - the same samples give the same BITS however the stream is cut into calls (the project's rule for non-recursive stages);
+ *   - the device form and a plain C++ host form (std::fmaf in the order above) give the same bits;
+ *   - a non-finite input sample s of row c makes non-finite exactly those outputs n of the rows fed by a route r reading c for
+ *     which n - D_r - T_r + 1 <= s <= n - D_r, and no others;
+ *   - there are no atomics anywhere.
+ * LIMITS (anything outside is EARHIP_INVALID_ARGUMENT, checked before any device work): n_in and n_out in [1, 64]; R in
+ * [1, 512]; T_r in [1, 32]; D_r in [0, 65536]; every tap finite; max_samples >= 1.
+ *
+ * Out of scope: changing or crossfading routes while running, time-varying delays, PCM frames in or out of the stage, a
+ * multi-GPU stage, attaching the stage to a renderer as groups L, M and N attach (feed it the rows a process call wrote:
+ * earhip_delaymix_process_device on the same context follows the call's kernels on the stream).
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_delaymix earhip_delaymix;
+typedef struct earhip_delaymix_route {
+  int in;          /* [0, n_in) */
+  int out;         /* [0, n_out) */
+  int delay;       /* D in [0, 65536] */
+  int n_taps;      /* T in [1, 32] */
+  float taps[32];  /* the first T: h[0 .. T), finite */
+} earhip_delaymix_route;
+typedef struct earhip_delaymix_config {
+  int n_in;                            /* [1, 64] */
+  int n_out;                           /* [1, 64] */
+  int n_routes;                        /* R in [1, 512] */
+  const earhip_delaymix_route *routes; /* [R]; copied */
+  size_t max_samples;                  /* >= 1: the longest process call */
+} earhip_delaymix_config;
+typedef struct earhip_delaymix_properties {
+  int tile_out;        /* outputs of one tile of the kernel */
+  size_t launch_in;    /* inputs of one launch: a longer call runs as several launches */
+  int routes;          /* R */
+  int history;         /* H = max_r (D_r + T_r - 1) */
+  int max_fan_in;      /* the most routes into one output */
+  int total_taps;      /* sum of T_r */
+  size_t device_bytes; /* device memory the stage holds */
+} earhip_delaymix_properties;
+/* Everything is made here — the tap and route tables, the histories (the last H = max_r (D_r + T_r - 1) inputs of every row
+ * that is read, double-buffered: a call reads one and writes the other; a call shorter than H keeps the tail of the old
+ * history in front of its own samples), device rows and pinned staging for the host form: a process call allocates nothing,
+ * and earhip_delaymix_process_device synchronises nothing. */
+int earhip_delaymix_create(earhip_ctx *ctx, const earhip_delaymix_config *config, earhip_delaymix **out);
+int earhip_delaymix_destroy(earhip_delaymix *dm);
+int earhip_delaymix_reset(earhip_delaymix *dm); /* histories and clock to zero */
+int earhip_delaymix_info(const earhip_delaymix *dm, earhip_delaymix_properties *info);
+/* planar float32 rows in device memory: input i at in_dev + i * in_stride, output k at out_dev + k * out_stride, nsamples each,
+ * any nsamples in [0, max_samples]; the rows of in and out must not overlap; no alignment beyond a float's is asked of a row.
+ * nsamples > max_samples is EARHIP_INVALID_ARGUMENT and nothing is consumed.  Samples beyond nsamples and other rows are left
+ * alone.  Enqueues on the context's stream, allocates nothing, does not synchronise. */
+int earhip_delaymix_process_device(earhip_delaymix *dm, size_t nsamples, const float *in_dev, size_t in_stride, float *out_dev,
+                                   size_t out_stride);
+/* host rows in[n_in], out[n_out] (in[c] of a row no route reads may be anything): H2D + the above + D2H; synchronises */
+int earhip_delaymix_process(earhip_delaymix *dm, size_t nsamples, const float *const *in, float *const *out);
+/* Two pure host designers, no context and no device.
+ * earhip_delaymix_fractional: a delay of `delay` samples as a route's whole delay and n_taps = T taps (taps[T], float64; the
+ * route takes them as float32).  T = 1: whole = floor(delay + 0.5), the tap is 1.  T even in [2, 32]: with c = T / 2 - 1
+ * (delay >= c is required), whole = floor(delay - c), mu = delay - c - whole, t_j = j - c - mu,
+ *     h_j = sinc(t_j) I0(beta sqrt(max(0, 1 - (2 t_j / T)^2))) / I0(beta),   sinc(t) = sin(pi t) / (pi t), sinc(0) = 1,
+ * and h is then divided by its sum.  An odd T > 1, T outside [1, 32], beta < 0, a delay that is negative, non-finite or gives
+ * whole > 65536 is EARHIP_INVALID_ARGUMENT.
+ * earhip_delaymix_align: loudspeakers at distance_m[n] brought to the farthest one's arrival time and level:
+ * delay_samples[c] = (d_max - d_c) / speed_of_sound * sample_rate, gain[c] = d_c / d_max.  n < 1, a distance <= 0 or non-finite,
+ * a rate or speed <= 0 or non-finite is EARHIP_INVALID_ARGUMENT. */
+int earhip_delaymix_fractional(double delay, int n_taps, double beta, int *whole, double *taps);
+int earhip_delaymix_align(int n, const double *distance_m, double sample_rate, double speed_of_sound, double *delay_samples,
+                          double *gain);
 
 #ifdef __cplusplus
 }

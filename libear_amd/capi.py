@@ -1754,3 +1754,98 @@ class SampleRateConverter:
         if self.h:
             load().earhip_src_destroy(self.h)
             self.h = C.c_void_p()
+
+
+# (S) delay matrix
+
+class _DelaymixRoute(C.Structure):
+    _fields_ = [("in_", C.c_int), ("out", C.c_int), ("delay", C.c_int), ("n_taps", C.c_int), ("taps", C.c_float * 32)]
+
+
+class _DelaymixConfig(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("n_out", C.c_int), ("n_routes", C.c_int), ("routes", C.POINTER(_DelaymixRoute)),
+                ("max_samples", C.c_size_t)]
+
+
+class _DelaymixProperties(C.Structure):
+    _fields_ = [("tile_out", C.c_int), ("launch_in", C.c_size_t), ("routes", C.c_int), ("history", C.c_int),
+                ("max_fan_in", C.c_int), ("total_taps", C.c_int), ("device_bytes", C.c_size_t)]
+
+
+def delaymix_fractional(delay, n_taps=16, beta=8.0):
+    """(whole, taps float64 [n_taps]): a delay of `delay` samples as a route's whole delay and taps; n_taps = 1 rounds to the
+    nearest sample, an even n_taps is a Kaiser-windowed sinc centred on the fraction with unit DC gain.  A pure host function"""
+    T = _src_int("n_taps", n_taps)
+    whole, taps = C.c_int(0), np.zeros(T if 0 < T <= 32 else 1, np.float64)
+    load().earhip_delaymix_fractional.argtypes = [C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+    check(load().earhip_delaymix_fractional(float(delay), T, float(beta), C.byref(whole), C.c_void_p(taps.ctypes.data)))
+    return whole.value, taps
+
+
+def delaymix_align(distances_m, sample_rate, speed_of_sound=343.0):
+    """(delay_samples, gain), float64 [n]: loudspeakers at distances_m brought to the farthest one's arrival time and level.
+    A pure host function"""
+    d = np.ascontiguousarray(np.asarray(distances_m, np.float64).reshape(-1))
+    delay, gain = np.zeros(max(d.size, 1), np.float64), np.zeros(max(d.size, 1), np.float64)
+    load().earhip_delaymix_align.argtypes = [C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    check(load().earhip_delaymix_align(d.size, C.c_void_p(d.ctypes.data) if d.size else None, float(sample_rate),
+                                       float(speed_of_sound), C.c_void_p(delay.ctypes.data), C.c_void_p(gain.ctypes.data)))
+    return delay[:d.size], gain[:d.size]
+
+
+class DelayMatrix:
+    """(S) a sparse matrix of delayed short FIRs: routes = [(in, out, delay, taps)], delay a whole number of samples in
+    [0, 65536], taps 1 .. 32 float32 values (a gain: one tap); out_k[n] = the fmaf chain over the routes into k in list order of
+    taps[j] * x_in[n - delay - j]; the same bits however the stream is cut into calls."""
+
+    def __init__(self, ctx, n_in, n_out, routes, max_samples=48000):
+        n_in, n_out = _src_int("n_in", n_in), _src_int("n_out", n_out)
+        if isinstance(max_samples, bool) or not isinstance(max_samples, (int, np.integer)) or int(max_samples) < 1:
+            raise InvalidArgument(INVALID_ARGUMENT, "max_samples must be an integer >= 1")
+        routes = list(routes)
+        arr = (_DelaymixRoute * max(len(routes), 1))()
+        for i, route in enumerate(routes):
+            if len(route) != 4:
+                raise InvalidArgument(INVALID_ARGUMENT, "a route is (in, out, delay, taps)")
+            rin, rout, delay, taps = route
+            h = np.asarray(taps, np.float64).reshape(-1)
+            with np.errstate(over="ignore"):
+                h = h.astype(np.float32)
+            arr[i].in_, arr[i].out, arr[i].delay = _src_int("a route's in", rin), _src_int("a route's out", rout), _src_int("a route's delay", delay)
+            arr[i].n_taps = h.size
+            for j in range(min(h.size, 32)):
+                arr[i].taps[j] = h[j]
+        self.ctx, self.n_in, self.n_out = ctx, n_in, n_out
+        self.max_samples = int(max_samples)
+        cfg = _DelaymixConfig(n_in, n_out, len(routes), arr, self.max_samples)
+        self.h = C.c_void_p()
+        check(load().earhip_delaymix_create(ctx.h if ctx is not None else None, C.byref(cfg), C.byref(self.h)))
+
+    def info(self):
+        """dict: tile_out, launch_in, routes, history (H), max_fan_in, total_taps, device_bytes"""
+        v = _DelaymixProperties()
+        check(load().earhip_delaymix_info(self.h, C.byref(v)))
+        return {name: getattr(v, name) for name, _ in _DelaymixProperties._fields_}
+
+    def process(self, x):
+        """x [n_in][n] host array, any n -> [n_out][n]"""
+        x = _f32(x)
+        if x.ndim != 2 or x.shape[0] != self.n_in:
+            raise InvalidArgument(INVALID_ARGUMENT, "x must be [n_in][n]")
+        n = x.shape[1]
+        out = np.empty((self.n_out, n), np.float32)
+        check(load().earhip_delaymix_process(self.h, C.c_size_t(n), _chan_ptrs(x), _chan_ptrs(out)))
+        return out
+
+    def process_device(self, nsamples, in_ptr, in_stride, out_ptr, out_stride):
+        """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); enqueues on the context's stream"""
+        check(load().earhip_delaymix_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
+                                                    C.c_void_p(out_ptr), C.c_size_t(out_stride)))
+
+    def reset(self):
+        check(load().earhip_delaymix_reset(self.h))
+
+    def close(self):
+        if self.h:
+            load().earhip_delaymix_destroy(self.h)
+            self.h = C.c_void_p()

@@ -1,0 +1,167 @@
+// Drop-in test of ear::hip::DelayMatrix, compiled against the C++14 mirror headers only (libear_amd/host/ear/...).  A time
+// alignment of six loudspeakers at unequal distances (16-tap fractional delays, the designer's taps) plus the low end of the
+// mains summed into the LFE behind a whole delay, fed the float rows an ObjectsRenderer returned, must give the BITS of the
+// operation of include/earhip.h (group S) — written out here from the header, with std::fmaf, sample by sample; the device form
+// fed the same rows in the same calls must give the same bits; reset() starts over; configurations outside the header's limits
+// are refused.
+// Needs a GPU (without one the constructors throw: no CPU fallback).
+// Build (one line): g++ -std=c++14 -Wall -Wextra -Werror -Iinclude -Ilibear_amd/host tests/cpp/test_dropin_delaymix.cpp
+//            -Llibear_amd/lib -learhip -Wl,-rpath,$PWD/libear_amd/lib -o test_dropin_delaymix
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <string>
+#include <vector>
+
+#include <ear/decorrelate.hpp>
+#include <ear/dsp/objects_renderer.hpp>
+#include <ear/hip_delaymix.hpp>
+
+using ear::dsp::ObjectsRenderer;
+using ear::hip::DelayMatrix;
+
+static int g_failed = 0, g_checks = 0;
+#define CHECK(cond)                                                 \
+  do {                                                              \
+    g_checks++;                                                     \
+    if (!(cond)) {                                                  \
+      g_failed++;                                                   \
+      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+    }                                                               \
+  } while (0)
+
+static const size_t M = 13, N = 6, B = 512, T = 6, n = B * T;
+
+static void set_curves(ObjectsRenderer &r) {
+  for (size_t m = 0; m < M; m++) {
+    std::vector<int64_t> t = {0, (int64_t)(700 + 37 * m), (int64_t)(2 * n)};
+    std::vector<std::vector<float>> d, f;
+    for (int k = 0; k < 3; k++) {
+      std::vector<float> g(N), h(N);
+      for (size_t c = 0; c < N; c++) g[c] = 0.25f * (float)((m + c + k) % 7), h[c] = 0.15f * (float)((m * 3 + c + 2 * k) % 5);
+      d.push_back(g), f.push_back(h);
+    }
+    r.set_object_points(m, t, d, f);
+  }
+}
+
+// the header's operation over whole rows: out_k[i] = the chain over the routes into k in list order, x = +0.0f in front of the stream
+static std::vector<float> delay_mix(const std::vector<std::vector<float>> &x, const std::vector<DelayMatrix::Route> &routes, size_t k) {
+  std::vector<float> y(x[0].size());
+  for (size_t i = 0; i < y.size(); i++) {
+    float acc = 0.0f;
+    for (const DelayMatrix::Route &r : routes) {
+      if (r.out != k) continue;
+      for (size_t j = 0; j < r.taps.size(); j++) acc = std::fmaf(r.taps[j], r.delay + j <= i ? x[r.in][i - r.delay - j] : 0.0f, acc);
+    }
+    y[i] = acc;
+  }
+  return y;
+}
+
+int main() {
+  const std::vector<std::string> names = {"M+030", "M-030", "M+000", "LFE1", "M+110", "M-110"};
+  ObjectsRenderer r(M, N, B, ear::designDecorrelators(names), 255, T);
+  set_curves(r);
+  ear::hip::Context &ctx = ear::hip::default_context();
+
+  // the designers: the farthest loudspeaker gets no delay and unit gain; the taps pass DC
+  const std::vector<double> distances = {2.0, 2.35, 3.1, 1.2, 1.8, 1.95};
+  const std::vector<std::pair<double, double>> dg = DelayMatrix::align(distances, 48000.0);
+  CHECK(dg.size() == N && dg[2].first == 0.0 && dg[2].second == 1.0);
+  CHECK(std::fabs(dg[0].first - (3.1 - 2.0) / 343.0 * 48000.0) < 1e-9 && std::fabs(dg[0].second - 2.0 / 3.1) < 1e-12);
+  const std::pair<size_t, std::vector<float>> f = DelayMatrix::fractional(20.3, 16, 8.0);
+  double dc = 0;
+  for (float v : f.second) dc += v;
+  CHECK(f.first == 13 && f.second.size() == 16 && std::fabs(dc - 1.0) < 1e-6);
+  CHECK(DelayMatrix::fractional(3.5, 1).first == 4 && DelayMatrix::fractional(3.5, 1).second == std::vector<float>(1, 1.0f));
+
+  std::vector<DelayMatrix::Route> routes = DelayMatrix::alignment(distances, 48000.0);
+  CHECK(routes.size() == N && routes[2].in == 2 && routes[2].out == 2 && routes[2].delay == 0 && routes[2].taps.size() == 16);
+  for (size_t c = 0; c < N; c++)
+    if (c != 3) routes.push_back(DelayMatrix::Route{c, 3, 100 + 7 * c, {0.2f, -0.1f}});  // the mains into the LFE, behind its own route
+  DelayMatrix host(N, N, routes, n), device(N, N, routes, n);
+  CHECK(host.num_inputs() == N && host.num_outputs() == N);
+  CHECK(host.info().routes == (int)routes.size() && host.info().max_fan_in == 6 && host.info().total_taps == 6 * 16 + 5 * 2);
+  size_t history = 0;
+  for (const DelayMatrix::Route &q : routes) history = std::max(history, q.delay + q.taps.size() - 1);
+  CHECK(host.info().history == (int)history && history > 136);  // (the alignment of the nearest loudspeaker, not the LFE sums)
+
+  std::mt19937 rng(11);
+  std::uniform_real_distribution<float> u(-1.0f, 1.0f);
+  const size_t stride = 2 * n + 9;  // odd: rows are not made of 16-byte vectors
+  float *bus = ctx.alloc_host(N * stride), *sink = ctx.alloc_host(N * stride);
+  for (size_t i = 0; i < N * stride; i++) sink[i] = 9.0f;
+  std::vector<std::vector<float>> in(M, std::vector<float>(2 * n)), out(N, std::vector<float>(2 * n));
+  for (auto &row : in)
+    for (auto &v : row) v = 0.5f * u(rng);
+  std::vector<std::vector<float>> aligned(N, std::vector<float>(2 * n));
+  for (size_t call = 0; call < 2; call++) {
+    std::vector<const float *> ip;
+    std::vector<float *> op, mp;
+    for (auto &row : in) ip.push_back(row.data() + call * n);
+    for (auto &row : out) op.push_back(row.data() + call * n);
+    for (auto &row : aligned) mp.push_back(row.data() + call * n);
+    r.process(T, ip.data(), op.data());
+    // the host form, and the device form on rows in device-reachable memory
+    std::vector<const float *> rp(op.begin(), op.end());
+    host.process(n, rp.data(), mp.data());
+    for (size_t k = 0; k < N; k++) std::memcpy(bus + k * stride + call * n, out[k].data() + call * n, n * sizeof(float));
+    device.process_device(n, bus + call * n, stride, sink + call * n, stride);
+  }
+  ctx.synchronize();
+  for (size_t k = 0; k < N; k++) {
+    const std::vector<float> want = delay_mix(out, routes, k);
+    CHECK(std::memcmp(aligned[k].data(), want.data(), 2 * n * sizeof(float)) == 0);
+    CHECK(std::memcmp(sink + k * stride, want.data(), 2 * n * sizeof(float)) == 0);
+    for (size_t i = 2 * n; i < stride; i++) CHECK(sink[k * stride + i] == 9.0f);
+  }
+  std::printf("alignment and an LFE sum over a renderer's rows: %zu samples of %zu channels, the header's bits\n", 2 * n, N);
+
+  // a call longer than max_samples is refused and consumes nothing; reset() starts over
+  {
+    bool threw = false;
+    try {
+      device.process_device(n + 1, bus, stride, sink, stride);
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+  }
+  host.reset();
+  {
+    std::vector<float *> ip, mp;
+    std::vector<std::vector<float>> again(N, std::vector<float>(n));
+    for (auto &row : out) ip.push_back(row.data());
+    for (auto &row : again) mp.push_back(row.data());
+    host.process(n, ip.data(), mp.data());  // (the float** overload)
+    for (size_t k = 0; k < N; k++) CHECK(std::memcmp(again[k].data(), aligned[k].data(), n * sizeof(float)) == 0);
+  }
+
+  // configurations outside the header's limits
+  for (int which = 0; which < 9; which++) {
+    bool threw = false;
+    const std::vector<float> one(1, 1.0f);
+    try {
+      if (which == 0) DelayMatrix bad(N, N, std::vector<DelayMatrix::Route>(), n);                                    // no route
+      if (which == 1) DelayMatrix bad(N, N, {DelayMatrix::Route{N, 0, 0, one}}, n);                                   // in out of range
+      if (which == 2) DelayMatrix bad(N, N, {DelayMatrix::Route{0, 0, 65537, one}}, n);                               // delay
+      if (which == 3) DelayMatrix bad(N, N, {DelayMatrix::Route{0, 0, 0, std::vector<float>(33, 1.0f)}}, n);          // taps
+      if (which == 4) DelayMatrix bad(N, N, {DelayMatrix::Route{0, 0, 0, std::vector<float>()}}, n);                  // no tap
+      if (which == 5) DelayMatrix bad(N, N, {DelayMatrix::Route{0, 0, 0, {std::numeric_limits<float>::infinity()}}}, n);
+      if (which == 6) DelayMatrix bad(65, N, {DelayMatrix::Route{0, 0, 0, one}}, n);
+      if (which == 7) DelayMatrix bad(N, N, {DelayMatrix::Route{0, 0, 0, one}}, 0);
+      if (which == 8) (void)DelayMatrix::fractional(2.0, 16);  // shorter than the taps' centre
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+  }
+
+  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
+  return g_failed ? 1 : 0;
+}
