@@ -1,6 +1,7 @@
 // api_panner.hip — (I) the gain-vector producer for Objects content of include/earhip.h: the handle and the entry points.
 // The point source panner and the host set-up of a layout are panner.h (plain C++, also compiled on the CPU), the kernels
-// panner_kernels.h (a thread per position), extent_kernels.h (a wave per position that is spread) and objects_kernels.h
+// panner_kernels.h (a thread per position), extent_kernels.h (a wave per position that is spread, over the plain core of
+// extent.h) and objects_kernels.h
 // (channelLock, objectDivergence, zoneExclusion).  The HOA decode matrix, which pans the directions of a t-design through
 // panner_pan_points, is api_hoa.hip.
 #include <algorithm>
@@ -87,39 +88,14 @@ std::vector<double> earhip::panner_pan_points(earhip_panner *p, size_t npos, con
   });
 }
 
-// PolarExtent's constructor (src/object_based/polar_extent.cpp:16-50, :96-176): the 37 rows of points and the
-// point source panner's gains at each of them (device, one thread per point, double), kept as float
+// PolarExtent's constructor (src/object_based/polar_extent.cpp:16-50, :96-176): the 37 rows of points (extent_grid,
+// extent.h) and the point source panner's gains at each of them (device, one thread per point, double), kept as float
 static void build_extent_table(earhip_panner &pn) {
-  const double pi = 3.14159265358979323846264338327950288;
-  struct GridPoint {
-    Vec3 v;
-    int band;
-    double az;
-    int row;
-  };
-  std::vector<GridPoint> grid;
-  for (int r = 0; r < kExtentRows; r++) {
-    const double el = -90.0 + r * (180.0 / (kExtentRows - 1));
-    const double radius = std::cos(el * pi / 180.0);
-    int n_points = (int)std::round(((2 * pi * radius) / (2 * pi)) * 2 * (kExtentRows - 1));
-    if (n_points == 0) n_points = 1;
-    for (int i = 0; i < n_points; i++) {
-      const double az = i * (360.0 / n_points);
-      grid.push_back({polar_to_cart(az, el, 1.0), r / 8, az, r});
-    }
-  }
-  // The device kernel classifies CHUNKS of 64 points against an extent, so a chunk should be a compact patch:
-  // bands of 8 rows (40 degrees), each walked along the azimuth.  (The order of the points only changes the
-  // order of the float additions; libear's is row by row.)
-  std::stable_sort(grid.begin(), grid.end(), [](const GridPoint &a, const GridPoint &b) {
-    if (a.band != b.band) return a.band < b.band;
-    if (a.az != b.az) return a.az < b.az;
-    return a.row < b.row;
-  });
-  const size_t np = grid.size(), padded = (np + 63) / 64 * 64, n_chunks = padded / 64;
+  const ExtentGrid grid = extent_grid();
+  const size_t np = grid.points.size(), padded = grid.n_padded, n_chunks = grid.n_chunks;
   require(n_chunks <= (size_t)kExtentMaxChunks, "extent grid too large");
   std::vector<double> xyz(3 * np);
-  for (size_t q = 0; q < np; q++) xyz[3 * q] = grid[q].v.x, xyz[3 * q + 1] = grid[q].v.y, xyz[3 * q + 2] = grid[q].v.z;
+  for (size_t q = 0; q < np; q++) xyz[3 * q] = grid.points[q].x, xyz[3 * q + 1] = grid.points[q].y, xyz[3 * q + 2] = grid.points[q].z;
   const size_t S = pn.P.stereo ? 2 : (size_t)pn.P.table.n_real;
   unsigned missed = 0;
   const std::vector<double> G = panner_pan_points(&pn, np, xyz.data(), &missed);
@@ -131,26 +107,14 @@ static void build_extent_table(earhip_panner &pn) {
   }
   for (size_t q = 0; q < np; q++)
     for (size_t c = 0; c < S; c++) gains[c * padded + q] = (float)G[q * S + c];
-  // per chunk: mean direction, angular radius around it, float sum of the gain vectors
+  // per chunk: mean direction and angular radius around it (the grid's), float sum of the gain vectors
   const size_t MC = (size_t)kExtentMaxChunks;
   std::vector<float> chunks(3 * MC + MC + MC * kMaxPanOut, 0.0f);
   float *dir = chunks.data(), *rad = dir + 3 * MC, *sum = rad + MC;
   for (size_t c = 0; c < n_chunks; c++) {
     const size_t lo = 64 * c, hi = std::min(lo + 64, np);
-    Vec3 m = {0.0, 0.0, 0.0};
-    for (size_t q = lo; q < hi; q++) m = vadd(m, grid[q].v);
-    double n = std::sqrt(vdot(m, m));
-    if (n < 1e-6) m = grid[lo].v, n = 1.0;
-    // (the kernel works with the float direction: measure the radius around that)
-    const float fx = (float)(m.x / n), fy = (float)(m.y / n), fz = (float)(m.z / n);
-    const double fn = std::sqrt((double)fx * fx + (double)fy * fy + (double)fz * fz);
-    double worst = 0.0;
-    for (size_t q = lo; q < hi; q++) {
-      const double cs = (grid[q].v.x * fx + grid[q].v.y * fy + grid[q].v.z * fz) / fn;
-      worst = std::max(worst, std::acos(std::min(1.0, std::max(-1.0, cs))));
-    }
-    dir[c] = fx, dir[MC + c] = fy, dir[2 * MC + c] = fz;
-    rad[c] = (float)(worst + 1e-4);
+    for (size_t k = 0; k < 3; k++) dir[k * MC + c] = grid.chunk_dir[k * n_chunks + c];
+    rad[c] = grid.chunk_rad[c];
     for (size_t q = lo; q < hi; q++)
       for (size_t k = 0; k < S; k++) sum[c * kMaxPanOut + k] += gains[k * padded + q];
   }
