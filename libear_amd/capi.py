@@ -265,6 +265,11 @@ class ConvCtx:
         self.h = C.c_void_p()
         check(load().earhip_conv_ctx_create(ctx.h, C.c_size_t(block_size), C.byref(self.h)))
 
+    def close(self):
+        if self.h:
+            check(load().earhip_conv_ctx_destroy(self.h))
+            self.h = C.c_void_p()
+
 
 class ConvFilter:
     def __init__(self, cctx, taps):
@@ -274,6 +279,11 @@ class ConvFilter:
 
     def num_blocks(self):
         return load().earhip_conv_filter_num_blocks(self.h)
+
+    def close(self):
+        if self.h:
+            check(load().earhip_conv_filter_destroy(self.h))
+            self.h = C.c_void_p()
 
 
 class BlockConvolver:
@@ -305,6 +315,11 @@ class BlockConvolver:
             check(load().earhip_conv_process(self.h, _ptr(x), _ptr(out)))
         return out
 
+    def close(self):
+        if self.h:
+            check(load().earhip_conv_destroy(self.h))
+            self.h = C.c_void_p()
+
 
 class DelayBuffer:
     def __init__(self, ctx, nch, delay):
@@ -320,6 +335,11 @@ class DelayBuffer:
         out = np.empty_like(x)
         check(load().earhip_delay_process(self.h, C.c_size_t(x.shape[1]), _chan_ptrs(x), _chan_ptrs(out)))
         return out
+
+    def close(self):
+        if self.h:
+            check(load().earhip_delay_destroy(self.h))
+            self.h = C.c_void_p()
 
 
 class VariableBlockSizeAdapter:
