@@ -1333,10 +1333,25 @@ def loudness_layout_weights(layout):
     return w
 
 
-class Loudness:
+class _BusStage:
+    """what the output-bus stages share: the handle `h` of earhip_<_stem>_create goes back through earhip_<_stem>_reset and
+    earhip_<_stem>_destroy"""
+    _stem = None
+
+    def reset(self):
+        check(getattr(load(), f"earhip_{self._stem}_reset")(self.h))
+
+    def close(self):
+        if self.h:
+            getattr(load(), f"earhip_{self._stem}_destroy")(self.h)
+            self.h = C.c_void_p()
+
+
+class Loudness(_BusStage):
     """(L) the meter: K-weighted 100 ms step energies kept on the device, gated on request.  true_peak=True also measures
     true and sample peak with BS.1770-4's 4 x 12 interpolator (44100 and 48000 Hz); (phases, taps, coeffs [phases][taps]) brings
     another table."""
+    _stem = "loudness"
 
     def __init__(self, ctx, n_channels, sample_rate=48000, max_steps=36000, coeffs=None, true_peak=False):
         self.ctx, self.C = ctx, n_channels
@@ -1411,14 +1426,6 @@ class Loudness:
         check(load().earhip_loudness_result_range(self.h, C.c_void_p(w.ctypes.data), *[C.byref(v) for v in out]))
         return tuple(v.value for v in out)
 
-    def reset(self):
-        check(load().earhip_loudness_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_loudness_destroy(self.h)
-            self.h = C.c_void_p()
-
 
 # (M) FIR filter matrix
 
@@ -1427,11 +1434,12 @@ class _FirmixConfig(C.Structure):
                 ("max_blocks", C.c_int)]
 
 
-class FirMatrix:
+class FirMatrix(_BusStage):
     """(M) taps [K][C][J] float32: K outputs from C inputs through one J-tap FIR per pair, partitioned at block_size; pairs whose
     taps are all zero cost nothing and their input channels are never read.  n_sets: room for that many filter sets of this shape
     (earhip_firmix_create_sets: `taps` is set 0 and current; load_set / select switch and crossfade while it runs); None: a plain
     matrix (earhip_firmix_create)."""
+    _stem = "firmix"
 
     def __init__(self, ctx, taps, block_size, max_blocks=1, n_sets=None):
         taps = _f32(taps)
@@ -1497,14 +1505,6 @@ class FirMatrix:
         check(load().earhip_firmix_info(self.h, out))
         return {"n_in": out[0], "n_out": out[1], "block_size": out[2], "partitions": out[3], "pairs": out[4]}
 
-    def reset(self):
-        check(load().earhip_firmix_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_firmix_destroy(self.h)
-            self.h = C.c_void_p()
-
 
 # (N) look-ahead true-peak limiter
 
@@ -1513,10 +1513,11 @@ class _LimiterConfig(C.Structure):
                 ("hold", C.c_int), ("detect", C.c_int), ("tp", C.c_void_p), ("max_samples", C.c_size_t)]
 
 
-class Limiter:
+class Limiter(_BusStage):
     """(N) one gain for all channels that keeps every output sample under `ceiling`, looking `lookahead` samples ahead and
     holding `hold` samples; true_peak=True detects on BS.1770-4's 4 x 12 interpolator (44100 and 48000 Hz), (phases, taps,
     coeffs [phases][taps]) brings another table, False detects sample peaks only.  The output is delayed by latency() samples."""
+    _stem = "limiter"
 
     def __init__(self, ctx, n_channels, ceiling, lookahead=64, hold=480, sample_rate=48000, true_peak=True, max_samples=48000):
         for name, v in (("n_channels", n_channels), ("lookahead", lookahead), ("hold", hold), ("sample_rate", sample_rate),
@@ -1587,14 +1588,6 @@ class Limiter:
         check(load().earhip_limiter_stats(self.h, C.byref(g), C.byref(n), int(bool(reset))))
         return np.float32(g.value), n.value
 
-    def reset(self):
-        check(load().earhip_limiter_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_limiter_destroy(self.h)
-            self.h = C.c_void_p()
-
 
 # (O) biquad filter matrix
 
@@ -1620,9 +1613,10 @@ def iir_design(kind, sample_rate, f0, q=2.0 ** -0.5, gain_db=0.0):
     return out
 
 
-class IirBank:
+class IirBank(_BusStage):
     """(O) a matrix of biquad cascades: routes = [(in, out, gain, sections)], sections [S][5] = b0 b1 b2 a1 a2 with S in
     [0, 8] (S = 0, or None: a pure gain route); out_k = the sum of gain * filtered input over the routes into k."""
+    _stem = "iir"
 
     def __init__(self, ctx, n_in, n_out, routes, max_samples=48000):
         for name, v in (("n_in", n_in), ("n_out", n_out), ("max_samples", max_samples)):
@@ -1675,14 +1669,6 @@ class IirBank:
         check(load().earhip_iir_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
                                                C.c_void_p(out_ptr), C.c_size_t(out_stride)))
 
-    def reset(self):
-        check(load().earhip_iir_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_iir_destroy(self.h)
-            self.h = C.c_void_p()
-
 
 # (P) polyphase sample-rate converter
 
@@ -1715,9 +1701,10 @@ def src_design(up, down, taps_per_phase, beta=10.0, cutoff=1.0):
     return out
 
 
-class SampleRateConverter:
+class SampleRateConverter(_BusStage):
     """(P) a rational rate change by up / down on planar float32 rows: y = scipy.signal.upfirdn(taps, x, up, down) in float32,
     every output one chain of taps_per_phase fused multiply-adds; the same bits however the stream is cut into calls."""
+    _stem = "src"
 
     def __init__(self, ctx, channels, up, down, taps_per_phase, taps, max_samples=48000):
         channels, up, down = _src_int("channels", channels), _src_int("up", up), _src_int("down", down)
@@ -1767,14 +1754,6 @@ class SampleRateConverter:
                                                C.c_void_p(out_ptr), C.c_size_t(out_stride), C.c_size_t(out_capacity), C.byref(got)))
         return got.value
 
-    def reset(self):
-        check(load().earhip_src_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_src_destroy(self.h)
-            self.h = C.c_void_p()
-
 
 # (S) delay matrix
 
@@ -1813,10 +1792,11 @@ def delaymix_align(distances_m, sample_rate, speed_of_sound=343.0):
     return delay[:d.size], gain[:d.size]
 
 
-class DelayMatrix:
+class DelayMatrix(_BusStage):
     """(S) a sparse matrix of delayed short FIRs: routes = [(in, out, delay, taps)], delay a whole number of samples in
     [0, 65536], taps 1 .. 32 float32 values (a gain: one tap); out_k[n] = the fmaf chain over the routes into k in list order of
     taps[j] * x_in[n - delay - j]; the same bits however the stream is cut into calls."""
+    _stem = "delaymix"
 
     def __init__(self, ctx, n_in, n_out, routes, max_samples=48000):
         n_in, n_out = _src_int("n_in", n_in), _src_int("n_out", n_out)
@@ -1861,11 +1841,3 @@ class DelayMatrix:
         """planar float32 rows in device memory (e.g. torch tensors' data_ptr()); enqueues on the context's stream"""
         check(load().earhip_delaymix_process_device(self.h, C.c_size_t(nsamples), C.c_void_p(in_ptr), C.c_size_t(in_stride),
                                                     C.c_void_p(out_ptr), C.c_size_t(out_stride)))
-
-    def reset(self):
-        check(load().earhip_delaymix_reset(self.h))
-
-    def close(self):
-        if self.h:
-            load().earhip_delaymix_destroy(self.h)
-            self.h = C.c_void_p()

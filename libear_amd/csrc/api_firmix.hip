@@ -4,24 +4,32 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "bus_stage.h"
 #include "fft_launch.h"
 #include "firmix_kernels.h"
 
 using namespace earhip;
 
-struct earhip_firmix {
-  earhip_ctx *ctx = nullptr;
+struct earhip_firmix : BusStage {  // (a call's unit is a block of `block` samples)
+  static constexpr StageWords words = {
+      "matrix must not be NULL",
+      "device pointers must not be NULL", "device pointers must not be NULL",
+      "stride too small", "stride too small",
+      "in and out must not be NULL", "in and out must not be NULL",
+      "a row pointer of a channel that is read is NULL", "an output row pointer is NULL"};
+  earhip_firmix() { noun = "FIR matrix", room_name = "max_blocks"; }
+  ~earhip_firmix() override {
+    if (staged) (void)hipEventDestroy(staged);
+  }
   FirmixPlan plan;
-  int C = 0, K = 0, B = 0, P = 0, R = 0, max_blocks = 0;
+  int P = 0, R = 0;
   unsigned long long clock = 0;  // blocks since create / reset
-  int par = 0;                   // which half of `prev` holds the block before the next call
   // everything a process call touches, made at create
   DevBuf<cf> H, X, tw;
-  DevBuf<float> prev;  // [2][ring rows][B]
+  PingPong<float> prev;  // [2][ring rows][block]: the block before the next call
   DevBuf<int> rows, group_start;
   DevBuf<FirmixEntry> entries;
-  DevBuf<float> d_in, d_out;  // the host form's rows: [C][max_blocks B], [K][max_blocks B]
+  HostRows host;  // [n_in][max_blocks block], [n_out][max_blocks block]
   // filter sets (earhip_firmix_create_sets; n_sets == 0: a plain matrix, none of this is used).  H, entries and group_start
   // hold n_sets slices of the full width; the steady launch points at the current set's, the fade launch at two of them.
   int n_sets = 0, J = 0;
@@ -34,23 +42,23 @@ struct earhip_firmix {
   DevBuf<float> d_stage;              // [K C][P B]: the taps zero-padded to whole partitions (the padding is written once)
   hipEvent_t staged = nullptr;        // the copies out of the staging buffers have run
 
+  // the handle's shape from its plan, and the host form's rows
+  void shape_from_plan(int max_blocks) {
+    n_in = plan.n_in, n_out = plan.n_out, block = plan.block, P = plan.partitions, R = plan.ring, room = (size_t)max_blocks;
+    host.alloc((size_t)n_in * room * (size_t)block, (size_t)n_out * room * (size_t)block);
+  }
   size_t rows_used() const { return plan.used.size(); }
-  size_t set_spectra() const { return (size_t)K * (size_t)C * (size_t)P * (size_t)B; }
-  size_t set_entries() const { return firmix_set_entries_room(C, K); }
+  size_t set_spectra() const { return (size_t)n_out * (size_t)n_in * (size_t)P * (size_t)block; }
+  size_t set_entries() const { return firmix_set_entries_room(n_in, n_out); }
   size_t set_groups() const { return (size_t)plan.groups() + 1; }
   const cf *H_of(int s) const { return H.p + (size_t)s * set_spectra(); }
   const FirmixEntry *entries_of(int s) const { return entries.p + (size_t)s * set_entries(); }
   const int *groups_of(int s) const { return group_start.p + (size_t)s * set_groups(); }
 
-  void zero() {
-    EARHIP_HIP(hipMemsetAsync(prev.p, 0, sizeof(float) * prev.n, ctx->stream));
+  void zero() override {
+    prev.zero(ctx->stream);
     clock = 0;
-    par = 0;
     firmix_fade_end(fade);  // (a fade's target is current)
-  }
-
-  void check_room(size_t nblocks) const {
-    if (nblocks > (size_t)max_blocks) fail_invalid("the call would pass the FIR matrix's max_blocks (nothing was consumed)");
   }
 
   template <int L>
@@ -60,8 +68,7 @@ struct earhip_firmix {
       FirmixSpectraArgs s;
       s.in = in, s.in_stride = in_stride;
       s.rows = rows.p;
-      s.prev_in = prev.p + (size_t)par * rows_used() * (size_t)B;
-      s.prev_out = prev.p + (size_t)(par ^ 1) * rows_used() * (size_t)B;
+      s.prev_in = prev.in(), s.prev_out = prev.out();
       s.X = X.p, s.tw = tw.p;
       s.n = n, s.slot0 = slot0, s.R = R;
       hipLaunchKernelGGL((k_firmix_spectra<L, false>), dim3((unsigned)n, (unsigned)rows_used()), dim3(kFirmixThreads), 0, ctx->stream, s);
@@ -74,7 +81,7 @@ struct earhip_firmix {
       f.ea = entries_of(fade.from), f.eb = entries_of(fade.current);
       f.ga = groups_of(fade.from), f.gb = groups_of(fade.current);
       f.out = out, f.out_stride = out_stride;
-      f.K = K, f.P = P, f.slot0 = slot0, f.R = R;
+      f.K = n_out, f.P = P, f.slot0 = slot0, f.R = R;
       f.blocks_before = clock;
       f.q0 = fade.done, f.F = fade.total;
       hipLaunchKernelGGL((k_firmix_fade<L>), dim3((unsigned)nfade, (unsigned)plan.groups()), dim3(kFirmixThreads), 0, ctx->stream, f);
@@ -86,22 +93,22 @@ struct earhip_firmix {
       m.H = n_sets ? H_of(fade.current) : H.p;
       m.entries = n_sets ? entries_of(fade.current) : entries.p;
       m.group_start = n_sets ? groups_of(fade.current) : group_start.p;
-      m.out = out + (size_t)nfade * (size_t)B, m.out_stride = out_stride;
-      m.K = K, m.P = P, m.slot0 = firmix_ring_slot(slot0, nfade, 0, R), m.R = R;
+      m.out = out + (size_t)nfade * (size_t)block, m.out_stride = out_stride;
+      m.K = n_out, m.P = P, m.slot0 = firmix_ring_slot(slot0, nfade, 0, R), m.R = R;
       m.blocks_before = clock + (unsigned long long)nfade;
       hipLaunchKernelGGL((k_firmix_mac_inverse<L>), dim3((unsigned)(n - nfade), (unsigned)plan.groups()), dim3(kFirmixThreads), 0,
                          ctx->stream, m);
     }
     EARHIP_HIP(hipGetLastError());
     clock += (unsigned long long)n;
-    par ^= 1;
+    prev.flip();
   }
 
   // `pairs` rows of taps [P B] -> their spectra at Hdst
   template <int L>
   void spectra_of_taps_t(const float *staged, cf *Hdst, int pairs) {
     FirmixSpectraArgs s;
-    s.in = staged, s.in_stride = (size_t)P * (size_t)B;
+    s.in = staged, s.in_stride = (size_t)P * (size_t)block;
     s.rows = nullptr, s.prev_in = nullptr, s.prev_out = nullptr;
     s.X = Hdst, s.tw = tw.p;
     s.n = P, s.slot0 = 0, s.R = 0;
@@ -112,11 +119,10 @@ struct earhip_firmix {
   // f(the transform size 2 B as a constant): the kernels exist for blocks of 64 ... 4096 samples
   template <typename F>
   void with_transform_size(F &&f) {
-    fft_size_switch<128>(2 * B, f, [] { fail_internal("FIR matrix block size without a kernel"); });
+    fft_size_switch<128>(2 * block, f, [] { fail_internal("FIR matrix block size without a kernel"); });
   }
 
-  // device rows; the caller has checked the room and the strides
-  void feed(size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride) {
+  void feed(size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride) override {
     with_transform_size([&](auto L) { launch_t<decltype(L)::value>((int)nblocks, in, in_stride, out, out_stride); });
   }
   void spectra_of_taps(const float *staged, cf *Hdst, int pairs) {
@@ -131,9 +137,9 @@ struct earhip_firmix {
   }
   // taps [K][C][J] in memory the device reads (pinned or device): pad to whole partitions, transform into the set's slice
   void transform_set(int set, const float *taps, hipMemcpyKind kind) {
-    EARHIP_HIP(hipMemcpy2DAsync(d_stage.p, sizeof(float) * (size_t)P * (size_t)B, taps, sizeof(float) * (size_t)J,
-                                sizeof(float) * (size_t)J, (size_t)K * (size_t)C, kind, ctx->stream));
-    spectra_of_taps(d_stage.p, H.p + (size_t)set * set_spectra(), K * C);
+    EARHIP_HIP(hipMemcpy2DAsync(d_stage.p, sizeof(float) * (size_t)P * (size_t)block, taps, sizeof(float) * (size_t)J,
+                                sizeof(float) * (size_t)J, (size_t)n_out * (size_t)n_in, kind, ctx->stream));
+    spectra_of_taps(d_stage.p, H.p + (size_t)set * set_spectra(), n_out * n_in);
   }
   // the lists of a set to the device, behind every call enqueued so far; the staging buffers are free again at `staged`
   void put_lists(int set, const FirmixSetLists &l) {
@@ -148,8 +154,8 @@ struct earhip_firmix {
     set_pairs[(size_t)set] = l.n_pairs;
   }
   void load_host(int set, const float *taps) {
-    const size_t ntaps = (size_t)K * (size_t)C * (size_t)J;
-    FirmixSetLists l = firmix_make_set_lists(C, K, J, taps);
+    const size_t ntaps = (size_t)n_out * (size_t)n_in * (size_t)J;
+    FirmixSetLists l = firmix_make_set_lists(n_in, n_out, J, taps);
     EARHIP_HIP(hipEventSynchronize(staged));  // an earlier load's copies have left the staging buffers
     std::memcpy(stage.p, taps, sizeof(float) * ntaps);
     transform_set(set, stage.p, hipMemcpyHostToDevice);
@@ -164,23 +170,17 @@ struct earhip_firmix {
                               hipMemcpyDeviceToDevice, ctx->stream));
     EARHIP_HIP(hipMemcpyAsync(entries.p + (size_t)set * set_entries(), dense_en.p, sizeof(FirmixEntry) * set_entries(),
                               hipMemcpyDeviceToDevice, ctx->stream));
-    set_pairs[(size_t)set] = K * C;
+    set_pairs[(size_t)set] = n_out * n_in;
     loaded[(size_t)set] = 1;
   }
   DevBuf<int> dense_gs;
   DevBuf<FirmixEntry> dense_en;
 };
 
-namespace earhip {
-void firmix_check_room(const earhip_firmix *fm, size_t nblocks) { fm->check_room(nblocks); }
-void firmix_feed(earhip_firmix *fm, size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride) {
-  fm->feed(nblocks, in, in_stride, out, out_stride);
+template <>
+BusStage *earhip::as_stage<earhip_firmix>(earhip_firmix *h) {
+  return h;
 }
-const earhip_ctx *firmix_ctx(const earhip_firmix *fm) { return fm->ctx; }
-int firmix_inputs(const earhip_firmix *fm) { return fm->C; }
-int firmix_outputs(const earhip_firmix *fm) { return fm->K; }
-int firmix_block(const earhip_firmix *fm) { return fm->B; }
-}  // namespace earhip
 
 extern "C" {
 
@@ -196,21 +196,15 @@ int earhip_firmix_create(earhip_ctx *ctx, const earhip_firmix_config *cfg, earhi
     fm->ctx = ctx;
     fm->plan = firmix_make_plan(cfg->n_in, cfg->n_out, cfg->block_size, cfg->n_taps, cfg->max_blocks, cfg->taps);
     const FirmixPlan &p = fm->plan;
-    fm->C = p.n_in, fm->K = p.n_out, fm->B = p.block, fm->P = p.partitions, fm->R = p.ring, fm->max_blocks = cfg->max_blocks;
-    const size_t B = (size_t)p.block, PB = (size_t)p.partitions * B;
+    fm->shape_from_plan(cfg->max_blocks);
+    const size_t PB = (size_t)p.partitions * (size_t)p.block;
     upload_twiddles(fm->tw, 2 * p.block);
     fm->H.alloc(p.spectra_elems());
     fm->X.alloc(p.ring_elems());
-    fm->prev.alloc(p.state_elems());
-    fm->rows.alloc(p.used.size());
-    fm->group_start.alloc(p.group_start.size());
-    fm->entries.alloc(p.entries.size());
-    if (!p.used.empty()) EARHIP_HIP(hipMemcpy(fm->rows.p, p.used.data(), sizeof(int) * p.used.size(), hipMemcpyHostToDevice));
-    EARHIP_HIP(hipMemcpy(fm->group_start.p, p.group_start.data(), sizeof(int) * p.group_start.size(), hipMemcpyHostToDevice));
-    if (!p.entries.empty())
-      EARHIP_HIP(hipMemcpy(fm->entries.p, p.entries.data(), sizeof(FirmixEntry) * p.entries.size(), hipMemcpyHostToDevice));
-    fm->d_in.alloc((size_t)p.n_in * (size_t)cfg->max_blocks * B);
-    fm->d_out.alloc((size_t)p.n_out * (size_t)cfg->max_blocks * B);
+    fm->prev.alloc(p.state_elems() / 2);
+    fm->rows.upload(p.used);
+    fm->group_start.upload(p.group_start);
+    fm->entries.upload(p.entries);
     if (p.n_pairs) {  // the non-zero pairs' taps, zero-padded to whole partitions, through the forward pass
       std::vector<float> staged((size_t)p.n_pairs * PB, 0.0f);
       for (int k = 0; k < p.n_out; k++)
@@ -220,14 +214,11 @@ int earhip_firmix_create(earhip_ctx *ctx, const earhip_firmix_config *cfg, earhi
                       sizeof(float) * (size_t)p.n_taps);
         }
       DevBuf<float> d_taps;
-      d_taps.alloc(staged.size());
-      EARHIP_HIP(hipMemcpy(d_taps.p, staged.data(), sizeof(float) * staged.size(), hipMemcpyHostToDevice));
+      d_taps.upload(staged);
       fm->spectra_of_taps(d_taps.p, fm->H.p, p.n_pairs);
       EARHIP_HIP(hipStreamSynchronize(ctx->stream));  // (d_taps goes away)
     }
-    fm->zero();
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    *out = fm.release();
+    stage_ready(fm, out);
   });
 }
 
@@ -248,7 +239,7 @@ int earhip_firmix_create_sets(earhip_ctx *ctx, const earhip_firmix_config *cfg, 
     p.partitions = firmix_partitions(cfg->n_taps, cfg->block_size);
     p.ring = firmix_ring_slots(p.partitions, cfg->max_blocks);
     for (int c = 0; c < p.n_in; c++) p.used.push_back(c), p.row_of.push_back(c);
-    fm->C = p.n_in, fm->K = p.n_out, fm->B = p.block, fm->P = p.partitions, fm->R = p.ring, fm->max_blocks = cfg->max_blocks;
+    fm->shape_from_plan(cfg->max_blocks);
     fm->n_sets = n_sets, fm->J = cfg->n_taps;
     fm->loaded.assign((size_t)n_sets, 0);
     fm->set_pairs.assign((size_t)n_sets, 0);
@@ -256,28 +247,21 @@ int earhip_firmix_create_sets(earhip_ctx *ctx, const earhip_firmix_config *cfg, 
     upload_twiddles(fm->tw, 2 * p.block);
     fm->H.alloc((size_t)n_sets * fm->set_spectra());
     fm->X.alloc(p.ring_elems());
-    fm->prev.alloc(p.state_elems());
-    fm->rows.alloc(p.used.size());
-    EARHIP_HIP(hipMemcpy(fm->rows.p, p.used.data(), sizeof(int) * p.used.size(), hipMemcpyHostToDevice));
+    fm->prev.alloc(p.state_elems() / 2);
+    fm->rows.upload(p.used);
     fm->group_start.alloc((size_t)n_sets * fm->set_groups());
     fm->entries.alloc((size_t)n_sets * fm->set_entries());
     const FirmixSetLists dense = firmix_make_set_lists(p.n_in, p.n_out, p.n_taps, nullptr);
-    fm->dense_gs.alloc(dense.group_start.size());
-    fm->dense_en.alloc(dense.entries.size());
-    EARHIP_HIP(hipMemcpy(fm->dense_gs.p, dense.group_start.data(), sizeof(int) * dense.group_start.size(), hipMemcpyHostToDevice));
-    EARHIP_HIP(hipMemcpy(fm->dense_en.p, dense.entries.data(), sizeof(FirmixEntry) * dense.entries.size(), hipMemcpyHostToDevice));
+    fm->dense_gs.upload(dense.group_start);
+    fm->dense_en.upload(dense.entries);
     fm->stage.reserve(ntaps);
     fm->stage_gs.reserve(fm->set_groups());
     fm->stage_en.reserve(fm->set_entries());
     fm->d_stage.alloc_zero((size_t)p.n_out * (size_t)p.n_in * (size_t)p.partitions * B, ctx->stream);
     EARHIP_HIP(hipEventCreateWithFlags(&fm->staged, hipEventDisableTiming));
     EARHIP_HIP(hipEventRecord(fm->staged, ctx->stream));
-    fm->d_in.alloc((size_t)p.n_in * (size_t)cfg->max_blocks * B);
-    fm->d_out.alloc((size_t)p.n_out * (size_t)cfg->max_blocks * B);
     fm->load_host(0, cfg->taps);
-    fm->zero();
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    *out = fm.release();
+    stage_ready(fm, out);
   });
 }
 
@@ -285,7 +269,7 @@ int earhip_firmix_load_set(earhip_firmix *fm, int set, const float *taps) {
   return guarded([&] {
     require(fm != nullptr && taps != nullptr, "matrix and taps must not be NULL");
     fm->check_loadable(set);
-    require(firmix_taps_finite(taps, (size_t)fm->K * (size_t)fm->C * (size_t)fm->J), "every tap must be finite");
+    require(firmix_taps_finite(taps, (size_t)fm->n_out * (size_t)fm->n_in * (size_t)fm->J), "every tap must be finite");
     fm->ctx->use();
     fm->load_host(set, taps);
   });
@@ -325,61 +309,25 @@ int earhip_firmix_set_info(const earhip_firmix *fm, int set, int info[2]) {
   });
 }
 
-int earhip_firmix_destroy(earhip_firmix *fm) {
-  return guarded([&] {
-    if (!fm) return;
-    (void)hipSetDevice(fm->ctx->device);
-    (void)hipStreamSynchronize(fm->ctx->stream);
-    if (fm->staged) (void)hipEventDestroy(fm->staged);
-    delete fm;
-  });
-}
-
-int earhip_firmix_reset(earhip_firmix *fm) {
-  return guarded([&] {
-    require(fm != nullptr, "matrix must not be NULL");
-    fm->ctx->use();
-    fm->zero();
-  });
-}
+int earhip_firmix_destroy(earhip_firmix *fm) { return stage_destroy(fm); }
+int earhip_firmix_reset(earhip_firmix *fm) { return stage_reset(fm); }
 
 int earhip_firmix_info(const earhip_firmix *fm, int info[5]) {
   return guarded([&] {
     require(fm != nullptr && info != nullptr, "matrix and info must not be NULL");
-    info[0] = fm->C, info[1] = fm->K, info[2] = fm->B, info[3] = fm->P;
+    info[0] = fm->n_in, info[1] = fm->n_out, info[2] = fm->block, info[3] = fm->P;
     info[4] = fm->n_sets ? fm->set_pairs[(size_t)fm->fade.current] : fm->plan.n_pairs;
   });
 }
 
 int earhip_firmix_process_device(earhip_firmix *fm, size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev,
                                  size_t out_stride) {
-  return guarded([&] {
-    require(fm != nullptr, "matrix must not be NULL");
-    fm->check_room(nblocks);
-    if (nblocks == 0) return;
-    require(in_dev != nullptr && out_dev != nullptr, "device pointers must not be NULL");
-    require(in_stride >= nblocks * (size_t)fm->B && out_stride >= nblocks * (size_t)fm->B, "stride too small");
-    fm->ctx->use();
-    fm->feed(nblocks, in_dev, in_stride, out_dev, out_stride);
-  });
+  return guarded([&] { stage_process_device(fm, nblocks, in_dev, in_stride, out_dev, out_stride); });
 }
 
+// (a channel without a pair is not read here either: plan.row_of is -1 for it)
 int earhip_firmix_process(earhip_firmix *fm, size_t nblocks, const float *const *in, float *const *out) {
-  return guarded([&] {
-    require(fm != nullptr, "matrix must not be NULL");
-    fm->check_room(nblocks);
-    if (nblocks == 0) return;
-    require(in != nullptr && out != nullptr, "in and out must not be NULL");
-    for (int c : fm->plan.used) require(in[c] != nullptr, "a row pointer of a channel that is read is NULL");
-    for (int k = 0; k < fm->K; k++) require(out[k] != nullptr, "an output row pointer is NULL");
-    earhip_ctx *ctx = fm->ctx;
-    ctx->use();
-    const size_t n = nblocks * (size_t)fm->B;
-    rows_to_device(fm->d_in.p, in, fm->C, n, ctx->stream, &fm->plan.used);  // (a channel without a pair is not read here either)
-    fm->feed(nblocks, fm->d_in.p, n, fm->d_out.p, n);
-    rows_from_device(out, fm->d_out.p, fm->K, n, ctx->stream);
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-  });
+  return guarded([&] { stage_process_host(fm, nblocks, in, out, [&](int c) { return fm->plan.row_of[(size_t)c] >= 0; }); });
 }
 
 }  // extern "C"

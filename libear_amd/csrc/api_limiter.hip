@@ -3,28 +3,33 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "bus_stage.h"
 #include "limiter_kernels.h"
 #include "pcm_frames.h"
 
 using namespace earhip;
 
-struct earhip_limiter {
-  earhip_ctx *ctx = nullptr;
-  int C = 0;
+struct earhip_limiter : BusStage {  // (n_in = n_out = the channels)
+  static constexpr StageWords words = {
+      "limiter must not be NULL",
+      "device pointers must not be NULL", "device pointers must not be NULL",
+      "stride too small", "stride too small",
+      "in and out must not be NULL", "in and out must not be NULL",
+      "a row pointer is NULL", "a row pointer is NULL"};
+  earhip_limiter() { noun = "limiter", room_name = "max_samples"; }
   float c = 0.0f;
   int detect = 0;
   LimiterShape sh;
-  size_t max_samples = 0;
   unsigned long long clock = 0;  // samples since create / reset: the output clock (the dither's t)
-  int par = 0;                   // which half of xhist / rhist holds the history in front of the next launch
   float h[4][12];                // the table where its shape is 4 x 12
   // everything a process call touches, made at create
-  DevBuf<float> table, xhist, rhist, ones, r;  // [phases][taps]; [2][C][HX]; [2][HR]; [HR] of 1.0f; [max launch]
-  DevBuf<unsigned> stat_min;                   // [kLimSlots]
-  DevBuf<unsigned long long> stat_count;       // [kLimSlots]
-  DevBuf<float> d_in, d_out, d_gain;           // the host form's rows and the PCM form's: [C][max_samples] each, [max_samples]
-  PcmLevels levels;                            // the PCM form's
+  DevBuf<float> table, ones, r;           // [phases][taps]; [HR] of 1.0f; [max launch]
+  PingPong<float> xhist, rhist;           // [2][C][HX]; [2][HR]: flipped together
+  DevBuf<unsigned> stat_min;              // [kLimSlots]
+  DevBuf<unsigned long long> stat_count;  // [kLimSlots]
+  HostRows host;                          // the host form's rows and the PCM form's: [C][max_samples] each
+  DevBuf<float> d_gain;                   // [max_samples]
+  PcmLevels levels;                       // the PCM form's
 
   // a launch's sample indices are ints
   static constexpr size_t kMaxLaunch = (size_t)1 << 24;
@@ -33,29 +38,23 @@ struct earhip_limiter {
     EARHIP_HIP(hipMemsetAsync(stat_min.p, 0, sizeof(unsigned) * stat_min.n, ctx->stream));
     EARHIP_HIP(hipMemsetAsync(stat_count.p, 0, sizeof(unsigned long long) * stat_count.n, ctx->stream));
   }
-  void zero() {
-    EARHIP_HIP(hipMemsetAsync(xhist.p, 0, sizeof(float) * xhist.n, ctx->stream));
-    for (int b = 0; b < 2; b++)  // r = 1 before the clock starts
-      EARHIP_HIP(hipMemcpyAsync(rhist.p + (size_t)b * (size_t)sh.r_hist(), ones.p, sizeof(float) * (size_t)sh.r_hist(),
-                                hipMemcpyDeviceToDevice, ctx->stream));
+  void zero() override {
+    xhist.zero(ctx->stream);
+    rhist.rewind();
+    for (float *half : {rhist.in(), rhist.out()})  // r = 1 before the clock starts
+      EARHIP_HIP(hipMemcpyAsync(half, ones.p, sizeof(float) * (size_t)sh.r_hist(), hipMemcpyDeviceToDevice, ctx->stream));
     zero_stats();
     levels.zero(ctx->stream);
     clock = 0;
-    par = 0;
-  }
-
-  void check_room(size_t nsamples) const {
-    if (nsamples > max_samples) fail_invalid("the call would pass the limiter's max_samples (nothing was consumed)");
   }
 
   void launch(size_t n, const float *in, size_t in_stride, float *out, size_t out_stride, float *gain) {
     LimArgs a;
     a.in = in, a.in_stride = in_stride, a.out = out, a.out_stride = out_stride, a.gain = gain;
-    a.n = (unsigned)n, a.C = C, a.c = c;
+    a.n = (unsigned)n, a.C = n_in, a.c = c;
     a.L = sh.L, a.M = sh.M, a.K = sh.K, a.D = sh.D, a.HX = sh.x_hist(), a.HR = sh.r_hist(), a.phases = sh.phases, a.taps = sh.taps;
-    const size_t xh = (size_t)C * (size_t)a.HX, rh = (size_t)a.HR;
-    a.xhist_in = xhist.p + (size_t)par * xh, a.xhist_out = xhist.p + (size_t)(par ^ 1) * xh;
-    a.rhist_in = rhist.p + (size_t)par * rh, a.rhist_out = rhist.p + (size_t)(par ^ 1) * rh;
+    a.xhist_in = xhist.in(), a.xhist_out = xhist.out();
+    a.rhist_in = rhist.in(), a.rhist_out = rhist.out();
     a.r = r.p;
     a.stat_min = stat_min.p, a.stat_count = stat_count.p;
     a.table = table.p;
@@ -72,28 +71,25 @@ struct earhip_limiter {
     hipLaunchKernelGGL(k_lim_apply, dim3((unsigned)((n + kLimTile - 1) / kLimTile)), dim3(kLimThreads), lds, ctx->stream, a);
     EARHIP_HIP(hipGetLastError());
     clock += n;
-    par ^= 1;
+    xhist.flip(), rhist.flip();
   }
 
-  // device rows; the caller has checked the room and the strides
-  void feed(size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride, float *gain) {
-    const size_t most = std::min(kMaxLaunch, r.n);
-    for (size_t at = 0; at < nsamples;) {
-      const size_t n = std::min(most, nsamples - at);
+  // gain: a row [nsamples] for the gain, or NULL
+  void feed_gain(size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride, float *gain) {
+    for_each_launch(nsamples, std::min(kMaxLaunch, r.n), [&](size_t at, size_t n, size_t) {
       launch(n, in + at, in_stride, out + at, out_stride, gain ? gain + at : nullptr);
-      at += n;
-    }
+      return n;
+    });
+  }
+  void feed(size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride) override {
+    feed_gain(nsamples, in, in_stride, out, out_stride, nullptr);
   }
 };
 
-namespace earhip {
-void limiter_check_room(const earhip_limiter *lim, size_t nsamples) { lim->check_room(nsamples); }
-void limiter_feed(earhip_limiter *lim, size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride) {
-  lim->feed(nsamples, in, in_stride, out, out_stride, nullptr);
+template <>
+BusStage *earhip::as_stage<earhip_limiter>(earhip_limiter *h) {
+  return h;
 }
-const earhip_ctx *limiter_ctx(const earhip_limiter *lim) { return lim->ctx; }
-int limiter_channels(const earhip_limiter *lim) { return lim->C; }
-}  // namespace earhip
 
 extern "C" {
 
@@ -110,47 +106,27 @@ int earhip_limiter_create(earhip_ctx *ctx, const earhip_limiter_config *cfg, ear
     ctx->use();
     std::unique_ptr<earhip_limiter> lim(new earhip_limiter);
     lim->ctx = ctx;
-    lim->C = cfg->n_channels, lim->c = cfg->ceiling, lim->detect = cfg->detect;
+    lim->n_in = lim->n_out = cfg->n_channels, lim->c = cfg->ceiling, lim->detect = cfg->detect;
     lim->sh = limiter_shape(cfg->lookahead, cfg->hold, cfg->detect, table.phases, table.taps);
-    lim->max_samples = cfg->max_samples;
+    lim->room = cfg->max_samples;
     std::memcpy(lim->h, table.h, sizeof(lim->h));
     const size_t C = (size_t)cfg->n_channels, HR = (size_t)lim->sh.r_hist();
-    lim->table.alloc(table.v.size());
-    if (!table.v.empty()) EARHIP_HIP(hipMemcpy(lim->table.p, table.v.data(), sizeof(float) * table.v.size(), hipMemcpyHostToDevice));
-    lim->xhist.alloc(2 * C * (size_t)lim->sh.x_hist());
-    lim->rhist.alloc(2 * HR);
-    lim->ones.alloc(HR);
-    const std::vector<float> ones(HR, 1.0f);
-    EARHIP_HIP(hipMemcpy(lim->ones.p, ones.data(), sizeof(float) * HR, hipMemcpyHostToDevice));
+    lim->table.upload(table.v);
+    lim->xhist.alloc(C * (size_t)lim->sh.x_hist());
+    lim->rhist.alloc(HR);
+    lim->ones.upload(std::vector<float>(HR, 1.0f));
     lim->r.alloc(std::min(cfg->max_samples, earhip_limiter::kMaxLaunch));
     lim->stat_min.alloc(kLimSlots);
     lim->stat_count.alloc(kLimSlots);
-    lim->d_in.alloc(C * cfg->max_samples);
-    lim->d_out.alloc(C * cfg->max_samples);
+    lim->host.alloc(C * cfg->max_samples, C * cfg->max_samples);
     lim->d_gain.alloc(cfg->max_samples);
     lim->levels.reserve(cfg->n_channels, ctx->stream);
-    lim->zero();
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    *out = lim.release();
+    stage_ready(lim, out);
   });
 }
 
-int earhip_limiter_destroy(earhip_limiter *lim) {
-  return guarded([&] {
-    if (!lim) return;
-    (void)hipSetDevice(lim->ctx->device);
-    (void)hipStreamSynchronize(lim->ctx->stream);
-    delete lim;
-  });
-}
-
-int earhip_limiter_reset(earhip_limiter *lim) {
-  return guarded([&] {
-    require(lim != nullptr, "limiter must not be NULL");
-    lim->ctx->use();
-    lim->zero();
-  });
-}
+int earhip_limiter_destroy(earhip_limiter *lim) { return stage_destroy(lim); }
+int earhip_limiter_reset(earhip_limiter *lim) { return stage_reset(lim); }
 
 int earhip_limiter_latency(const earhip_limiter *lim, int *samples) {
   return guarded([&] {
@@ -162,31 +138,24 @@ int earhip_limiter_latency(const earhip_limiter *lim, int *samples) {
 int earhip_limiter_process_device(earhip_limiter *lim, size_t nsamples, const float *in_dev, size_t in_stride, float *out_dev,
                                   size_t out_stride, float *gain_dev) {
   return guarded([&] {
-    require(lim != nullptr, "limiter must not be NULL");
-    lim->check_room(nsamples);
-    if (nsamples == 0) return;
-    require(in_dev != nullptr && out_dev != nullptr, "device pointers must not be NULL");
-    require(in_stride >= nsamples && out_stride >= nsamples, "stride too small");
+    if (!stage_admits(lim, nsamples)) return;
+    check_device_rows(earhip_limiter::words, nsamples, in_dev, in_stride, nsamples, out_dev, out_stride);
     lim->ctx->use();
-    lim->feed(nsamples, in_dev, in_stride, out_dev, out_stride, gain_dev);
+    lim->feed_gain(nsamples, in_dev, in_stride, out_dev, out_stride, gain_dev);
   });
 }
 
 int earhip_limiter_process(earhip_limiter *lim, size_t nsamples, const float *const *in, float *const *out, float *gain) {
   return guarded([&] {
-    require(lim != nullptr, "limiter must not be NULL");
-    lim->check_room(nsamples);
-    if (nsamples == 0) return;
-    require(in != nullptr && out != nullptr, "in and out must not be NULL");
-    for (int c = 0; c < lim->C; c++) require(in[c] != nullptr && out[c] != nullptr, "a row pointer is NULL");
-    earhip_ctx *ctx = lim->ctx;
-    ctx->use();
+    if (!stage_admits(lim, nsamples)) return;
     const size_t n = nsamples;
-    rows_to_device(lim->d_in.p, in, lim->C, n, ctx->stream);
-    lim->feed(n, lim->d_in.p, n, lim->d_out.p, n, gain ? lim->d_gain.p : nullptr);
-    rows_from_device(out, lim->d_out.p, lim->C, n, ctx->stream);
-    if (gain) EARHIP_HIP(hipMemcpyAsync(gain, lim->d_gain.p, sizeof(float) * n, hipMemcpyDeviceToHost, ctx->stream));
-    EARHIP_HIP(hipStreamSynchronize(ctx->stream));
+    check_host_rows(earhip_limiter::words, n, in, lim->n_in, reads_every_row, n, out, lim->n_out);
+    hipStream_t stream = lim->ctx->stream;
+    lim->ctx->use();
+    lim->host.to_device(in, lim->n_in, n, stream, reads_every_row);
+    lim->feed_gain(n, lim->host.d_in.p, n, lim->host.d_out.p, n, gain ? lim->d_gain.p : nullptr);
+    if (gain) EARHIP_HIP(hipMemcpyAsync(gain, lim->d_gain.p, sizeof(float) * n, hipMemcpyDeviceToHost, stream));
+    lim->host.from_device(out, lim->n_out, n, stream);
   });
 }
 
@@ -194,7 +163,7 @@ int earhip_limiter_process_pcm_device(earhip_limiter *lim, size_t nsamples, cons
                                       size_t out_frame_bytes, size_t out_first_byte, const earhip_pcm_out *out) {
   return guarded([&] {
     require(lim != nullptr, "limiter must not be NULL");
-    check_pcm_out_frame(lim->C, check_pcm_out(out), out_dev, out_frame_bytes, out_first_byte, "n_channels");
+    check_pcm_out_frame(lim->n_in, check_pcm_out(out), out_dev, out_frame_bytes, out_first_byte, "n_channels");
     lim->check_room(nsamples);
     if (nsamples == 0) return;
     require(in_dev != nullptr, "in_dev must not be NULL");
@@ -202,8 +171,8 @@ int earhip_limiter_process_pcm_device(earhip_limiter *lim, size_t nsamples, cons
     earhip_ctx *ctx = lim->ctx;
     ctx->use();
     const int64_t t0 = (int64_t)lim->clock;
-    lim->feed(nsamples, in_dev, in_stride, lim->d_out.p, nsamples, nullptr);
-    launch_rows_to_pcm(*out, lim->d_out.p, nsamples, lim->C, nsamples, static_cast<unsigned char *>(out_dev), out_frame_bytes,
+    lim->feed(nsamples, in_dev, in_stride, lim->host.d_out.p, nsamples);
+    launch_rows_to_pcm(*out, lim->host.d_out.p, nsamples, lim->n_in, nsamples, static_cast<unsigned char *>(out_dev), out_frame_bytes,
                        out_first_byte, lim->levels.peak.p, lim->levels.clip.p, t0, ctx->stream);
   });
 }
@@ -215,7 +184,7 @@ int earhip_limiter_output_levels(earhip_limiter *lim, float *peak, uint64_t *cli
     earhip_ctx *ctx = lim->ctx;
     ctx->use();
     EARHIP_HIP(hipStreamSynchronize(ctx->stream));
-    lim->levels.read(lim->C, peak, clipped);
+    lim->levels.read(lim->n_in, peak, clipped);
     if (reset) lim->levels.zero(ctx->stream);
   });
 }

@@ -11,7 +11,7 @@
 #include <memory>
 #include <vector>
 
-#include "common.h"
+#include "bus_stage.h"
 #include "curves.h"
 #include "decor_stage.h"
 #include "host_pipeline.h"
@@ -250,48 +250,53 @@ struct earhip_render {
   // enqueued in order.  An attached limiter (earhip_render_attach_limiter) comes behind the meter and the matrix, which both see
   // the unlimited bus, and writes the limited rows to its own sink.  Without a tap this is render_spans and nothing else.
   struct BusTap {
-    float *sink = nullptr;
+    BusStage *stage = nullptr;  // NULL: nothing attached
+    float *sink = nullptr;      // (the meter has none)
     size_t stride = 0, cap = 0, pos = 0;
-    // a stage is attached (on: its sink is checked first) or detached; either way the tap starts at 0
-    void attach(bool on, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
-      if (on) {
+  };
+  enum { TAP_METER, TAP_MATRIX, TAP_LIMITER, TAP_COUNT };  // the order they are fed in
+  BusTap taps[TAP_COUNT];
+  bool tapped() const {
+    for (const BusTap &t : taps)
+      if (t.stage) return true;
+    return false;
+  }
+  // a stage is attached or (NULL) detached; either way the tap starts at 0.  rows_words: the refusal of a stage with other rows
+  // than the bus; a stage that writes brings its sink
+  void attach(int which, BusStage *stage, const char *rows_words, bool writes, float *sink_dev, size_t sink_stride,
+              size_t sink_capacity) {
+    if (stage) {
+      const std::string the = std::string("the ") + stage->noun;
+      if (stage->ctx != ctx) fail_invalid(the + " must belong to the renderer's context");
+      require(stage->n_in == N, rows_words);
+      if (stage->block != 1 && stage->block != B) fail_invalid(the + " must have the renderer's block size");
+      if (writes) {
         require(sink_dev != nullptr, "sink_dev must not be NULL");
         require(sink_stride >= sink_capacity, "sink_stride must be >= sink_capacity");
       }
-      *this = on ? BusTap{sink_dev, sink_stride, sink_capacity, 0} : BusTap{};
     }
-  };
-  earhip_loudness *meter = nullptr;
-  earhip_firmix *fm = nullptr;
-  earhip_limiter *lim = nullptr;
-  BusTap fm_tap, lim_tap;
+    taps[which] = stage && writes ? BusTap{stage, sink_dev, sink_stride, sink_capacity, 0} : BusTap{stage};
+  }
   // a tap that has no room for the call refuses it before anything is rendered
   void check_taps(size_t nblocks) const {
     const size_t n = nblocks * (size_t)B;
-    if (meter) loudness_check_room(meter, n);
-    if (fm) {
-      firmix_check_room(fm, nblocks);
-      if (fm_tap.pos + n > fm_tap.cap) fail_invalid("the call would pass the FIR matrix's sink_capacity (nothing was rendered)");
-    }
-    if (lim) {
-      limiter_check_room(lim, n);
-      if (lim_tap.pos + n > lim_tap.cap) fail_invalid("the call would pass the limiter's sink_capacity (nothing was rendered)");
+    for (const BusTap &t : taps) {
+      if (!t.stage) continue;
+      t.stage->check_room(n / (size_t)t.stage->block);
+      if (t.sink && t.pos + n > t.cap)
+        fail_invalid(std::string("the call would pass the ") + t.stage->noun + "'s sink_capacity (nothing was rendered)");
     }
   }
   void feed_taps(size_t nblocks, const float *out_dev, size_t out_stride) {
     const size_t n = nblocks * (size_t)B;
-    if (meter) loudness_feed(meter, n, out_dev, out_stride);
-    if (fm) {
-      firmix_feed(fm, nblocks, out_dev, out_stride, fm_tap.sink + fm_tap.pos, fm_tap.stride);
-      fm_tap.pos += n;
-    }
-    if (lim) {
-      limiter_feed(lim, n, out_dev, out_stride, lim_tap.sink + lim_tap.pos, lim_tap.stride);
-      lim_tap.pos += n;
+    for (BusTap &t : taps) {
+      if (!t.stage) continue;
+      t.stage->feed(n / (size_t)t.stage->block, out_dev, out_stride, t.sink ? t.sink + t.pos : nullptr, t.stride);
+      if (t.sink) t.pos += n;
     }
   }
   void process_device(size_t nblocks, const float *in_dev, size_t in_stride, float *out_dev, size_t out_stride) {
-    if (!meter && !fm && !lim) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
+    if (!tapped()) return render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
     check_taps(nblocks);
     render_spans(nblocks, in_dev, in_stride, out_dev, out_stride);
     feed_taps(nblocks, out_dev, out_stride);
@@ -502,52 +507,34 @@ int earhip_render_reset(earhip_render *r, int64_t sample_time) {
 int earhip_render_attach_loudness(earhip_render *r, earhip_loudness *m) {
   return guarded([&] {
     require(r != nullptr, "render must not be NULL");
-    if (m) {
-      require(loudness_ctx(m) == r->ctx, "the meter must belong to the renderer's context");
-      require(loudness_channels(m) == r->N, "the meter must have n_out channels");
-    }
-    r->meter = m;
+    r->attach(earhip_render::TAP_METER, as_stage(m), "the meter must have n_out channels", false, nullptr, 0, 0);
   });
 }
 
 int earhip_render_attach_firmix(earhip_render *r, earhip_firmix *fm, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
   return guarded([&] {
     require(r != nullptr, "render must not be NULL");
-    if (fm) {
-      require(firmix_ctx(fm) == r->ctx, "the FIR matrix must belong to the renderer's context");
-      require(firmix_inputs(fm) == r->N, "the FIR matrix must have n_in = the renderer's n_out");
-      require(firmix_block(fm) == r->B, "the FIR matrix must have the renderer's block size");
-    }
-    r->fm_tap.attach(fm != nullptr, sink_dev, sink_stride, sink_capacity);
-    r->fm = fm;
-  });
-}
-
-int earhip_render_firmix_position(earhip_render *r, size_t *samples) {
-  return guarded([&] {
-    require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
-    *samples = r->fm_tap.pos;
+    r->attach(earhip_render::TAP_MATRIX, as_stage(fm), "the FIR matrix must have n_in = the renderer's n_out", true, sink_dev,
+              sink_stride, sink_capacity);
   });
 }
 
 int earhip_render_attach_limiter(earhip_render *r, earhip_limiter *lim, float *sink_dev, size_t sink_stride, size_t sink_capacity) {
   return guarded([&] {
     require(r != nullptr, "render must not be NULL");
-    if (lim) {
-      require(limiter_ctx(lim) == r->ctx, "the limiter must belong to the renderer's context");
-      require(limiter_channels(lim) == r->N, "the limiter must have n_channels = the renderer's n_out");
-    }
-    r->lim_tap.attach(lim != nullptr, sink_dev, sink_stride, sink_capacity);
-    r->lim = lim;
+    r->attach(earhip_render::TAP_LIMITER, as_stage(lim), "the limiter must have n_channels = the renderer's n_out", true, sink_dev,
+              sink_stride, sink_capacity);
   });
 }
 
-int earhip_render_limiter_position(earhip_render *r, size_t *samples) {
+static int tap_position(earhip_render *r, int which, size_t *samples) {
   return guarded([&] {
     require(r != nullptr && samples != nullptr, "render and samples must not be NULL");
-    *samples = r->lim_tap.pos;
+    *samples = r->taps[which].pos;
   });
 }
+int earhip_render_firmix_position(earhip_render *r, size_t *samples) { return tap_position(r, earhip_render::TAP_MATRIX, samples); }
+int earhip_render_limiter_position(earhip_render *r, size_t *samples) { return tap_position(r, earhip_render::TAP_LIMITER, samples); }
 
 int earhip_render_process_device(earhip_render *r, size_t nblocks, const float *in_dev,
                                  size_t in_stride, float *out_dev, size_t out_stride) {

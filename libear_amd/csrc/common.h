@@ -87,6 +87,11 @@ struct DevBuf {
   void reserve(size_t count) {
     if (count > n) alloc(count);
   }
+  // a host table to the device, at create (waits)
+  void upload(const std::vector<T> &v) {
+    alloc(v.size());
+    if (!v.empty()) EARHIP_HIP(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+  }
 };
 
 // Pinned host staging buffer.
@@ -109,18 +114,6 @@ struct PinBuf {
     n = count;
   }
 };
-
-// The small host forms' rows: C pageable rows of n samples to or from a device buffer [C][n], enqueued on a stream (`only`: just
-// the rows listed there — the others' pointers are not looked at).
-inline void rows_to_device(float *dev, const float *const *rows, int C, size_t n, hipStream_t s, const std::vector<int> *only = nullptr) {
-  for (int i = 0; i < (only ? (int)only->size() : C); i++) {
-    const int c = only ? (*only)[(size_t)i] : i;
-    EARHIP_HIP(hipMemcpyAsync(dev + (size_t)c * n, rows[c], sizeof(float) * n, hipMemcpyHostToDevice, s));
-  }
-}
-inline void rows_from_device(float *const *rows, const float *dev, int C, size_t n, hipStream_t s) {
-  for (int c = 0; c < C; c++) EARHIP_HIP(hipMemcpyAsync(rows[c], dev + (size_t)c * n, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-}
 
 }  // namespace earhip
 
@@ -213,36 +206,4 @@ const PanParams &panner_params(const earhip_panner *p);
 std::vector<double> panner_pan_points(earhip_panner *p, size_t npos, const double *xyz, unsigned *missed);
 // the directions of the HOA decoder's t-design as unit vectors (api_hoa.hip), [points + extra_rows][3], the extra rows zero
 std::vector<double> tdesign_directions(size_t extra_rows = 0);
-}  // namespace earhip
-
-struct earhip_loudness;
-namespace earhip {
-// the programme loudness meter (api_loudness.hip) as the renderer's tap sees it (earhip_render_attach_loudness): does a call of
-// nsamples fit its step store (throws EARHIP_INVALID_ARGUMENT), and the meter's kernels over planar device rows on the context's stream
-void loudness_check_room(const earhip_loudness *m, size_t nsamples);
-void loudness_feed(earhip_loudness *m, size_t nsamples, const float *rows, size_t stride);
-const earhip_ctx *loudness_ctx(const earhip_loudness *m);
-int loudness_channels(const earhip_loudness *m);
-}  // namespace earhip
-
-struct earhip_firmix;
-namespace earhip {
-// the FIR filter matrix (api_firmix.hip) as the renderer's tap sees it (earhip_render_attach_firmix): does a call of nblocks fit
-// its scratch (throws EARHIP_INVALID_ARGUMENT), and its two passes over planar device rows on the context's stream
-void firmix_check_room(const earhip_firmix *fm, size_t nblocks);
-void firmix_feed(earhip_firmix *fm, size_t nblocks, const float *in, size_t in_stride, float *out, size_t out_stride);
-const earhip_ctx *firmix_ctx(const earhip_firmix *fm);
-int firmix_inputs(const earhip_firmix *fm);
-int firmix_outputs(const earhip_firmix *fm);
-int firmix_block(const earhip_firmix *fm);
-}  // namespace earhip
-
-struct earhip_limiter;
-namespace earhip {
-// the look-ahead limiter (api_limiter.hip) as the renderer's tap sees it (earhip_render_attach_limiter): does a call of nsamples
-// fit its scratch (throws EARHIP_INVALID_ARGUMENT), and its two passes over planar device rows on the context's stream
-void limiter_check_room(const earhip_limiter *lim, size_t nsamples);
-void limiter_feed(earhip_limiter *lim, size_t nsamples, const float *in, size_t in_stride, float *out, size_t out_stride);
-const earhip_ctx *limiter_ctx(const earhip_limiter *lim);
-int limiter_channels(const earhip_limiter *lim);
 }  // namespace earhip

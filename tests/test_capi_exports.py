@@ -120,6 +120,20 @@ def test_staging_path_helpers_on_cpu(tmp_path):
     assert res.returncode == 0, res.stdout
 
 
+def test_launch_cuts_on_cpu(tmp_path):
+    """libear_amd/csrc/launch_cuts.h (what every output-bus stage cuts its calls with): for n in {0, 1, most - 1, most, most + 1,
+    2 most + 1} and most in {1, 7, 2^24} the pieces are in order, sum to n, are each <= most and all equal to most but the last;
+    the two-halves index arithmetic over four flips — under ASan + UBSan"""
+    exe = tmp_path / "test_launch_cuts"
+    src = os.path.join(ROOT, "tests", "cpp", "test_launch_cuts.cpp")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "libear_amd", "csrc"), src, "-o", str(exe)], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
+    assert res.returncode == 0, res.stdout
+
+
 def test_launch_plans_fit_the_bus_buffer_on_cpu(tmp_path):
     """libear_amd/csrc/curves.h: every plan plan_mix makes fits bus_samples_bound() (host code, hipcc)"""
     exe = tmp_path / "test_plan_bounds"

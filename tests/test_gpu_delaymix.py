@@ -46,6 +46,7 @@ def run_device(ctx, mx, x, calls=None, odd=False):
     rows_in[:, :n] = torch.from_numpy(np.ascontiguousarray(x)).cuda()
     out = torch.full(((mx.n_out + 2) * so + 4,), 7.5, dtype=torch.float32, device="cuda")
     assert xin.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    torch.cuda.synchronize()  # (the canaries are torch's work on its own stream: done before the context's stream writes among them)
     at = 0
     for k in calls:
         mx.process_device(k, xin.data_ptr() + 4 * (off + at), si, out.data_ptr() + 4 * (off + so + at), so)
@@ -263,3 +264,37 @@ def test_in_front_of_the_biquad_matrix_on_one_stream(ctx):
     finally:
         mx.close()
         bank.close()
+
+
+def test_the_host_form_never_looks_at_the_row_of_an_input_without_a_route(ctx):
+    """include/earhip.h, group S: the host form does not look at the pointer of an input without a route.  3 -> 2, two routes, input 2
+    unrouted, one tile + 3 samples, through the library's own symbols (the wrapper cannot pass a NULL row): a NULL pointer there
+    gives the bits of a NaN row there; a NULL pointer of an input that is read is EARHIP_INVALID_ARGUMENT and consumes nothing"""
+    import ctypes as C
+    from libear_amd import capi
+    lib = capi.load()
+    tile, _ = tile_of(ctx)
+    n = tile + 3
+    routes = [(0, 0, 5, dm.taps_for(2, 21)), (1, 1, 0, [-0.5])]
+    x = dm.noise(3, n, seed=23)
+    x[2] = np.nan
+
+    def call(mx, null_row):
+        rows = capi._chan_ptrs(x)
+        if null_row is not None:
+            rows[null_row] = None
+        out = np.full((2, n), 7.5, np.float32)
+        return lib.earhip_delaymix_process(mx.h, C.c_size_t(n), rows, capi._chan_ptrs(out)), out
+
+    mx, fresh = make(ctx, 3, 2, routes, n), make(ctx, 3, 2, routes, n)
+    try:
+        rc, with_nan = call(fresh, None)
+        assert rc == capi.OK and np.isfinite(with_nan).all()
+        rc, untouched = call(mx, 1)  # an input that is read
+        assert rc == capi.INVALID_ARGUMENT and (untouched == 7.5).all()
+        rc, with_null = call(mx, 2)  # the next valid call: a fresh matrix's bits, the unread row's pointer NULL
+        assert rc == capi.OK, lib.earhip_last_error()
+        assert np.array_equal(dm.bits(with_null), dm.bits(with_nan))
+    finally:
+        mx.close()
+        fresh.close()

@@ -365,3 +365,39 @@ def test_a_meter_and_a_matrix_together(ctx):
         m.close()
         alone.close()
         r.close()
+
+
+def test_the_host_form_never_looks_at_the_row_of_a_channel_without_a_pair(ctx):
+    """include/earhip.h, group M: the pointer of an input channel that is never read is not looked at.  3 -> 2 at B = 64, 2 blocks, input 2
+    without a pair, through the library's own symbols (the wrapper cannot pass a NULL row): a NULL pointer there gives the bits
+    of a NaN row there; a NULL pointer of a channel that is read is EARHIP_INVALID_ARGUMENT and consumes nothing"""
+    import ctypes as C
+    from libear_amd import capi
+    lib = capi.load()
+    B, T = 64, 2
+    rng = np.random.default_rng(77)
+    h = rng.uniform(-0.1, 0.1, (2, 3, B + 7)).astype(np.float32)
+    h[:, 2] = 0.0
+    x = rng.uniform(-1.0, 1.0, (3, T * B)).astype(np.float32)
+    x[2] = np.nan
+
+    def call(m, null_row):
+        rows = capi._chan_ptrs(x)
+        if null_row is not None:
+            rows[null_row] = None
+        out = np.full((2, T * B), 7.5, np.float32)
+        return lib.earhip_firmix_process(m.h, C.c_size_t(T), rows, capi._chan_ptrs(out)), out
+
+    m, fresh = capi.FirMatrix(ctx, h, B, max_blocks=T), capi.FirMatrix(ctx, h, B, max_blocks=T)
+    try:
+        assert m.info()["pairs"] == 4
+        rc, with_nan = call(fresh, None)
+        assert rc == capi.OK and np.isfinite(with_nan).all()
+        rc, untouched = call(m, 1)  # a channel that is read
+        assert rc == capi.INVALID_ARGUMENT and (untouched == 7.5).all()
+        rc, with_null = call(m, 2)  # the next valid call: a fresh matrix's bits, the unread row's pointer NULL
+        assert rc == capi.OK, lib.earhip_last_error()
+        assert np.array_equal(bits(with_null), bits(with_nan))
+    finally:
+        m.close()
+        fresh.close()

@@ -38,7 +38,7 @@ Tile (:757-767): Grid 256 (no call here is long enough for 512, :877), Pieces 25
 gsplit, split-operand kernels and F32Grid (:788-793): doubles while g < 16, ntiles * mnz * mgroups * g < 512 and M / (2 g) >= 64:
   96 and 33 objects: 1 (96 / 2 < 64).  288 objects at 64 columns: 288 / 2 = 144, 288 / 4 = 72, 288 / 8 = 36 < 64: 4 (at most 4 tiles x 2
   groups x 4 = 32 workgroups: the other bound is far).
-gsplit, slot lists (:908-922; max_waves = 4, tiles_per_wg = 4: common.h:175-176):
+gsplit, slot lists (:908-922; max_waves = 4, tiles_per_wg = 4: common.h:168-169):
   96 objects, mgroups = 2 (49 .. 96 columns): tpw = min(4, ntiles, 4 / 2) = 2 (:909; :914 leaves it: ceil(96 / 128) = 1), wsplit =
      max(1, min(4 / (2 * 2), 96 / 8)) = 1, per_wg = 96; g doubles while (ntiles / 2) * g < 512 and 96 / (2 g) >= 8: 48, 24, 12, then
      96 / 16 = 6: gsplit 8.

@@ -2,6 +2,7 @@
     python tools/render_digest.py            (EARHIP_LIB=<another build of libearhip.so>: the same list through that build)
     python tools/render_digest.py k2         (the second list: the decorrelator stage and the transforms' launch layer, at the end)
     python tools/render_digest.py paths      (the third list: the rare paths of the split-operand gain kernels, at the end)
+    python tools/render_digest.py bus        (the fourth list: the output-bus stages alone and attached, and their refusals, at the end)
 One line per case: its name, what the renderer reports about the call (gain kernel, tile, tiles, object splits, list layout, whether
 the device handed the call to the stand-by lists or ran the robust form) and the digest of the output rows.  Two builds whose host
 code enqueues the same kernels on the same data print the same lines; a refactor of the launch code is compared this way.
@@ -274,8 +275,324 @@ def run_paths(kind, opts, n_out, unaligned):
     print(f"{name:42s} {what}\n    {sha(outs[0])} {sha(outs[1])}")
 
 
+# ---- the fourth list (argument "bus"): the stages of the output bus (bus_stage.h) --------------------------------------------
+# Every stage alone, in its device form and its host form: three consecutive calls of unequal lengths (1 sample, a tile + 3, two
+# tiles + 331; the FIR matrix: 1, 2 and 3 blocks of 64), reset, the first call again; an input row nothing reads where the stage
+# has that notion.  A call one sample longer than a launch (delay matrix, biquad matrix, converter).  A renderer of 16 objects and 5
+# outputs in blocks of 64 with meter, matrix and limiter attached, through every form of call and a host call that runs as a pipeline
+# of chunks, one stage detached at the end; the same with 32 objects (the fewest the split-operand gain kernels take) for a call cut
+# into a main span and a tail.  Every call the stages' shared checks refuse:
+# its status and message, and behind each a valid call in the same form whose digest is that of a stage never refused anything.
+def bus_stages(ctx):
+    """name -> (make(), rows in, the tile the call lengths are built on); made anew for each form"""
+    rng = np.random.default_rng(12)
+    fir = rng.uniform(-0.1, 0.1, (2, 3, 64 + 7)).astype(np.float32)
+    fir[:, 2] = 0.0  # (input 2 has no pair)
+    lp, hs = capi.iir_design("lowpass", 48000, 1000.0), capi.iir_design("high_shelf", 48000, 4000.0, gain_db=3.0)
+    src_taps = capi.src_design(3, 2, 8)
+    dly = rng.uniform(-0.5, 0.5, 2).astype(np.float32)
+    return {
+        "loudness": (lambda: capi.Loudness(ctx, 2, 48000, max_steps=8, true_peak=True), 2, 4800),
+        "firmix": (lambda: capi.FirMatrix(ctx, fir, 64, max_blocks=3), 3, 64),
+        "limiter": (lambda: capi.Limiter(ctx, 2, 0.5, max_samples=4096), 2, 1024),
+        "iir": (lambda: capi.IirBank(ctx, 3, 2, [(0, 0, 1.0, [lp]), (1, 1, 0.5, None), (2, 1, 0.25, [lp, hs])], max_samples=4096), 3, 256),
+        "src": (lambda: capi.SampleRateConverter(ctx, 2, 3, 2, 8, src_taps, max_samples=4096), 2, 1024),
+        "delaymix": (lambda: capi.DelayMatrix(ctx, 3, 2, [(0, 0, 5, dly), (1, 1, 0, [-0.5])], max_samples=4096), 3, 1024),
+    }
+
+
+def bus_lengths(name, tile):
+    return [64, 128, 192] if name == "firmix" else [1, tile + 3, 2 * tile + 331]
+
+
+def stage_call(name, st, x, device, ctx):
+    """one call of the stage on x [rows][n] -> what it hands back (the meter: its step energies and peaks so far)"""
+    import torch
+    n = x.shape[1]
+    if not device:
+        if name == "loudness":
+            st.process(x)
+        elif name == "limiter":
+            out, gain = st.process(x, with_gain=True)
+            return np.concatenate([out.reshape(-1), gain])
+        else:
+            return st.process(x)
+    else:
+        xi = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        rows_out = st.K if name == "firmix" else getattr(st, "n_out", x.shape[0])  # (the others: as many as come in)
+        cap = st.next_out(n) if name == "src" else n
+        o = torch.full((rows_out, cap + 3), 7.5, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+        if name == "loudness":
+            st.process_device(n, xi.data_ptr(), n)
+        elif name == "firmix":
+            st.process_device(n // 64, xi.data_ptr(), n, o.data_ptr(), cap + 3)
+        elif name == "src":
+            assert st.process_device(n, xi.data_ptr(), n, o.data_ptr(), cap + 3, cap) == cap
+        else:
+            st.process_device(n, xi.data_ptr(), n, o.data_ptr(), cap + 3)
+        ctx.synchronize()
+        if name != "loudness":
+            return o.cpu().numpy()
+    return np.concatenate([st.steps().reshape(-1), np.concatenate(st.peaks()).astype(np.float64)])
+
+
+def run_bus_stages(ctx):
+    for name, (make, rows, tile) in bus_stages(ctx).items():
+        lengths = bus_lengths(name, tile)
+        x = scenes.audio(rows, sum(lengths), seed=51)
+        for device in (True, False):
+            st = make()
+            outs, at = [], 0
+            for n in lengths:
+                outs.append(stage_call(name, st, x[:, at:at + n], device, ctx))
+                at += n
+            st.reset()
+            outs.append(stage_call(name, st, x[:, :lengths[0]], device, ctx))
+            st.close()
+            print(f"{'bus_%s_%s' % (name, 'device' if device else 'host'):42s}\n    {' '.join(sha(o) for o in outs)}")
+    # one sample more than a launch, where a stage says what its launch holds (the delay matrix: launch_in; the biquad matrix: a
+    # chunk in front of and behind scan_groups x scan_lanes whole ones) or its tests reach it (the converter: 2^20 inputs); the
+    # meter's and the limiter's launches are longer than any call of the tests, the FIR matrix does not cut its calls
+    probe = capi.DelayMatrix(ctx, 1, 1, [(0, 0, 0, [1.0])], 1)
+    dly_launch = probe.info()["launch_in"]
+    probe.close()
+    lp = capi.iir_design("lowpass", 48000, 1000.0)
+    probe = capi.IirBank(ctx, 1, 1, [(0, 0, 1.0, [lp])], max_samples=1)
+    info = probe.info()
+    probe.close()
+    iir_launch = (info["scan_groups"] * info["scan_lanes"] + 1) * info["chunk"]
+    src_launch, src_taps = 1 << 20, capi.src_design(2, 3, 8)
+    longer = {
+        "delaymix": (dly_launch, lambda n: capi.DelayMatrix(ctx, 1, 1, [(0, 0, 5, [0.75, -0.25])], max_samples=n)),
+        "iir": (iir_launch, lambda n: capi.IirBank(ctx, 1, 1, [(0, 0, 0.5, [lp])], max_samples=n)),
+        "src": (src_launch, lambda n: capi.SampleRateConverter(ctx, 1, 2, 3, 8, src_taps, max_samples=n)),
+    }
+    for name, (launch, make) in longer.items():
+        x = scenes.audio(1, launch + 1, seed=52)
+        for device in (True, False):
+            st = make(launch + 1)
+            out = stage_call(name, st, x, device, ctx)
+            st.close()
+            print(f"{'bus_%s_launch_plus_1_%s' % (name, 'device' if device else 'host'):42s} launch {launch}\n    {sha(out)}")
+
+
+def run_bus_renderer(M, tail_cut):
+    """M = 16: every form of call and the pipeline.  The tail cut is the split-operand gain kernels', which take 32 objects or more:
+    the call of two spans goes through a second renderer of 32"""
+    import torch
+    N, B, T, TAIL = 5, 64, 4096, 2112  # (T: a host call of 16 MB of input rows; TAIL: 264 tiles of 512)
+    if tail_cut:
+        T = TAIL
+    rng = np.random.default_rng(13)
+    dec = rng.uniform(-0.1, 0.1, (N, 512)).astype(np.float32)
+    fir = rng.uniform(-0.1, 0.1, (2, N, B + 7)).astype(np.float32)
+    ctx = capi.Context(0)
+    ctx.set_option("H2_TILE", 512)
+    r = capi.Renderer(ctx, M, N, B, dec, 255, max_blocks=T)
+    for i, (t, d, f) in enumerate(scenes.dense_curves(M, N, 512, 2 * T * B // 512)):
+        r.set_object_points(i, t, d, f)
+    r.commit()
+    cap = 2 * T * B
+    meter = capi.Loudness(ctx, N, 48000, max_steps=cap // 4800 + 1, true_peak=True)
+    matrix = capi.FirMatrix(ctx, fir, B, max_blocks=T)
+    lim = capi.Limiter(ctx, N, 0.25, max_samples=T * B)
+    sink_m = torch.zeros((2, cap), dtype=torch.float32, device="cuda")
+    sink_l = torch.zeros((N, cap), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+    r.attach_loudness(meter)
+    r.attach_fir_matrix(matrix, sink_m.data_ptr(), cap, cap)
+    r.attach_limiter(lim, sink_l.data_ptr(), cap, cap)
+
+    def report(name, out, seen):
+        """the call's rows, what the taps wrote for it, and where they stand"""
+        ctx.synchronize()
+        a, b = r.fir_matrix_position(), r.limiter_position()
+        print(f"{name:42s} matrix at {a} limiter at {b} meter steps {meter.num_steps()} chunks {r.last_host_chunks()} "
+              f"tail {r.last_tail_blocks()} kernel {r.last_plan()['kernel']}\n    {sha(out)} {sha(sink_m[:, seen[0]:a].cpu().numpy())} {sha(sink_l[:, seen[1]:b].cpu().numpy())} "
+              f"{sha(np.concatenate(meter.peaks()))}")
+        seen[0], seen[1] = a, b
+
+    seen = [0, 0]
+    x = scenes.audio(M, T * B, seed=53)
+    n = 8 * B  # (the short calls end on the grid of the gain kernel's tiles)
+    if not tail_cut:
+        report("bus_render_process", r.process(x[:, :n]), seen)
+        xi = torch.from_numpy(np.ascontiguousarray(x[:, :n])).cuda()
+        o = torch.zeros((N, n), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+        r.process_device(8, xi.data_ptr(), n, o.data_ptr(), n)
+        ctx.synchronize()
+        report("bus_render_process_device", o.cpu().numpy(), seen)
+        frames = rng.integers(-20000, 20000, (n, M)).astype(np.int16)
+        report("bus_render_process_frames", r.process_frames(frames, "s16"), seen)
+        ctx.set_option("HOST_CHUNK_MB", 4)  # 16 MB of input rows: a pipeline of four chunks
+        report("bus_render_host_pipeline", r.process(x), seen)
+        assert r.last_host_chunks() >= 3
+    else:
+        ctx.set_option("HOST_CHUNK_MB", 0)  # 264 tiles of 512 in one piece: a whole round and a few tiles behind it
+        xi = torch.from_numpy(x).cuda()
+        o = torch.zeros((N, TAIL * B), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+        r.process_device(TAIL, xi.data_ptr(), T * B, o.data_ptr(), TAIL * B)
+        ctx.synchronize()
+        report("bus_render_32_objects_tail_cut", o.cpu().numpy(), seen)
+        assert r.last_tail_blocks() > 0
+    r.attach_fir_matrix(None)
+    report(f"bus_render_{M}_objects_matrix_detached", r.process(x[:, :n]), seen)
+    print(f"{'bus_render_%d_objects_meter' % M:42s}\n    {sha(meter.steps())}")
+    for st in (meter, matrix, lim):
+        st.close()
+    r.close()
+    ctx.close()
+
+
+WIDE = 49152  # (samples per row behind the refused calls' pointers: more than any of them names)
+
+
+def refusal(what, rc):
+    msg = capi.load().earhip_last_error().decode() if rc else ""
+    print(f"    {what:34s} status {rc} {msg!r}")
+
+
+def run_bus_refusals(ctx):
+    """the calls the shared checks refuse, through the library's own symbols (the wrapper cannot pass a NULL handle or row)"""
+    import ctypes as C
+    import torch
+    lib = capi.load()
+    sz, vp = C.c_size_t, C.c_void_p
+    for name, (make, rows, tile) in bus_stages(ctx).items():
+        unit = 64 if name == "firmix" else 1
+        n = 2 * unit  # (a call of two units)
+        rows_out = {"firmix": 2, "iir": 2, "delaymix": 2, "loudness": 0}.get(name, rows)
+        x = scenes.audio(rows, WIDE, seed=54)
+        xi = torch.from_numpy(x).cuda()
+        o = torch.zeros((max(rows_out, 1), WIDE), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+        host_out = np.zeros((max(rows_out, 1), WIDE), np.float32)
+        stride = x.shape[1]
+        dev_fn, host_fn = getattr(lib, f"earhip_{name}_process_device"), getattr(lib, f"earhip_{name}_process")
+        got = sz(0)
+        tail = {"limiter": (None,), "src": (sz(stride), C.byref(got))}.get(name, ())
+
+        def dev(h, units, i, istride, out, ostride, tail=tail):
+            if name == "loudness":
+                return dev_fn(h, sz(units), vp(i), sz(istride))
+            return dev_fn(h, sz(units), vp(i), sz(istride), vp(out), sz(ostride), *tail)
+
+        def host(h, units, ins, outs, tail=tail):
+            if name == "loudness":
+                return host_fn(h, sz(units), ins)
+            return host_fn(h, sz(units), ins, outs, *tail)
+
+        st = make()
+        over = {"loudness": 10 * 4800, "firmix": 4}.get(name, 4097)
+        read_row = 0
+        print(f"bus_refusals_{name}")
+        twin, at = make(), [0]  # (the twin takes the valid calls alone)
+
+        def refuse(what, rc, st=st, twin=twin, at=at, name=name, x=x):
+            """the refusal, and behind it a valid call in the refused call's form: its digest, and whether a stage that was never
+            refused anything gives the same"""
+            refusal(what, rc)
+            device = what.startswith("device")
+            seg = np.ascontiguousarray(x[:, at[0]:at[0] + (64 if name == "firmix" else 96)])
+            at[0] += seg.shape[1]
+            got, want = stage_call(name, st, seg, device, ctx), stage_call(name, twin, seg, device, ctx)
+            print(f"        the next call ({'device' if device else 'host'}): untouched {sha(got) == sha(want)} {sha(got)[:16]}")
+
+        refuse("device: NULL handle", dev(None, n // unit, xi.data_ptr(), stride, o.data_ptr(), stride))
+        refuse("device: over room", dev(st.h, over, xi.data_ptr(), stride, o.data_ptr(), stride))
+        refuse("device: NULL in", dev(st.h, n // unit, None, stride, o.data_ptr(), stride))
+        if rows_out:
+            refuse("device: NULL out", dev(st.h, n // unit, xi.data_ptr(), stride, None, stride))
+        refuse("device: short in stride", dev(st.h, n // unit, xi.data_ptr(), n - 1, o.data_ptr(), stride))
+        if rows_out:
+            refuse("device: short out stride", dev(st.h, n // unit, xi.data_ptr(), stride, o.data_ptr(), 0))
+        refuse("host: NULL handle", host(None, n // unit, capi._chan_ptrs(x), capi._chan_ptrs(host_out)))
+        refuse("host: over room", host(st.h, over, capi._chan_ptrs(x), capi._chan_ptrs(host_out)))
+        refuse("host: NULL in", host(st.h, n // unit, None, capi._chan_ptrs(host_out)))
+        if rows_out:
+            refuse("host: NULL out", host(st.h, n // unit, capi._chan_ptrs(x), None))
+        ins = capi._chan_ptrs(x)
+        ins[read_row] = None
+        refuse("host: NULL row that is read", host(st.h, n // unit, ins, capi._chan_ptrs(host_out)))
+        if rows_out:
+            outs = capi._chan_ptrs(host_out)
+            outs[rows_out - 1] = None
+            refuse("host: NULL row that is written", host(st.h, n // unit, capi._chan_ptrs(x), outs))
+        if name == "src":
+            refuse("device: short out_capacity", dev(st.h, n, xi.data_ptr(), stride, o.data_ptr(), stride, tail=(sz(1), C.byref(got))))
+            refuse("host: short out_capacity", host(st.h, n, capi._chan_ptrs(x), capi._chan_ptrs(host_out), tail=(sz(1), C.byref(got))))
+        refuse("reset: NULL handle", getattr(lib, f"earhip_{name}_reset")(None))
+        refuse("destroy: NULL handle", getattr(lib, f"earhip_{name}_destroy")(None))
+        ctx.synchronize()
+        assert not o.any() and not host_out.any(), name
+        st.close()
+        twin.close()
+    # the renderer's taps
+    M, N, B, T = 16, 5, 64, 4
+    dec = np.random.default_rng(14).uniform(-0.1, 0.1, (N, 512)).astype(np.float32)
+    fir = np.random.default_rng(15).uniform(-0.1, 0.1, (2, N, B)).astype(np.float32)
+    r = capi.Renderer(ctx, M, N, B, dec, 255, max_blocks=T)
+    for i, (t, d, f) in enumerate(scenes.dense_curves(M, N, B, 2 * T)):
+        r.set_object_points(i, t, d, f)
+    other = capi.Context(0)
+    sink = torch.zeros((N, 2 * T * B), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()  # (torch's fill, on its own stream, is done before the context's stream writes there)
+    cap = 2 * T * B
+    makers = {
+        "loudness": lambda c, rows, b: capi.Loudness(c, rows, 48000, max_steps=4),
+        "firmix": lambda c, rows, b: capi.FirMatrix(c, fir[:, :rows] if rows <= N else np.concatenate([fir, fir[:, :1]], axis=1), b, max_blocks=T),
+        "limiter": lambda c, rows, b: capi.Limiter(c, rows, 0.25, max_samples=T * B),
+    }
+
+    def attach(name, st, sink_ptr, stride, capacity):
+        if name == "loudness":
+            return lib.earhip_render_attach_loudness(r.h, st.h)
+        return getattr(lib, f"earhip_render_attach_{name}")(r.h, st.h, vp(sink_ptr), sz(stride), sz(capacity))
+
+    x = scenes.audio(M, 2 * T * B, seed=55)
+    print("bus_refusals_attach")
+    for name, make in makers.items():
+        for what, c, rows, b in (("another context", other, N, B), ("other rows", ctx, N + 1, B), ("another block size", ctx, N, 2 * B)):
+            if what == "another block size" and name != "firmix":
+                continue
+            st = make(c, rows, b)
+            refusal(f"{name}: {what}", attach(name, st, sink.data_ptr(), cap, cap))
+            st.close()
+        if name == "loudness":
+            continue
+        st = make(ctx, N, B)
+        refusal(f"{name}: NULL sink", attach(name, st, None, cap, cap))
+        refusal(f"{name}: stride < capacity", attach(name, st, sink.data_ptr(), cap - 1, cap))
+        refusal(f"{name}: attached", attach(name, st, sink.data_ptr(), cap, T * B + B))
+        first = r.process(x[:, :T * B])
+        unwritten = np.zeros((N, T * B), np.float32)
+        rc = lib.earhip_render_process(r.h, sz(T), capi._chan_ptrs(x, T * B), capi._chan_ptrs(unwritten))
+        refusal(f"{name}: past the sink's capacity", rc)
+        pos = sz(0)
+        getattr(lib, f"earhip_render_{name}_position")(r.h, C.byref(pos))
+        getattr(r, {"firmix": "attach_fir_matrix", "limiter": "attach_limiter"}[name])(None)
+        second = r.process(np.ascontiguousarray(x[:, T * B:]))  # (the refused call rendered nothing: this is the stream's second call)
+        print(f"    {name}: position {pos.value}, the calls around the refusal\n    {sha(first)} {sha(second)}")
+        r.reset(0)
+        st.close()
+    refusal("position: NULL", lib.earhip_render_firmix_position(r.h, None))
+    r.close()
+    other.close()
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["k2"]:
+    if sys.argv[1:] == ["bus"]:
+        import torch  # noqa: F401  (before the library touches the device: one HIP runtime per process, torch's)
+        ctx = capi.Context(0)
+        run_bus_stages(ctx)
+        run_bus_refusals(ctx)
+        ctx.close()
+        run_bus_renderer(16, False)
+        run_bus_renderer(32, True)
+    elif sys.argv[1:] == ["k2"]:
         for name, block, opts, kw in K2_CASES:
             run_k2(name, block, opts, **kw)
         run_transforms()
