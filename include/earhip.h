@@ -1662,6 +1662,90 @@ int earhip_delaymix_fractional(double delay, int n_taps, double beta, int *whole
 int earhip_delaymix_align(int n, const double *distance_m, double sample_rate, double speed_of_sound, double *delay_samples,
                           double *gain);
 
+/* ------------------------------------------------------------------------
+ * (T) The allocentric (Cartesian) point-source panner for Objects — what ITU-R BS.2127-0 section 7.3.10 sends an
+ * audioBlockFormat with cartesian == 1 to.  It stands the loudspeakers on a cube and pans along z, then y, then x.  The other
+ * way to render such a block, earhip_conversion_to_polar[_device] (group K) and then the polar panner (group I), gives
+ * different gains, and an object at the centre of the room, (0, 0, 0), has no polar direction at all.  libear carries only a
+ * stub (AllocentricPanner::handle returns boost::none), and ear::GainCalculatorObjects and ear::hip::ObjectsGainCalculator keep
+ * refusing Cartesian blocks.  THIS COMMENT IS THE SPECIFICATION.  It was written after BS.2127-0 7.3.10 WITHOUT A REFERENCE
+ * IMPLEMENTATION TO COMPARE AGAINST; the loudspeaker table can be replaced by the caller (earhip_allo_create_positions), so a
+ * disagreement about a table entry does not block a user.
+ *
+ * THE HANDLE is pure host data: no context, no device.  layout is a BS.2051 name or a layout defined through group H, looked up
+ * once, at creation; an unknown name is EARHIP_UNKNOWN_LAYOUT.  earhip_allo_create takes the built-in table below and is
+ * EARHIP_NOT_IMPLEMENTED for a defined layout, which has no table.  earhip_allo_create_positions takes one (x, y, z) per channel
+ * of the full layout (at most 32, the registry's limit); LFE entries are ignored; a non-finite coordinate of a channel that is
+ * not an LFE, or n_channels other than the layout's channel count, is EARHIP_INVALID_ARGUMENT.
+ *   SNAPPING, once, at creation, per axis: the coordinates of the loudspeakers that are not LFE are sorted ascending and
+ *   walked; a value within 1e-6 of the FIRST value of the current group takes that first value, any other value starts a
+ *   group.  After this "the same plane, row or column" is exact equality.  Two loudspeakers that end up on the same (x, y, z)
+ *   are EARHIP_INVALID_ARGUMENT.
+ * earhip_allo_positions returns the snapped positions, xyz [n_channels][3], the rows of LFE channels NaN.
+ * earhip_allo_excluded_channels sets bit c of *mask when loudspeaker c (not an LFE) lies in at least one zone, by the Cartesian
+ * rule of group I against the HANDLE'S positions: min - 1e-6 < c < max + 1e-6 for each coordinate.  Only Cartesian zones
+ * count: a polar zone is EARHIP_INVALID_ARGUMENT (earhip_objects_excluded_channels takes polar zones, on nominal positions).
+ *
+ * THE BUILT-IN TABLE.  ADM axes: x right, y front, z up; s = sqrt(2) - 1; a +- row gives the + name (left) first.
+ *     M+000 (0, 1, 0)        M+-030 (-+1, 1, 0), except in 9+10+3: (-+s, 1, 0)          M+-SC (-+s, 1, 0)
+ *     M+-060 (-+1, s, 0)     M+-090 (-+1, 0, 0)     M+-110 (-+1, -1, 0)     M+-135 (-+1, -1, 0)     M+180 (0, -1, 0)
+ *     U+000 (0, 1, 1)        U+-030 (-+1, 1, 1)     U+-045 (-+1, 1, 1)      U+-090 (-+1, 0, 1)      U+-110 (-+1, -1, 1)
+ *     U+-135 (-+1, -1, 1)    U+180 (0, -1, 1)       UH+180 (0, -1, 1)       T+000 (0, 0, 1)
+ *     B+000 (0, 1, -1)       B+-045 (-+1, 1, -1)
+ * Every channel of the ten layouts of group H that is not an LFE is in this list (csrc/allo_table.h, keyed by (layout, name)).
+ *
+ * THE GAINS, exactly (a caller can reproduce them).  Let A be the loudspeakers (channels that are not LFE) whose bit in the
+ * object's excluded mask is clear; if that leaves none, A is every loudspeaker.
+ *   bracket(V, v), for a non-empty set V of distinct doubles: lo = the largest element <= v, hi = the smallest element >= v.
+ *     No lo: {hi: 1}.  No hi: {lo: 1}.  lo == hi: {lo: 1}.  Otherwise, with f = (v - lo) / (hi - lo):
+ *     {lo: cos(f * (pi/2)), hi: sin(f * (pi/2))}, pi/2 the double nearest to it, the product f * (pi/2) taken first.
+ *     A position outside the loudspeakers' box is therefore clipped to it.
+ *   For an object at (x, y, z):
+ *     1. for each (Z, wz) in bracket({z_i : i in A}, z):  P = {i in A : z_i == Z};
+ *     2. for each (Y, wy) in bracket({y_i : i in P}, y):  R = {i in P : y_i == Y};
+ *     3. for each (X, wx) in bracket({x_i : i in R}, x):  the one i in R with x_i == X gets w_i = (wz * wy) * wx;
+ *     4. every other channel gets 0.
+ *   At most 8 channels are non-zero, sum w^2 = 1 up to rounding, and a position on a loudspeaker gives exactly 1 there and
+ *   exactly 0 elsewhere.
+ *   Outputs, in float64, left to right, ONE rounding to float32:
+ *     direct[i][c] = (float)(w_c * gain * sqrt(1 - diffuse)),   diffuse_out[i][c] = (float)(w_c * gain * sqrt(diffuse)).
+ *   The columns of LFE channels are +0.
+ * The host form and the kernel run these operations in this order (one shared core, csrc/allo.h, which also compiles without
+ * HIP); they differ only in the math library behind cos, sin and sqrt, so an output of one is the other's float or its
+ * neighbour.
+ *
+ * ENTRY POINTS.  gain, diffuse and excluded may be NULL (1, 0 and 0); diffuse_out may be NULL only when diffuse is NULL.
+ * direct and diffuse_out are [n][n_channels] float, row-major.  n == 0 is a no-op; n < 2^31.
+ * earhip_allo_calculate is a pure host function (a deliberate CPU computation on the calling thread, like the host forms of
+ * groups K and Q).  EARHIP_INVALID_ARGUMENT, the message naming the element's index: a non-finite x, y, z or gain; a diffuse
+ * that is NaN or outside [0, 1]; a mask bit at or beyond the channel count (bits of LFE channels are ignored).  The rows before
+ * that index are written, its row and those after it are not.
+ * earhip_allo_calculate_device takes SoA device arrays of n elements (device-reachable host memory included); it runs ONE kernel
+ * on the context's stream, allocates nothing, does not synchronise and never computes on the CPU.  It cannot refuse an element:
+ * an element the host form would refuse gets NaN in every column of both rows and status 1 — except that mask bits at or
+ * beyond the channel count are ignored — and every other element status 0 (status_dev: int[n], may be NULL).  The kernel gives
+ * a wave 64 positions, one per lane, the snapped table a by-value argument; a lane keeps its at most 8 weights in registers and
+ * the wave's 64 rows leave through one LDS tile as full-width contiguous stores, first direct, then diffuse_out.  No atomics:
+ * the same input gives the same bits.
+ *
+ * Out of scope: the Cartesian extent panner (width, height, depth), channelLock for Cartesian blocks, Cartesian
+ * objectDivergence, the screen stages on Cartesian positions (for all four a Cartesian block still takes group K and the polar
+ * producer), attaching anything to a renderer, tables for layouts outside BS.2051.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_allo earhip_allo;
+int earhip_allo_create(const char *layout, earhip_allo **out);
+int earhip_allo_create_positions(const char *layout, int n_channels, const double *x, const double *y, const double *z,
+                                 earhip_allo **out);
+int earhip_allo_destroy(earhip_allo *a);
+int earhip_allo_num_channels(const earhip_allo *a, int *n_channels);
+int earhip_allo_positions(const earhip_allo *a, double *xyz);
+int earhip_allo_excluded_channels(const earhip_allo *a, int n_zones, const earhip_exclusion_zone *zones, uint32_t *mask);
+int earhip_allo_calculate(const earhip_allo *a, size_t n, const double *x, const double *y, const double *z, const double *gain,
+                          const double *diffuse, const uint32_t *excluded, float *direct, float *diffuse_out);
+int earhip_allo_calculate_device(earhip_ctx *ctx, const earhip_allo *a, size_t n, const double *x_dev, const double *y_dev,
+                                 const double *z_dev, const double *gain_dev, const double *diffuse_dev,
+                                 const uint32_t *excluded_dev, float *direct_dev, float *diffuse_out_dev, int *status_dev);
+
 #ifdef __cplusplus
 }
 #endif

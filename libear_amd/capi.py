@@ -626,16 +626,21 @@ def objects_lock_priority(layout):
     return list(order)
 
 
-def objects_excluded_channels(layout, zones):
-    """(I) the bit mask (full layout) of the loudspeakers a list of zones excludes (pure host).  A zone is a dict of
-    keyword bounds: min_azimuth, max_azimuth, min_elevation, max_elevation, or min_x .. max_z (a Cartesian zone)"""
+def _zones(zones):
+    """a list of dicts of keyword bounds -> ExclusionZone[]; a zone with any of min_x .. max_z is a Cartesian one"""
     zs = (ExclusionZone * max(len(zones), 1))()
     for z, given in zip(zs, zones):
         z.cartesian = int(any(k.endswith(("_x", "_y", "_z")) for k in given))
         for k, v in given.items():
             setattr(z, k, float(v))
+    return zs
+
+
+def objects_excluded_channels(layout, zones):
+    """(I) the bit mask (full layout) of the loudspeakers a list of zones excludes (pure host).  A zone is a dict of
+    keyword bounds: min_azimuth, max_azimuth, min_elevation, max_elevation, or min_x .. max_z (a Cartesian zone)"""
     mask = C.c_uint32(0)
-    check(load().earhip_objects_excluded_channels(layout.encode(), len(zones), zs, C.byref(mask)))
+    check(load().earhip_objects_excluded_channels(layout.encode(), len(zones), _zones(zones), C.byref(mask)))
     return mask.value
 
 
@@ -1020,6 +1025,86 @@ def screen_apply_device(ctx, n, az, el, az_out, el_out, reproduction, reference=
                                             _dev_ptr(screen_ref, n, "uint8"), _dev_ptr(lock_horizontal, n, "uint8"),
                                             _dev_ptr(lock_vertical, n, "uint8"), _dev_ptr(az_out, n, "float64"),
                                             _dev_ptr(el_out, n, "float64"), _dev_ptr(status, n, "int32")))
+
+
+# (T) the allocentric (Cartesian) point-source panner for Objects
+
+class Allo:
+    """earhip_allo: the loudspeakers of a layout on the cube (pure host: no context, no device).  positions: float64
+    [n_channels][3] (x right, y front, z up), one row per channel of the full layout, LFE rows ignored; None: the built-in
+    table of the BS.2051 layouts."""
+
+    def __init__(self, layout, positions=None):
+        self.h = C.c_void_p()
+        f64 = C.POINTER(C.c_double)
+        if positions is None:
+            check(load().earhip_allo_create(layout.encode(), C.byref(self.h)))
+        else:
+            p = np.ascontiguousarray(positions, np.float64)
+            if p.ndim != 2 or p.shape[1] != 3:
+                raise InvalidArgument(INVALID_ARGUMENT, "positions must be [n_channels][3]")
+            x, y, z = (np.ascontiguousarray(p[:, k]) for k in range(3))
+            check(load().earhip_allo_create_positions(layout.encode(), len(p), _ptr(x, f64), _ptr(y, f64), _ptr(z, f64),
+                                                      C.byref(self.h)))
+        n = C.c_int(0)
+        check(load().earhip_allo_num_channels(self.h, C.byref(n)))
+        self.n_out = n.value
+
+    def positions(self):
+        """the snapped positions, float64 [n_channels][3]; the rows of LFE channels are NaN"""
+        xyz = np.empty((self.n_out, 3), np.float64)
+        check(load().earhip_allo_positions(self.h, _ptr(xyz, C.POINTER(C.c_double))))
+        return xyz
+
+    def excluded_channels(self, zones):
+        """the bit mask (full layout) of the loudspeakers a list of Cartesian zones excludes, at the handle's positions; a
+        zone is a dict of keyword bounds min_x .. max_z (a polar zone is an InvalidArgument)"""
+        mask = C.c_uint32(0)
+        check(load().earhip_allo_excluded_channels(self.h, len(zones), _zones(zones), C.byref(mask)))
+        return mask.value
+
+    def calculate(self, x, y, z, gain=None, diffuse=None, excluded=None):
+        """Cartesian positions -> (direct, diffuse) float32 [n][n_channels] on the calling thread (no device needed); arrays
+        [n] or scalars, None = absent (gain 1, diffuse 0, nothing excluded).  Raises on the first element the host form
+        refuses, the message naming it; the rows before it are written (the exception's `partial`: the two arrays)."""
+        f64 = C.POINTER(C.c_double)
+        x = np.ascontiguousarray(np.atleast_1d(x), np.float64)
+        n = x.size
+
+        def arr(v, dtype=np.float64):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (n,)))
+        y, z, gain, diffuse = arr(y), arr(z), arr(gain), arr(diffuse)
+        excluded = arr(excluded, np.uint32)
+        direct = np.full((n, self.n_out), np.nan, np.float32)
+        diff = np.full((n, self.n_out), np.nan, np.float32)
+        try:
+            check(load().earhip_allo_calculate(self.h, C.c_size_t(n), _ptr(x, f64), _ptr(y, f64), _ptr(z, f64),
+                                               None if gain is None else _ptr(gain, f64),
+                                               None if diffuse is None else _ptr(diffuse, f64),
+                                               None if excluded is None else _ptr(excluded, C.POINTER(C.c_uint32)),
+                                               _ptr(direct), _ptr(diff)))
+        except EarHipError as e:
+            e.partial = (direct, diff)
+            raise
+        return direct, diff
+
+    def close(self):
+        if self.h:
+            load().earhip_allo_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def allo_calculate_device(ctx, allo, n, x, y, z, gain, diffuse, excluded, direct, diffuse_out, status=None):
+    """the same on the device: float64 tensors (or device addresses) of n elements, gain / diffuse / excluded (an int32
+    tensor holding the mask bits) may be None, direct and diffuse_out float32 tensors [n][n_channels] (diffuse_out may be
+    None when diffuse is), status an int32 tensor [n] (may be None): 1 and rows of NaN for an element Allo.calculate
+    refuses.  Enqueues one kernel on the context's stream and does not synchronise."""
+    nc = allo.n_out
+    check(load().earhip_allo_calculate_device(ctx.h, allo.h, C.c_size_t(n), _dev_ptr(x, n, "float64"), _dev_ptr(y, n, "float64"),
+                                              _dev_ptr(z, n, "float64"), _dev_ptr(gain, n, "float64"),
+                                              _dev_ptr(diffuse, n, "float64"), _dev_ptr(excluded, n, "int32"),
+                                              _dev_ptr(direct, n * nc, "float32"), _dev_ptr(diffuse_out, n * nc, "float32"),
+                                              _dev_ptr(status, n, "int32")))
 
 
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4

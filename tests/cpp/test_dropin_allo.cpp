@@ -1,0 +1,294 @@
+// ear::hip::AllocentricGainCalculator (libear_amd/host/ear/hip_allo.hpp): Objects blocks with Cartesian positions, written
+// against the mirror headers alone.  The expected gains are the rows of the C ABI (earhip_allo_calculate, include/earhip.h
+// group T) and its known answers.  Compiles as C++14 with -Wall -Wextra -Werror.  `test_dropin_allo host` runs what needs no
+// device (everything but calculate_device); without an argument the batch form on the device runs too, on a GPU.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include <ear/bs2051.hpp>
+#include <ear/hip_allo.hpp>
+
+using namespace ear;
+using ear::hip::AllocentricGainCalculator;
+
+static int g_failed = 0, g_checks = 0;
+#define CHECK(cond)                                                 \
+  do {                                                              \
+    g_checks++;                                                     \
+    if (!(cond)) {                                                  \
+      g_failed++;                                                   \
+      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+    }                                                               \
+  } while (0)
+
+static ObjectsTypeMetadata at(double x, double y, double z, double gain = 1.0, double diffuse = 0.0) {
+  ObjectsTypeMetadata m;
+  m.position = CartesianPosition(x, y, z);
+  m.cartesian = true;
+  m.gain = gain;
+  m.diffuse = diffuse;
+  return m;
+}
+
+// the gains are exactly `want` on the channels it names and 0 everywhere else
+static bool gains_are(const Layout &layout, const std::vector<float> &g, const std::map<std::string, float> &want) {
+  bool ok = g.size() == layout.channels().size();
+  for (size_t i = 0; ok && i < g.size(); i++) {
+    const auto it = want.find(layout.channels()[i].name());
+    ok = g[i] == (it == want.end() ? 0.0f : it->second);
+  }
+  return ok;
+}
+
+// "" when the block is accepted, else the not_implemented message
+static std::string refusal(const AllocentricGainCalculator &calc, const ObjectsTypeMetadata &m, size_t n) {
+  std::vector<float> direct(n), diffuse(n);
+  try {
+    calc.calculate(m, direct, diffuse);
+  } catch (const ear::not_implemented &e) {
+    return e.what();
+  }
+  return "";
+}
+
+static bool names(const std::string &msg, const char *field) { return msg.find(field) != std::string::npos; }
+
+static std::vector<ObjectsTypeMetadata> some_blocks() {
+  std::vector<ObjectsTypeMetadata> v;
+  for (int i = 0; i < 131; i++) {
+    ObjectsTypeMetadata m = at(-1.3 + 0.02 * i, 1.3 - 0.019 * i, -1.0 + 0.017 * i, 0.25 + 0.01 * i, (i % 11) / 10.0);
+    if (i % 4 == 1) m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 1.0f, -1.0f, 1.0f, 1.0f, 1.0f, "ceiling"});
+    if (i % 8 == 2) m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f, "front left"});
+    v.push_back(m);
+  }
+  v.push_back(at(0.0, 0.0, 0.0));
+  v.push_back(at(-0.0, 1.0, -0.0));
+  return v;
+}
+
+int main(int argc, char **argv) {
+  const bool host_only = argc > 1 && std::strcmp(argv[1], "host") == 0;
+  const float r2 = (float)std::sqrt(0.5), r8 = (float)std::sqrt(0.125);
+  const Layout layout = getLayout("4+5+0");
+  const size_t n = layout.channels().size();
+  const AllocentricGainCalculator calc(layout);
+  std::vector<float> direct(n), diffuse(n);
+
+  // known answers of the specification
+  calc.calculate(at(0.0, 1.0, 0.0), direct, diffuse);
+  CHECK(gains_are(layout, direct, {{"M+000", 1.0f}}) && gains_are(layout, diffuse, {}));
+  calc.calculate(at(0.0, 0.0, 0.5), direct, diffuse);
+  CHECK(gains_are(layout, direct, {{"M+000", 0.5f}, {"M+110", r8}, {"M-110", r8}, {"U+030", r8}, {"U-030", r8}, {"U+110", r8}, {"U-110", r8}}));
+  calc.calculate(at(0.0, 0.0, 0.0), direct, diffuse);
+  CHECK(gains_are(layout, direct, {{"M+000", r2}, {"M+110", 0.5f}, {"M-110", 0.5f}}));
+  {
+    const Layout l370 = getLayout("3+7+0");
+    const AllocentricGainCalculator c370(l370);
+    std::vector<double> d(l370.channels().size()), f(l370.channels().size());
+    c370.calculate(at(0.5, -1.0, 1.0, 0.5, 1.0), d, f);
+    for (size_t c = 0; c < d.size(); c++) CHECK(d[c] == 0.0 && f[c] == (l370.channels()[c].name() == "UH+180" ? 0.5 : 0.0));
+  }
+  // a Cartesian zone over the front row: (0, 1, 0) moves to the back row
+  {
+    ObjectsTypeMetadata m = at(0.0, 1.0, 0.0);
+    m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 1.0f, 1.0f, 1.0f, 0.0f, 0.0f, "front"});
+    calc.calculate(m, direct, diffuse);
+    CHECK(gains_are(layout, direct, {{"M+110", r2}, {"M-110", r2}}));
+  }
+
+  // the calculator against the rows of the C ABI, bit for bit: single blocks and the batch
+  const std::vector<ObjectsTypeMetadata> blocks = some_blocks();
+  std::vector<std::vector<float>> bd, bf;
+  calc.calculate(blocks, bd, bf);
+  CHECK(bd.size() == blocks.size() && bf.size() == blocks.size());
+  {
+    earhip_allo *h = nullptr;
+    CHECK(earhip_allo_create("4+5+0", &h) == EARHIP_OK);
+    size_t differ = 0;
+    for (size_t i = 0; i < blocks.size(); i++) {
+      const ObjectsTypeMetadata &m = blocks[i];
+      std::vector<earhip_exclusion_zone> zones;
+      for (const ExclusionZone &z : m.zoneExclusion.zones) {
+        earhip_exclusion_zone c = earhip_exclusion_zone();
+        c.cartesian = 1, c.min_x = z.cartesian.minX, c.max_x = z.cartesian.maxX, c.min_y = z.cartesian.minY;
+        c.max_y = z.cartesian.maxY, c.min_z = z.cartesian.minZ, c.max_z = z.cartesian.maxZ;
+        zones.push_back(c);
+      }
+      uint32_t mask = 0;
+      CHECK(earhip_allo_excluded_channels(h, (int)zones.size(), zones.data(), &mask) == EARHIP_OK);
+      std::vector<float> d(n), f(n);
+      CHECK(earhip_allo_calculate(h, 1, &m.position.cartesian.X, &m.position.cartesian.Y, &m.position.cartesian.Z, &m.gain,
+                                  &m.diffuse, &mask, d.data(), f.data()) == EARHIP_OK);
+      calc.calculate(m, direct, diffuse);
+      if (std::memcmp(d.data(), direct.data(), 4 * n) != 0 || std::memcmp(f.data(), diffuse.data(), 4 * n) != 0 ||
+          std::memcmp(d.data(), bd[i].data(), 4 * n) != 0 || std::memcmp(f.data(), bf[i].data(), 4 * n) != 0)
+        differ++;
+    }
+    std::printf("calculator vs C ABI: %zu of %zu rows differ\n", differ, blocks.size());
+    CHECK(differ == 0);
+    earhip_allo_destroy(h);
+  }
+
+  // what the panner does not render is refused by field name, not dropped
+  {
+    CHECK(refusal(calc, at(0.1, 0.2, 0.3), n).empty());
+    ObjectsTypeMetadata m = at(0.1, 0.2, 0.3);
+    m.position = PolarPosition(10.0, 5.0, 1.0);
+    CHECK(names(refusal(calc, m, n), "position"));
+    m = at(0.1, 0.2, 0.3), m.cartesian = false;
+    CHECK(names(refusal(calc, m, n), "cartesian"));
+    m = at(0.1, 0.2, 0.3), m.width = 0.2;
+    CHECK(names(refusal(calc, m, n), "width"));
+    m = at(0.1, 0.2, 0.3), m.height = 0.2;
+    CHECK(names(refusal(calc, m, n), "height"));
+    m = at(0.1, 0.2, 0.3), m.depth = 0.2;
+    CHECK(names(refusal(calc, m, n), "depth"));
+    m = at(0.1, 0.2, 0.3), m.channelLock.flag = true;
+    CHECK(names(refusal(calc, m, n), "channelLock"));
+    m = at(0.1, 0.2, 0.3), m.objectDivergence = CartesianObjectDivergence(0.5, 0.25);
+    CHECK(names(refusal(calc, m, n), "divergence"));
+    m = at(0.1, 0.2, 0.3), m.objectDivergence = PolarObjectDivergence(0.5, 30.0);
+    CHECK(names(refusal(calc, m, n), "divergence"));
+    m = at(0.1, 0.2, 0.3), m.screenRef = true;
+    CHECK(names(refusal(calc, m, n), "screenRef"));
+    m = at(0.1, 0.2, 0.3), m.zoneExclusion.zones.push_back(PolarExclusionZone{-30.0f, 30.0f, -10.0f, 10.0f, 0.0f, 2.0f, "front"});
+    CHECK(names(refusal(calc, m, n), "zone"));
+    // a zero divergence is no divergence
+    m = at(0.1, 0.2, 0.3), m.objectDivergence = CartesianObjectDivergence(0.0, 0.25);
+    CHECK(refusal(calc, m, n).empty());
+    // the batch refuses what the single form refuses
+    std::vector<ObjectsTypeMetadata> three(3, at(0.1, 0.2, 0.3));
+    three[2].channelLock.flag = true;
+    bool threw = false;
+    try {
+      calc.calculate(three, bd, bf);
+    } catch (const ear::not_implemented &e) {
+      threw = names(e.what(), "channelLock");
+    }
+    CHECK(threw);
+  }
+  // output vector sizes, and bad values as invalid_argument
+  {
+    std::vector<float> small(n - 1), right(n);
+    bool threw = false;
+    try {
+      calc.calculate(at(0.0, 0.0, 0.0), small, right);
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+    threw = false;
+    try {
+      calc.calculate(at(0.0, 0.0, 0.0), right, small);
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+    threw = false;
+    try {
+      calc.calculate(at(0.0, NAN, 0.0), direct, diffuse);
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+    threw = false;
+    try {
+      calc.calculate(at(0.0, 0.0, 0.0, 1.0, 1.5), direct, diffuse);
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+  }
+  // a layout without its LFE channels: the same gains on the channels that remain
+  {
+    const Layout bare = layout.withoutLfe();
+    const AllocentricGainCalculator cb(bare);
+    std::vector<float> d(bare.channels().size()), f(bare.channels().size());
+    CHECK(d.size() == n - 1);
+    cb.calculate(at(0.3, -0.2, 0.4, 0.7, 0.25), d, f);
+    calc.calculate(at(0.3, -0.2, 0.4, 0.7, 0.25), direct, diffuse);
+    size_t k = 0;
+    for (size_t c = 0; c < n; c++) {
+      if (layout.channels()[c].isLfe()) continue;
+      CHECK(d[k] == direct[c] && f[k] == diffuse[c]);
+      k++;
+    }
+    CHECK(k == d.size());
+  }
+  // the loudspeakers where the caller says; a layout of the caller's own has no table
+  {
+    std::vector<CartesianPosition> half;
+    for (const char *name : {"M+030", "M-030", "M+000", "LFE1", "M+110", "M-110"}) {
+      const std::string s(name);
+      half.push_back(s == "LFE1" ? CartesianPosition(NAN, NAN, NAN)
+                                 : CartesianPosition(s == "M+000" ? 0.0 : (s[1] == '+' ? -0.5 : 0.5), s[3] == '1' ? -0.5 : 0.5, 0.0));
+    }
+    const Layout l050 = getLayout("0+5+0");
+    const AllocentricGainCalculator cp(l050, half);
+    std::vector<float> d(6), f(6);
+    cp.calculate(at(-0.25, 0.5, 0.0), d, f);
+    CHECK(gains_are(l050, d, {{"M+030", r2}, {"M+000", r2}}));
+    bool threw = false;
+    try {
+      AllocentricGainCalculator bad(l050, std::vector<CartesianPosition>(5));
+    } catch (const ear::invalid_argument &) {
+      threw = true;
+    }
+    CHECK(threw);
+    const Layout own("own", {Channel("L", PolarPosition(30.0, 0.0, 1.0)), Channel("R", PolarPosition(-30.0, 0.0, 1.0)),
+                             Channel("C", PolarPosition(0.0, 0.0, 1.0)), Channel("Ls", PolarPosition(110.0, 0.0, 1.0)),
+                             Channel("Rs", PolarPosition(-110.0, 0.0, 1.0))});
+    threw = false;
+    try {
+      AllocentricGainCalculator none(own);
+    } catch (const ear::not_implemented &) {
+      threw = true;
+    }
+    CHECK(threw);
+    const AllocentricGainCalculator co(own, {CartesianPosition(-1, 1, 0), CartesianPosition(1, 1, 0), CartesianPosition(0, 1, 0),
+                                             CartesianPosition(-1, -1, 0), CartesianPosition(1, -1, 0)});
+    std::vector<float> d5(5), f5(5);
+    co.calculate(at(0.0, 0.0, 0.0), d5, f5);
+    CHECK(d5[0] == 0.0f && d5[1] == 0.0f && d5[2] == r2 && d5[3] == 0.5f && d5[4] == 0.5f);
+  }
+  if (host_only) {
+    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
+    return g_failed ? 1 : 0;
+  }
+
+  // the batch form on the device (one launch) against the host form: the two run one core and differ only in the math
+  // library, so an output of one is the other's float or its neighbour
+  {
+    std::vector<std::vector<float>> dd, df;
+    calc.calculate(blocks, bd, bf);
+    calc.calculate_device(blocks, dd, df);
+    CHECK(dd.size() == blocks.size() && df.size() == blocks.size());
+    size_t differ = 0, far = 0;
+    for (size_t i = 0; i < blocks.size() && i < dd.size(); i++)
+      for (size_t c = 0; c < n; c++)
+        for (int k = 0; k < 2; k++) {
+          const float a = k ? bf[i][c] : bd[i][c], b = k ? df[i][c] : dd[i][c];
+          differ += a != b;
+          far += !(std::fabs(a - b) <= std::fabs(a) * 1.2e-7f + 1e-12f);
+        }
+    std::printf("device batch vs host: %zu of %zu values differ, %zu by more than one spacing\n", differ, 2 * n * blocks.size(), far);
+    CHECK(far == 0);
+    std::vector<ObjectsTypeMetadata> bad = blocks;
+    bad[77] = at(0.0, INFINITY, 0.0);
+    bool threw = false;
+    try {
+      calc.calculate_device(bad, dd, df);
+    } catch (const ear::invalid_argument &e) {
+      threw = names(e.what(), "metadata block 77");
+    }
+    CHECK(threw);
+    calc.calculate_device(std::vector<ObjectsTypeMetadata>(), dd, df);
+    CHECK(dd.empty() && df.empty());
+  }
+  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
+  return g_failed ? 1 : 0;
+}
