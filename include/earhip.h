@@ -1728,9 +1728,10 @@ int earhip_delaymix_align(int n, const double *distance_m, double sample_rate, d
  * the wave's 64 rows leave through one LDS tile as full-width contiguous stores, first direct, then diffuse_out.  No atomics:
  * the same input gives the same bits.
  *
- * Out of scope: the Cartesian extent panner (width, height, depth), channelLock for Cartesian blocks, Cartesian
- * objectDivergence, the screen stages on Cartesian positions (for all four a Cartesian block still takes group K and the polar
- * producer), attaching anything to a renderer, tables for layouts outside BS.2051.
+ * Out of scope: the screen stages on Cartesian positions (a block with screenRef still takes group K and the polar producer),
+ * attaching anything to a renderer, tables for layouts outside BS.2051.  The Cartesian extent panner (width, height, depth),
+ * channelLock for Cartesian blocks and Cartesian objectDivergence are group U, on this handle; the entry points of this group
+ * stay point-source.
  * ---------------------------------------------------------------------- */
 typedef struct earhip_allo earhip_allo;
 int earhip_allo_create(const char *layout, earhip_allo **out);
@@ -1745,6 +1746,76 @@ int earhip_allo_calculate(const earhip_allo *a, size_t n, const double *x, const
 int earhip_allo_calculate_device(earhip_ctx *ctx, const earhip_allo *a, size_t n, const double *x_dev, const double *y_dev,
                                  const double *z_dev, const double *gain_dev, const double *diffuse_dev,
                                  const uint32_t *excluded_dev, float *direct_dev, float *diffuse_out_dev, int *status_dev);
+
+/* ------------------------------------------------------------------------
+ * (U) Extent, channelLock and objectDivergence for the allocentric panner, on the handle of group T: with these every Cartesian
+ * Objects block without screenRef is rendered allocentrically, on the host or as one device launch over a resident batch.
+ * libear carries only a stub here too.  THIS COMMENT IS THE SPECIFICATION.  It was written after BS.2127-0 7.3.6, 7.3.7 and
+ * 7.3.11 WITHOUT A REFERENCE IMPLEMENTATION TO COMPARE AGAINST and without the Recommendation's text at hand; three sets of
+ * constants are THIS PROJECT'S READING: the lock weights 1/16, 4, 32; the 20-point grid; the fall-off 10^(-5.0625 (u^4 - 1)).
+ *
+ * A, bracket(), the snapped table and the point-source weights w(q) of a position q are group T's.  s_c is the handle's
+ * snapped position of loudspeaker c.  Per object, in this order:
+ *   1. CHANNEL LOCK (channel_lock[i] non-zero).  Candidates are every loudspeaker that is not an LFE, the excluded ones too.
+ *        d_c = sqrt((1/16) (x - s_c.x)^2 + 4 (y - s_c.y)^2 + 32 (z - s_c.z)^2).
+ *      With a maxDistance, only loudspeakers with d_c < maxDistance + 1e-10 stay; if none is left, the position is unchanged.
+ *      Among those with d_c < min d + 1e-10, the first in the lock priority order wins, and the position becomes s_c.
+ *      THE LOCK PRIORITY ORDER is the indices of the loudspeakers that are not LFE, ascending by (|z|, z, -y, |x|, x) of the
+ *      snapped positions; earhip_allo_lock_priority returns it, one int per loudspeaker that is not an LFE.
+ *   2. DIVERGENCE v with positionRange r.  v == 0: the one position, with weight 1.  Otherwise the positions (x, y, z),
+ *      (x - r, y, z) and (x + r, y, z) with the power weights (1 - v) / (1 + v), v / (1 + v) and v / (1 + v).  Nothing is
+ *      clipped here; bracket() and step 3 clip.
+ *   3. EXTENT of each position q, with size = (width, depth, height) on (x, y, z).
+ *      Per handle: axis k is FLAT when all loudspeakers that are not LFE share its snapped coordinate.  A flat axis has one
+ *      grid point, at that coordinate, with F = 1.  A non-flat axis has the grid c_j = (2 j - 19) / 19, j = 0 .. 19.
+ *        s_k = min(size_k, 1) on the non-flat axes; s_eff their mean, s_max their maximum (both 0 when all axes are flat);
+ *        p = 6 for s_eff <= 0.5, else 6 - 8 (s_eff - 0.5);      alpha = min(s_max / 0.2, 1).
+ *      If s_max == 0 then g(q) = w(q) exactly, and nothing below is evaluated.  Otherwise, on a non-flat axis, with
+ *        o_k = clamp(q_k, -1, 1),   h_k = max(size_k, 0.1),   u = max(|c - o_k|, h_k) / h_k:    F_k(c) = 10^(-5.0625 (u^4 - 1)),
+ *      a plateau of half-width h_k and value 1 (the floor 0.1 keeps at least one grid point on it) and a steep fall beyond.
+ *      Over every grid source s = (c_i, c_j, c_l), with w_c(s) group T's weights of s under the object's mask:
+ *        G_c = (sum_s (F_x(s.x) F_y(s.y) F_z(s.z) w_c(s))^p)^(1/p),      ghat_c = G_c / sqrt(sum_c G_c^2),
+ *        g_c(q) = sqrt((1 - alpha) w_c(q)^2 + alpha ghat_c^2).
+ *   4. COMBINATION.  g_c = sqrt(sum_k weight_k g_c(q_k)^2) over the positions of step 2, or g = g(q) without divergence.
+ *   5. OUTPUTS.  The columns of LFE channels are +0.  In float64, left to right, ONE rounding to float32:
+ *        direct[i][c] = (float)(g_c * gain * sqrt(1 - diffuse)),   diffuse_out[i][c] = (float)(g_c * gain * sqrt(diffuse));
+ *      a loudspeaker with g_c == 0 holds +0.
+ * A row with no lock, v == 0 and s_max == 0 has the bits of earhip_allo_calculate[_device] on the same element.
+ * The sum over the up to 8000 grid sources is never formed: group T's weight is a product of one function per coordinate
+ * (the weight of c's plane, of c's row within the plane, of c within the row), and so is the fall-off, hence
+ * G_c^p = Pz_c Py_c Px_c with Pk_c = sum_j (F_k(c_j) wk_c(c_j))^p: 60 terms per loudspeaker (csrc/allo_objects.h, the one core
+ * of both forms, which also compiles without HIP).  The result is that of the triple sum up to rounding, and the bar of both
+ * forms is one float32 spacing at max(|value|, 2^-20) against a float64 evaluation of the triple sum.
+ *
+ * ENTRY POINTS.  x, y, z and direct as in group T; every other input array may be NULL: width, height, depth 0, gain 1,
+ * diffuse 0, channel_lock 0 (no lock), lock_max_distance +inf (none), divergence 0, position_range 0 (libear's
+ * CartesianObjectDivergence default), excluded 0.  diffuse_out may be NULL only when diffuse is NULL.  n == 0 is a no-op;
+ * n < 2^31.
+ * earhip_allo_calculate_objects is a pure host function.  EARHIP_INVALID_ARGUMENT, the message naming the element's index: what
+ * earhip_allo_calculate refuses; a size that is NaN, negative or infinite; a divergence that is NaN or outside [0, 1]; a
+ * position_range that is NaN, negative or infinite; a lock_max_distance that is NaN or negative (each whether or not the lock
+ * flag or the divergence makes use of it).  The rows before that index are written, its row and those after it are not.
+ * earhip_allo_calculate_objects_device takes SoA device arrays of n elements (device-reachable host memory included); it runs
+ * ONE kernel on the context's stream, allocates nothing, does not synchronise and never computes on the CPU.  An element the
+ * host form would refuse gets NaN in every column of both rows and status 1 — except that mask bits at or beyond the channel
+ * count are ignored — and every other element status 0 (status_dev: int[n], may be NULL).  The kernel's lanes run over
+ * (object, loudspeaker): each lane finds its loudspeaker's neighbours under the object's mask in the by-value table and adds
+ * its 60 terms, the normalisation is a sum in channel order through LDS, and rows leave through an LDS tile as contiguous
+ * stores.  No atomics: the same input gives the same bits.
+ * ---------------------------------------------------------------------- */
+int earhip_allo_lock_priority(const earhip_allo *a, int *order);
+int earhip_allo_calculate_objects(const earhip_allo *a, size_t n, const double *x, const double *y, const double *z,
+                                  const double *width, const double *height, const double *depth, const double *gain,
+                                  const double *diffuse, const unsigned char *channel_lock, const double *lock_max_distance,
+                                  const double *divergence, const double *position_range, const uint32_t *excluded,
+                                  float *direct, float *diffuse_out);
+int earhip_allo_calculate_objects_device(earhip_ctx *ctx, const earhip_allo *a, size_t n, const double *x_dev,
+                                         const double *y_dev, const double *z_dev, const double *width_dev,
+                                         const double *height_dev, const double *depth_dev, const double *gain_dev,
+                                         const double *diffuse_dev, const unsigned char *channel_lock_dev,
+                                         const double *lock_max_distance_dev, const double *divergence_dev,
+                                         const double *position_range_dev, const uint32_t *excluded_dev, float *direct_dev,
+                                         float *diffuse_out_dev, int *status_dev);
 
 #ifdef __cplusplus
 }

@@ -1088,6 +1088,41 @@ class Allo:
             raise
         return direct, diff
 
+    def lock_priority(self):
+        """(U) the channel indices of the loudspeakers that are not LFE in the order a channelLock tie is resolved in"""
+        n_real = int(np.count_nonzero(~np.isnan(self.positions()[:, 0])))
+        order = np.zeros(n_real, np.int32)
+        check(load().earhip_allo_lock_priority(self.h, _ptr(order, C.POINTER(C.c_int))))
+        return [int(c) for c in order]
+
+    def calculate_objects(self, x, y, z, width=None, height=None, depth=None, gain=None, diffuse=None, channel_lock=None,
+                          lock_max_distance=None, divergence=None, position_range=None, excluded=None):
+        """(U) Cartesian positions with extent, channelLock and divergence -> (direct, diffuse) float32 [n][n_channels] on
+        the calling thread; arrays [n] or scalars, None = absent (sizes 0, gain 1, diffuse 0, no lock, no maxDistance,
+        divergence 0, positionRange 0, nothing excluded).  Raises on the first element the host form refuses, the message
+        naming it; the rows before it are written (the exception's `partial`: the two arrays)."""
+        f64 = C.POINTER(C.c_double)
+        x = np.ascontiguousarray(np.atleast_1d(x), np.float64)
+        n = x.size
+
+        def arr(v, dtype=np.float64, t=f64):
+            if v is None:
+                return None, None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (n,)))
+            return a, _ptr(a, t)
+        ins = [arr(v) for v in (x, y, z, width, height, depth, gain, diffuse)]
+        ins.append(arr(None if channel_lock is None else np.asarray(channel_lock) != 0, np.uint8, C.POINTER(C.c_ubyte)))
+        ins += [arr(v) for v in (lock_max_distance, divergence, position_range)]
+        ins.append(arr(excluded, np.uint32, C.POINTER(C.c_uint32)))
+        direct = np.full((n, self.n_out), np.nan, np.float32)
+        diff = np.full((n, self.n_out), np.nan, np.float32)
+        try:
+            check(load().earhip_allo_calculate_objects(self.h, C.c_size_t(n), *(p for _, p in ins), _ptr(direct), _ptr(diff)))
+        except EarHipError as e:
+            e.partial = (direct, diff)
+            raise
+        return direct, diff
+
     def close(self):
         if self.h:
             load().earhip_allo_destroy(self.h)
@@ -1105,6 +1140,21 @@ def allo_calculate_device(ctx, allo, n, x, y, z, gain, diffuse, excluded, direct
                                               _dev_ptr(diffuse, n, "float64"), _dev_ptr(excluded, n, "int32"),
                                               _dev_ptr(direct, n * nc, "float32"), _dev_ptr(diffuse_out, n * nc, "float32"),
                                               _dev_ptr(status, n, "int32")))
+
+
+def allo_calculate_objects_device(ctx, allo, n, x, y, z, width, height, depth, gain, diffuse, channel_lock, lock_max_distance,
+                                  divergence, position_range, excluded, direct, diffuse_out, status=None):
+    """(U) Allo.calculate_objects on the device: float64 tensors (or device addresses) of n elements, channel_lock a uint8
+    tensor, excluded an int32 tensor holding the mask bits; every input but x, y, z may be None; direct and diffuse_out
+    float32 tensors [n][n_channels] (diffuse_out may be None when diffuse is), status an int32 tensor [n] (may be None): 1
+    and rows of NaN for an element Allo.calculate_objects refuses.  Enqueues one kernel on the context's stream and does not
+    synchronise."""
+    nc = allo.n_out
+    f64 = [_dev_ptr(v, n, "float64") for v in (x, y, z, width, height, depth, gain, diffuse)]
+    check(load().earhip_allo_calculate_objects_device(
+        ctx.h, allo.h, C.c_size_t(n), *f64, _dev_ptr(channel_lock, n, "uint8"), _dev_ptr(lock_max_distance, n, "float64"),
+        _dev_ptr(divergence, n, "float64"), _dev_ptr(position_range, n, "float64"), _dev_ptr(excluded, n, "int32"),
+        _dev_ptr(direct, n * nc, "float32"), _dev_ptr(diffuse_out, n * nc, "float32"), _dev_ptr(status, n, "int32")))
 
 
 PCM_S16, PCM_S24, PCM_S32, PCM_F32 = 1, 2, 3, 4

@@ -2,7 +2,8 @@
 // AllocentricPanner::handle returns boost::none).  The handle is host data: the layout's loudspeakers on the cube, snapped
 // per axis (allo_table.h or the caller's positions).  The arithmetic is allo.h, shared by the host form (computed on the
 // calling thread, like the host forms of groups K and Q) and the device form (allo_kernels.h: a wave per 64 positions,
-// enqueued on the context's stream).
+// enqueued on the context's stream).  Group U, on the same handle: channelLock, Cartesian objectDivergence and extent
+// (allo_objects.h, the core of both forms; allo_objects_kernels.h, lanes over (object, loudspeaker)).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -15,6 +16,8 @@
 #include "common.h"
 #include "allo.h"
 #include "allo_kernels.h"
+#include "allo_objects.h"
+#include "allo_objects_kernels.h"
 #include "allo_table.h"
 #include "layout_registry.h"
 
@@ -194,6 +197,78 @@ int earhip_allo_calculate_device(earhip_ctx *ctx, const earhip_allo *a, size_t n
     hipLaunchKernelGGL(k_allo_calculate, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * kTileWaves),
                        tile_lds_bytes(a->t.n), ctx->stream, a->t, n, x_dev, y_dev, z_dev, gain_dev, diffuse_dev, excluded_dev,
                        direct_dev, diffuse_out_dev, status_dev);
+    EARHIP_HIP(hipGetLastError());
+  });
+}
+
+int earhip_allo_lock_priority(const earhip_allo *a, int *order) {
+  return guarded([&] {
+    require(a != nullptr && order != nullptr, "NULL argument");
+    const Extras e = make_extras(a->t);
+    for (int k = 0; k < e.n_order; k++) order[k] = e.order[k];
+  });
+}
+
+int earhip_allo_calculate_objects(const earhip_allo *a, size_t n, const double *x, const double *y, const double *z,
+                                  const double *width, const double *height, const double *depth, const double *gain,
+                                  const double *diffuse, const unsigned char *channel_lock, const double *lock_max_distance,
+                                  const double *divergence, const double *position_range, const uint32_t *excluded,
+                                  float *direct, float *diffuse_out) {
+  return guarded([&] {
+    check_arrays(a, n, x, y, z, diffuse, direct, diffuse_out);
+    const Table &t = a->t;
+    const Extras e = make_extras(t);
+    const uint32_t beyond = t.n >= 32 ? 0u : ~0u << t.n;
+    for (size_t i = 0; i < n; i++) {
+      const double sw = width ? width[i] : 0.0, sh = height ? height[i] : 0.0, sd = depth ? depth[i] : 0.0;
+      const double g = gain ? gain[i] : 1.0, d = diffuse ? diffuse[i] : 0.0;
+      const bool lock = channel_lock ? channel_lock[i] != 0 : false;
+      const double maxd = lock_max_distance ? lock_max_distance[i] : HUGE_VAL;
+      const double v = divergence ? divergence[i] : 0.0, r = position_range ? position_range[i] : 0.0;
+      const uint32_t mask = excluded ? excluded[i] : 0u;
+      if (!position_valid(x[i], y[i], z[i], g, d) || !objects_valid(sw, sh, sd, maxd, v, r) || (mask & beyond)) {
+        char msg[640];
+        std::snprintf(msg, sizeof msg, "element %zu: x %g, y %g, z %g, width %g, height %g, depth %g, gain %g, diffuse %g, "
+                      "maxDistance %g, divergence %g, positionRange %g, excluded 0x%x: the position and the gain must be finite, "
+                      "the sizes and the positionRange finite and not negative, the maxDistance not negative, the diffuse and "
+                      "the divergence within [0, 1] and the mask within the layout's %d channels",
+                      i, x[i], y[i], z[i], sw, sh, sd, g, d, maxd, v, r, (unsigned)mask, t.n);
+        fail_invalid(msg);
+      }
+      Object o;
+      prepare_object(t, e, x[i], y[i], z[i], sw, sh, sd, lock, maxd, v, r, mask, o);
+      double w[kMaxChannels][3], G[kMaxChannels][3], sum[3] = {0.0, 0.0, 0.0}, norm[3];
+      for (int c = 0; c < t.n; c++) {
+        channel_terms(t, e, o, c, w[c], G[c]);
+        for (int k = 0; k < 3; k++) sum[k] += G[c][k] * G[c][k];
+      }
+      for (int k = 0; k < 3; k++) norm[k] = sqrt(sum[k]);
+      for (int c = 0; c < t.n; c++) {
+        const double gc = combine(o, w[c], G[c], norm);
+        direct[i * (size_t)t.n + c] = row_value(gc, g, direct_factor(d));
+        if (diffuse_out) diffuse_out[i * (size_t)t.n + c] = row_value(gc, g, diffuse_factor(d));
+      }
+    }
+  });
+}
+
+int earhip_allo_calculate_objects_device(earhip_ctx *ctx, const earhip_allo *a, size_t n, const double *x_dev,
+                                         const double *y_dev, const double *z_dev, const double *width_dev,
+                                         const double *height_dev, const double *depth_dev, const double *gain_dev,
+                                         const double *diffuse_dev, const unsigned char *channel_lock_dev,
+                                         const double *lock_max_distance_dev, const double *divergence_dev,
+                                         const double *position_range_dev, const uint32_t *excluded_dev, float *direct_dev,
+                                         float *diffuse_out_dev, int *status_dev) {
+  return guarded([&] {
+    require(ctx != nullptr, "context must not be NULL");
+    check_arrays(a, n, x_dev, y_dev, z_dev, diffuse_dev, direct_dev, diffuse_out_dev);
+    if (n == 0) return;
+    ctx->use();
+    const size_t per_wg = (size_t)objects_per_workgroup(a->t.n);
+    hipLaunchKernelGGL(k_allo_objects, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(kObjectsThreads), 0, ctx->stream, a->t,
+                       make_extras(a->t), objects_log2_width(a->t.n), n, x_dev, y_dev, z_dev, width_dev, height_dev, depth_dev,
+                       gain_dev, diffuse_dev, channel_lock_dev, lock_max_distance_dev, divergence_dev, position_range_dev,
+                       excluded_dev, direct_dev, diffuse_out_dev, status_dev);
     EARHIP_HIP(hipGetLastError());
   });
 }

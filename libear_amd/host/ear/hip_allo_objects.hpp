@@ -1,11 +1,9 @@
-// ear/hip_allo.hpp — a gain calculator for Objects blocks with Cartesian positions (cartesian == 1): the C++ face of group T
-// of the C ABI (include/earhip.h, where the allocentric panner's gains are specified, after ITU-R BS.2127-0 7.3.10).  libear
-// carries only a stub of this panner, and ear::GainCalculatorObjects and ear::hip::ObjectsGainCalculator keep refusing
-// Cartesian blocks, so there is no libear class this one mirrors; it has the constructor and calculate overloads of
-// ObjectsGainCalculator (hip_objects.hpp) and follows the conventions of the mirror classes (exceptions for status codes).
-// It is pure host: only calculate_device, the batch form that runs one device launch, takes a Context.
-// This class is the point-source form; AllocentricObjectsGainCalculator (hip_allo_objects.hpp, group U) also takes extent,
-// channelLock and CartesianObjectDivergence.
+// ear/hip_allo_objects.hpp — the gain calculator for every Objects block with Cartesian positions (cartesian == 1) but
+// screenRef: the C++ face of group U of the C ABI (include/earhip.h, where the gains are specified, after ITU-R BS.2127-0
+// 7.3.6, 7.3.7, 7.3.10 and 7.3.11).  Beyond AllocentricGainCalculator (hip_allo.hpp), whose constructors and calculate /
+// calculate_device overloads it has, it takes width, height and depth, channelLock (flag and maxDistance) and
+// CartesianObjectDivergence.  libear carries only a stub of this panner, so there is no libear class this one mirrors.  It is
+// pure host: only calculate_device, the batch form that runs one device launch, takes a Context.
 #pragma once
 #include <cstdint>
 #include <limits>
@@ -16,11 +14,11 @@
 
 namespace ear {
   namespace hip {
-    class AllocentricGainCalculator {
+    class AllocentricObjectsGainCalculator {
      public:
       /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels; its loudspeakers stand where the
       /// built-in table of group T puts them.  A layout of the caller's own has no table: not_implemented.
-      explicit AllocentricGainCalculator(const Layout &layout) {
+      explicit AllocentricObjectsGainCalculator(const Layout &layout) {
         std::vector<double> az, el;
         keep_ = ear::detail::match_layout(layout, name_, az, el);
         n_full_ = az.size();
@@ -28,21 +26,19 @@ namespace ear {
       }
       /// any layout, with the loudspeakers where the caller says: one position per channel of `layout`, in its order (those
       /// of LFE channels are ignored)
-      AllocentricGainCalculator(const Layout &layout, const std::vector<CartesianPosition> &positions) {
+      AllocentricObjectsGainCalculator(const Layout &layout, const std::vector<CartesianPosition> &positions) {
         std::vector<double> az, el;
         keep_ = ear::detail::match_layout(layout, name_, az, el);
         n_full_ = az.size();
         if (positions.size() != keep_.size()) throw invalid_argument("one position per channel of the layout");
-        // (a BS.2051 layout given without its LFE channels: the native creator ignores those rows, and refuses the NaN of
-        // any other channel that is missing)
         const double none = std::numeric_limits<double>::quiet_NaN();
         std::vector<double> x(n_full_, none), y(n_full_, none), z(n_full_, none);
         for (size_t c = 0; c < keep_.size(); c++) x[keep_[c]] = positions[c].X, y[keep_[c]] = positions[c].Y, z[keep_[c]] = positions[c].Z;
         check(earhip_allo_create_positions(name_.c_str(), (int)n_full_, x.data(), y.data(), z.data(), &h_));
       }
-      ~AllocentricGainCalculator() { earhip_allo_destroy(h_); }
-      AllocentricGainCalculator(const AllocentricGainCalculator &) = delete;
-      AllocentricGainCalculator &operator=(const AllocentricGainCalculator &) = delete;
+      ~AllocentricObjectsGainCalculator() { earhip_allo_destroy(h_); }
+      AllocentricObjectsGainCalculator(const AllocentricObjectsGainCalculator &) = delete;
+      AllocentricObjectsGainCalculator &operator=(const AllocentricObjectsGainCalculator &) = delete;
 
       /// one metadata block -> direct and diffuse gain vectors, which must have the layout's channel count
       template <typename T>
@@ -56,16 +52,17 @@ namespace ear {
         diffuseGains = f[0];
       }
       /// a batch of metadata blocks, on the calling thread.  Refused with not_implemented, the message naming the field: a
-      /// polar position or `cartesian == false`, width / height / depth, channelLock, a non-zero divergence, screenRef, a
-      /// polar exclusion zone (for all but the last a Cartesian block still takes ear::conversion and the polar calculators).
+      /// polar position or `cartesian == false`, a non-zero PolarObjectDivergence, screenRef (such a block still takes
+      /// ear::conversion and the polar calculators), a polar exclusion zone.
       template <typename T>
       void calculate(const std::vector<ObjectsTypeMetadata> &metadata, std::vector<std::vector<T>> &directGains,
                      std::vector<std::vector<T>> &diffuseGains) const {
         Batch b = gather(metadata);
         const size_t n = metadata.size();
         std::vector<float> d(n * n_full_), f(n * n_full_);
-        check(earhip_allo_calculate(h_, n, b.x.data(), b.y.data(), b.z.data(), b.gain.data(), b.diffuse.data(),
-                                    b.excluded.data(), d.data(), f.data()));
+        check(earhip_allo_calculate_objects(h_, n, b.v[0].data(), b.v[1].data(), b.v[2].data(), b.v[3].data(), b.v[4].data(),
+                                            b.v[5].data(), b.v[6].data(), b.v[7].data(), b.lock.data(), b.v[8].data(),
+                                            b.v[9].data(), b.v[10].data(), b.excluded.data(), d.data(), f.data()));
         scatter(n, d.data(), f.data(), directGains, diffuseGains);
       }
       /// the same batch in one device launch, through buffers in host memory the device reaches.  A block the host form
@@ -80,23 +77,27 @@ namespace ear {
           return;
         }
         void *mem = nullptr;
-        check(earhip_host_alloc(ctx.get(), n * (5 * sizeof(double) + sizeof(uint32_t) + sizeof(int) + 2 * n_full_ * sizeof(float)),
-                                &mem));
-        double *x = static_cast<double *>(mem), *y = x + n, *z = y + n, *gain = z + n, *diffuse = gain + n;
-        uint32_t *excluded = reinterpret_cast<uint32_t *>(diffuse + n);
+        check(earhip_host_alloc(ctx.get(), n * (kDoubles * sizeof(double) + sizeof(uint32_t) + sizeof(int) +
+                                                2 * n_full_ * sizeof(float) + 1), &mem));
+        double *v[kDoubles];
+        for (int k = 0; k < kDoubles; k++) {
+          v[k] = static_cast<double *>(mem) + k * n;
+          for (size_t i = 0; i < n; i++) v[k][i] = b.v[k][i];
+        }
+        uint32_t *excluded = reinterpret_cast<uint32_t *>(v[kDoubles - 1] + n);
         int *status = reinterpret_cast<int *>(excluded + n);
         float *d = reinterpret_cast<float *>(status + n), *f = d + n * n_full_;
-        for (size_t i = 0; i < n; i++) {
-          x[i] = b.x[i], y[i] = b.y[i], z[i] = b.z[i], gain[i] = b.gain[i], diffuse[i] = b.diffuse[i];
-          excluded[i] = b.excluded[i];
-        }
-        int st = earhip_allo_calculate_device(ctx.get(), h_, n, x, y, z, gain, diffuse, excluded, d, f, status);
+        unsigned char *lock = reinterpret_cast<unsigned char *>(f + n * n_full_);
+        for (size_t i = 0; i < n; i++) excluded[i] = b.excluded[i], lock[i] = b.lock[i];
+        int st = earhip_allo_calculate_objects_device(ctx.get(), h_, n, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], lock, v[8],
+                                                      v[9], v[10], excluded, d, f, status);
         if (st == EARHIP_OK) st = earhip_ctx_synchronize(ctx.get());
         std::string msg = st == EARHIP_OK ? std::string() : std::string(earhip_last_error());
         for (size_t i = 0; i < n && st == EARHIP_OK; i++)
           if (status[i] != 0) {
             st = EARHIP_INVALID_ARGUMENT;
-            msg = "metadata block " + std::to_string(i) + ": the position and the gain must be finite and the diffuse within [0, 1]";
+            msg = "metadata block " + std::to_string(i) + ": the position and the gain must be finite, the sizes, the "
+                  "positionRange and the maxDistance not negative, the diffuse and the divergence within [0, 1]";
           }
         if (st == EARHIP_OK) scatter(n, d, f, directGains, diffuseGains);
         earhip_host_release(ctx.get(), mem);
@@ -104,26 +105,33 @@ namespace ear {
       }
 
      private:
+      // the double arrays of the C ABI, in its order: x, y, z, width, height, depth, gain, diffuse, lock_max_distance,
+      // divergence, position_range
+      enum { kDoubles = 11 };
       struct Batch {
-        std::vector<double> x, y, z, gain, diffuse;
+        std::vector<double> v[kDoubles];
+        std::vector<unsigned char> lock;
         std::vector<uint32_t> excluded;
       };
       Batch gather(const std::vector<ObjectsTypeMetadata> &metadata) const {
         const size_t n = metadata.size();
         Batch b;
-        b.x.resize(n), b.y.resize(n), b.z.resize(n), b.gain.resize(n), b.diffuse.resize(n), b.excluded.assign(n, 0);
+        for (std::vector<double> &a : b.v) a.resize(n);
+        b.lock.assign(n, 0), b.excluded.assign(n, 0);
         for (size_t i = 0; i < n; i++) {
           const ObjectsTypeMetadata &m = metadata[i];
           if (!m.position.isCartesian) throw not_implemented("position: polar");
           if (!m.cartesian) throw not_implemented("cartesian == false");
-          if (m.width != 0.0) throw not_implemented("width");
-          if (m.height != 0.0) throw not_implemented("height");
-          if (m.depth != 0.0) throw not_implemented("depth");
-          if (m.channelLock.flag) throw not_implemented("channelLock");
-          if (m.objectDivergence.divergence != 0.0) throw not_implemented("divergence");
+          if (!m.objectDivergence.isCartesian && m.objectDivergence.divergence != 0.0)
+            throw not_implemented("objectDivergence: polar");
           if (m.screenRef) throw not_implemented("screenRef");
-          b.x[i] = m.position.cartesian.X, b.y[i] = m.position.cartesian.Y, b.z[i] = m.position.cartesian.Z;
-          b.gain[i] = m.gain, b.diffuse[i] = m.diffuse;
+          b.v[0][i] = m.position.cartesian.X, b.v[1][i] = m.position.cartesian.Y, b.v[2][i] = m.position.cartesian.Z;
+          b.v[3][i] = m.width, b.v[4][i] = m.height, b.v[5][i] = m.depth;
+          b.v[6][i] = m.gain, b.v[7][i] = m.diffuse;
+          b.lock[i] = m.channelLock.flag ? 1 : 0;
+          b.v[8][i] = m.channelLock.hasMaxDistance ? m.channelLock.maxDistance : std::numeric_limits<double>::infinity();
+          b.v[9][i] = m.objectDivergence.divergence;
+          b.v[10][i] = m.objectDivergence.isCartesian ? m.objectDivergence.range : 0.0;
           if (!m.zoneExclusion.zones.empty()) {
             std::vector<earhip_exclusion_zone> zones;
             for (const ExclusionZone &zn : m.zoneExclusion.zones) {

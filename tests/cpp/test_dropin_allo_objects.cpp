@@ -1,0 +1,285 @@
+// ear::hip::AllocentricObjectsGainCalculator (libear_amd/host/ear/hip_allo_objects.hpp): Cartesian Objects blocks with extent,
+// channelLock and divergence, written against the mirror headers alone.  The expected gains are the rows of the C ABI
+// (earhip_allo_calculate_objects, include/earhip.h group U).  Compiles as C++14 with -Wall -Wextra -Werror.
+// `test_dropin_allo_objects host` runs what needs no device (everything but calculate_device); without an argument the batch
+// form on the device runs too, on a GPU.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include <ear/bs2051.hpp>
+#include <ear/hip_allo.hpp>
+#include <ear/hip_allo_objects.hpp>
+
+using namespace ear;
+using ear::hip::AllocentricObjectsGainCalculator;
+
+static int g_failed = 0, g_checks = 0;
+#define CHECK(cond)                                                 \
+  do {                                                              \
+    g_checks++;                                                     \
+    if (!(cond)) {                                                  \
+      g_failed++;                                                   \
+      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+    }                                                               \
+  } while (0)
+
+static ObjectsTypeMetadata at(double x, double y, double z, double gain = 1.0, double diffuse = 0.0) {
+  ObjectsTypeMetadata m;
+  m.position = CartesianPosition(x, y, z);
+  m.cartesian = true;
+  m.gain = gain;
+  m.diffuse = diffuse;
+  return m;
+}
+
+// "" when the block is accepted, else the not_implemented message
+static std::string refusal(const AllocentricObjectsGainCalculator &calc, const ObjectsTypeMetadata &m, size_t n) {
+  std::vector<float> direct(n), diffuse(n);
+  try {
+    calc.calculate(m, direct, diffuse);
+  } catch (const ear::not_implemented &e) {
+    return e.what();
+  }
+  return "";
+}
+
+static bool names(const std::string &msg, const char *field) { return msg.find(field) != std::string::npos; }
+
+static std::vector<ObjectsTypeMetadata> some_blocks() {
+  std::vector<ObjectsTypeMetadata> v;
+  const double sizes[7] = {0.0, 0.03, 0.1, 0.2, 0.5, 1.0, 1.7};
+  for (int i = 0; i < 67; i++) {
+    ObjectsTypeMetadata m = at(-1.3 + 0.04 * i, 1.3 - 0.038 * i, -1.0 + 0.034 * i, 0.25 + 0.01 * i, (i % 11) / 10.0);
+    if (i % 4 == 1) m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 1.0f, -1.0f, 1.0f, 1.0f, 1.0f, "ceiling"});
+    if (i % 8 == 2) m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 0.0f, 1.0f, 1.0f, 0.0f, 0.0f, "front left"});
+    if (i % 2 == 1) m.width = sizes[i % 7], m.height = sizes[(i / 2) % 7], m.depth = sizes[(i / 3) % 7];
+    if (i % 5 == 0) m.channelLock = i % 2 ? ChannelLock(true, 0.7) : ChannelLock(true);
+    if (i % 3 == 0) m.objectDivergence = CartesianObjectDivergence(i % 2 ? 1.0 : 0.4, 0.05 * (i % 9));
+    if (i % 13 == 5) m.objectDivergence = PolarObjectDivergence(0.0, 30.0);  // a zero divergence is no divergence
+    v.push_back(m);
+  }
+  v.push_back(at(0.0, 0.0, 0.0));
+  v.push_back(at(-0.0, 1.0, -0.0));
+  return v;
+}
+
+int main(int argc, char **argv) {
+  const bool host_only = argc > 1 && std::strcmp(argv[1], "host") == 0;
+  const Layout layout = getLayout("4+5+0");
+  const size_t n = layout.channels().size();
+  const AllocentricObjectsGainCalculator calc(layout);
+  std::vector<float> direct(n), diffuse(n);
+
+  // a block the point-source class renders: the same bits
+  {
+    const ear::hip::AllocentricGainCalculator point(layout);
+    std::vector<float> d(n), f(n);
+    ObjectsTypeMetadata m = at(0.3, -0.2, 0.4, 0.7, 0.25);
+    m.zoneExclusion.zones.push_back(CartesianExclusionZone{-1.0f, 1.0f, 1.0f, 1.0f, 0.0f, 0.0f, "front"});
+    point.calculate(m, d, f);
+    calc.calculate(m, direct, diffuse);
+    CHECK(std::memcmp(d.data(), direct.data(), 4 * n) == 0 && std::memcmp(f.data(), diffuse.data(), 4 * n) == 0);
+  }
+  // a lock onto M+000 from nearby; a full divergence over the width of the front row leaves nothing in the centre
+  {
+    ObjectsTypeMetadata m = at(0.05, 0.95, 0.0);
+    m.channelLock = ChannelLock(true);
+    calc.calculate(m, direct, diffuse);
+    for (size_t c = 0; c < n; c++) CHECK(direct[c] == (layout.channels()[c].name() == "M+000" ? 1.0f : 0.0f));
+    m.channelLock = ChannelLock(true, 0.01);  // too far for this maxDistance: not locked
+    calc.calculate(m, direct, diffuse);
+    size_t nonzero = 0;
+    for (size_t c = 0; c < n; c++) nonzero += direct[c] != 0.0f;
+    CHECK(nonzero > 1);
+    m = at(0.0, 1.0, 0.0);
+    m.objectDivergence = CartesianObjectDivergence(1.0, 1.0);
+    calc.calculate(m, direct, diffuse);
+    const float r2 = (float)std::sqrt(0.5);
+    for (size_t c = 0; c < n; c++) {
+      const std::string name = layout.channels()[c].name();
+      CHECK(std::fabs(direct[c] - (name == "M+030" || name == "M-030" ? r2 : 0.0f)) <= 1.2e-7f);
+    }
+    m = at(0.0, 0.0, 0.5);
+    m.width = m.height = m.depth = 1.0;
+    calc.calculate(m, direct, diffuse);
+    for (size_t c = 0; c < n; c++) CHECK((direct[c] > 0.0f) == !layout.channels()[c].isLfe());
+  }
+
+  // the calculator against the rows of the C ABI, bit for bit: single blocks and the batch
+  const std::vector<ObjectsTypeMetadata> blocks = some_blocks();
+  std::vector<std::vector<float>> bd, bf;
+  calc.calculate(blocks, bd, bf);
+  CHECK(bd.size() == blocks.size() && bf.size() == blocks.size());
+  {
+    earhip_allo *h = nullptr;
+    CHECK(earhip_allo_create("4+5+0", &h) == EARHIP_OK);
+    size_t differ = 0;
+    for (size_t i = 0; i < blocks.size(); i++) {
+      const ObjectsTypeMetadata &m = blocks[i];
+      std::vector<earhip_exclusion_zone> zones;
+      for (const ExclusionZone &z : m.zoneExclusion.zones) {
+        earhip_exclusion_zone c = earhip_exclusion_zone();
+        c.cartesian = 1, c.min_x = z.cartesian.minX, c.max_x = z.cartesian.maxX, c.min_y = z.cartesian.minY;
+        c.max_y = z.cartesian.maxY, c.min_z = z.cartesian.minZ, c.max_z = z.cartesian.maxZ;
+        zones.push_back(c);
+      }
+      uint32_t mask = 0;
+      CHECK(earhip_allo_excluded_channels(h, (int)zones.size(), zones.data(), &mask) == EARHIP_OK);
+      const unsigned char lock = m.channelLock.flag ? 1 : 0;
+      const double maxd = m.channelLock.hasMaxDistance ? m.channelLock.maxDistance : std::numeric_limits<double>::infinity();
+      const double range = m.objectDivergence.isCartesian ? m.objectDivergence.range : 0.0;
+      std::vector<float> d(n), f(n);
+      CHECK(earhip_allo_calculate_objects(h, 1, &m.position.cartesian.X, &m.position.cartesian.Y, &m.position.cartesian.Z, &m.width,
+                                          &m.height, &m.depth, &m.gain, &m.diffuse, &lock, &maxd, &m.objectDivergence.divergence,
+                                          &range, &mask, d.data(), f.data()) == EARHIP_OK);
+      calc.calculate(m, direct, diffuse);
+      if (std::memcmp(d.data(), direct.data(), 4 * n) != 0 || std::memcmp(f.data(), diffuse.data(), 4 * n) != 0 ||
+          std::memcmp(d.data(), bd[i].data(), 4 * n) != 0 || std::memcmp(f.data(), bf[i].data(), 4 * n) != 0)
+        differ++;
+    }
+    std::printf("calculator vs C ABI: %zu of %zu rows differ\n", differ, blocks.size());
+    CHECK(differ == 0);
+    int order[16];
+    CHECK(earhip_allo_lock_priority(h, order) == EARHIP_OK && layout.channels()[order[0]].name() == "M+000");
+    earhip_allo_destroy(h);
+  }
+
+  // what remains unrendered is refused by field name, not dropped
+  {
+    ObjectsTypeMetadata m = at(0.1, 0.2, 0.3);
+    m.width = 0.2, m.height = 0.1, m.depth = 0.3, m.channelLock = ChannelLock(true, 0.5);
+    m.objectDivergence = CartesianObjectDivergence(0.5, 0.25);
+    CHECK(refusal(calc, m, n).empty());
+    m = at(0.1, 0.2, 0.3), m.position = PolarPosition(10.0, 5.0, 1.0);
+    CHECK(names(refusal(calc, m, n), "position"));
+    m = at(0.1, 0.2, 0.3), m.cartesian = false;
+    CHECK(names(refusal(calc, m, n), "cartesian"));
+    m = at(0.1, 0.2, 0.3), m.objectDivergence = PolarObjectDivergence(0.5, 30.0);
+    CHECK(names(refusal(calc, m, n), "objectDivergence"));
+    m = at(0.1, 0.2, 0.3), m.screenRef = true;
+    CHECK(names(refusal(calc, m, n), "screenRef"));
+    m = at(0.1, 0.2, 0.3), m.zoneExclusion.zones.push_back(PolarExclusionZone{-30.0f, 30.0f, -10.0f, 10.0f, 0.0f, 2.0f, "front"});
+    CHECK(names(refusal(calc, m, n), "zone"));
+    // the batch refuses what the single form refuses
+    std::vector<ObjectsTypeMetadata> three(3, at(0.1, 0.2, 0.3));
+    three[2].screenRef = true;
+    bool threw = false;
+    try {
+      calc.calculate(three, bd, bf);
+    } catch (const ear::not_implemented &e) {
+      threw = names(e.what(), "screenRef");
+    }
+    CHECK(threw);
+    three[2] = at(0.1, 0.2, 0.3), three[1].objectDivergence = PolarObjectDivergence(0.2, 30.0);
+    threw = false;
+    try {
+      calc.calculate(three, bd, bf);
+    } catch (const ear::not_implemented &e) {
+      threw = names(e.what(), "objectDivergence");
+    }
+    CHECK(threw);
+  }
+  // output vector sizes, and bad values as invalid_argument
+  {
+    std::vector<float> small(n - 1), right(n);
+    const ObjectsTypeMetadata ok = at(0.0, 0.0, 0.0);
+    ObjectsTypeMetadata w = ok, v = ok, r = ok, l = ok;
+    w.width = -0.1, v.objectDivergence = CartesianObjectDivergence(1.5, 0.1), r.objectDivergence = CartesianObjectDivergence(0.5, -0.1);
+    l.channelLock = ChannelLock(false, -1.0);
+    int threw = 0;
+    for (int k = 0; k < 6; k++) {
+      try {
+        if (k == 0) calc.calculate(ok, small, right);
+        if (k == 1) calc.calculate(ok, right, small);
+        if (k == 2) calc.calculate(w, direct, diffuse);
+        if (k == 3) calc.calculate(v, direct, diffuse);
+        if (k == 4) calc.calculate(r, direct, diffuse);
+        if (k == 5) calc.calculate(l, direct, diffuse);
+      } catch (const ear::invalid_argument &) {
+        threw++;
+      }
+    }
+    CHECK(threw == 6);
+  }
+  // a layout without its LFE channels, and loudspeakers where the caller says
+  {
+    const Layout bare = layout.withoutLfe();
+    const AllocentricObjectsGainCalculator cb(bare);
+    std::vector<float> d(bare.channels().size()), f(bare.channels().size());
+    ObjectsTypeMetadata m = at(0.3, -0.2, 0.4, 0.7, 0.25);
+    m.width = 0.5, m.objectDivergence = CartesianObjectDivergence(0.3, 0.4);
+    cb.calculate(m, d, f);
+    calc.calculate(m, direct, diffuse);
+    size_t k = 0;
+    for (size_t c = 0; c < n; c++) {
+      if (layout.channels()[c].isLfe()) continue;
+      CHECK(d[k] == direct[c] && f[k] == diffuse[c]);
+      k++;
+    }
+    const Layout own("own", {Channel("L", PolarPosition(30.0, 0.0, 1.0)), Channel("R", PolarPosition(-30.0, 0.0, 1.0)),
+                             Channel("C", PolarPosition(0.0, 0.0, 1.0)), Channel("Ls", PolarPosition(110.0, 0.0, 1.0)),
+                             Channel("Rs", PolarPosition(-110.0, 0.0, 1.0))});
+    bool threw = false;
+    try {
+      AllocentricObjectsGainCalculator none(own);
+    } catch (const ear::not_implemented &) {
+      threw = true;
+    }
+    CHECK(threw);
+    const AllocentricObjectsGainCalculator co(own, {CartesianPosition(-1, 1, 0), CartesianPosition(1, 1, 0), CartesianPosition(0, 1, 0),
+                                                    CartesianPosition(-1, -1, 0), CartesianPosition(1, -1, 0)});
+    std::vector<float> d5(5), f5(5);
+    ObjectsTypeMetadata lock = at(0.1, -0.9, 0.0);
+    lock.channelLock = ChannelLock(true);
+    co.calculate(lock, d5, f5);
+    CHECK(d5[0] == 0.0f && d5[1] == 0.0f && d5[2] == 0.0f && d5[3] == 0.0f && d5[4] == 1.0f);
+  }
+  if (host_only) {
+    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
+    return g_failed ? 1 : 0;
+  }
+
+  // the batch form on the device (one launch) against the host form: the two run one core and differ only in the math
+  // library, whose errors are far below half a float32 spacing, so an output of one is the other's float or its neighbour
+  {
+    std::vector<std::vector<float>> dd, df;
+    calc.calculate(blocks, bd, bf);
+    calc.calculate_device(blocks, dd, df);
+    CHECK(dd.size() == blocks.size() && df.size() == blocks.size());
+    size_t differ = 0, far = 0;
+    for (size_t i = 0; i < blocks.size() && i < dd.size(); i++)
+      for (size_t c = 0; c < n; c++)
+        for (int k = 0; k < 2; k++) {
+          const float a = k ? bf[i][c] : bd[i][c], b = k ? df[i][c] : dd[i][c];
+          differ += a != b;
+          far += !(std::fabs(a - b) <= std::fabs(a) * 1.2e-7f + 1e-12f);
+        }
+    std::printf("device batch vs host: %zu of %zu values differ, %zu by more than one spacing\n", differ, 2 * n * blocks.size(), far);
+    CHECK(far == 0);
+    std::vector<ObjectsTypeMetadata> bad = blocks;
+    bad[41].width = -1.0;
+    bool threw = false;
+    try {
+      calc.calculate_device(bad, dd, df);
+    } catch (const ear::invalid_argument &e) {
+      threw = names(e.what(), "metadata block 41");
+    }
+    CHECK(threw);
+    bad[41] = blocks[41], bad[3].screenRef = true;
+    threw = false;
+    try {
+      calc.calculate_device(bad, dd, df);
+    } catch (const ear::not_implemented &e) {
+      threw = names(e.what(), "screenRef");
+    }
+    CHECK(threw);
+    calc.calculate_device(std::vector<ObjectsTypeMetadata>(), dd, df);
+    CHECK(dd.empty() && df.empty());
+  }
+  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
+  return g_failed ? 1 : 0;
+}
