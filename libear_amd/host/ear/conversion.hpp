@@ -9,8 +9,7 @@
 #include <utility>
 #include <vector>
 
-#include "hip.hpp"
-#include "metadata.hpp"
+#include "hip_batch.hpp"
 
 namespace ear {
   namespace conversion {
@@ -90,7 +89,16 @@ namespace ear {
 
     namespace detail {
       // the batch form: the elements that need converting go to the device in one launch, through buffers in
-      // host memory the device reaches (earhip_host_alloc), converted in place; the others have their flag fixed
+      // host memory the device reaches (a DeviceBatch), converted in place; the others have their flag fixed
+      /// the arrays of convert_batch's block, in the order they are carved: positions and extents, converted in place
+      struct Arrays {
+        Arrays(ear::detail::Carver &c, size_t n) {
+          for (double *&p : a) p = c.take<double>(n);
+          status = c.take<int>(n);
+        }
+        double *a[6];
+        int *status;
+      };
       inline void convert_batch(std::vector<ObjectsTypeMetadata> &metadata, hip::Context &ctx, bool to_polar) {
         std::vector<size_t> idx;
         for (size_t i = 0; i < metadata.size(); i++) {
@@ -100,11 +108,9 @@ namespace ear {
         }
         const size_t n = idx.size();
         if (n == 0) return;
-        void *mem = nullptr;
-        hip::check(earhip_host_alloc(ctx.get(), n * (6 * sizeof(double) + sizeof(int)), &mem));
-        double *a[6];
-        for (int k = 0; k < 6; k++) a[k] = static_cast<double *>(mem) + k * n;
-        int *status = reinterpret_cast<int *>(static_cast<double *>(mem) + 6 * n);
+        const ear::detail::DeviceBatch<Arrays> batch(ctx, n);
+        double *const *a = batch.arrays.a;
+        int *status = batch.arrays.status;
         for (size_t j = 0; j < n; j++) {
           const ObjectsTypeMetadata &m = metadata[idx[j]];
           if (to_polar) {
@@ -115,34 +121,25 @@ namespace ear {
           }
           a[3][j] = m.width, a[4][j] = m.height, a[5][j] = m.depth;
         }
-        int st = to_polar ? earhip_conversion_to_polar_device(ctx.get(), n, a[0], a[1], a[2], a[3], a[4], a[5], a[0],
-                                                              a[1], a[2], a[3], a[4], a[5], status)
-                          : earhip_conversion_to_cartesian_device(ctx.get(), n, a[0], a[1], a[2], a[3], a[4], a[5],
-                                                                  a[0], a[1], a[2], a[3], a[4], a[5], status);
-        if (st == EARHIP_OK) st = earhip_ctx_synchronize(ctx.get());
-        const std::string msg = st == EARHIP_OK ? std::string() : std::string(earhip_last_error());
-        if (st == EARHIP_OK) {
-          // libear stops at the first failing element: so does the batch, before anything is written back
-          for (size_t j = 0; j < n && st == EARHIP_OK; j++)
-            if (status[j] != EARHIP_OK) {
-              st = status[j];
-              hip::check(earhip_host_release(ctx.get(), mem));
-              hip::check(st, "metadata block " + std::to_string(idx[j]) +
-                                 (st == EARHIP_INVALID_ARGUMENT ? ": azimuth is infinite or beyond +-2^40 degrees"
-                                                                : ": could not find sector"));
-            }
-          for (size_t j = 0; j < n; j++) {
-            ObjectsTypeMetadata &m = metadata[idx[j]];
-            if (to_polar)
-              m.position = PolarPosition(a[0][j], a[1][j], a[2][j]);
-            else
-              m.position = CartesianPosition(a[0][j], a[1][j], a[2][j]);
-            m.cartesian = !to_polar;
-            m.width = a[3][j], m.height = a[4][j], m.depth = a[5][j];
-          }
+        // libear stops at the first failing element: so does the batch, before anything is written back
+        batch.finish(to_polar ? earhip_conversion_to_polar_device(ctx.get(), n, a[0], a[1], a[2], a[3], a[4], a[5], a[0], a[1],
+                                                                  a[2], a[3], a[4], a[5], status)
+                              : earhip_conversion_to_cartesian_device(ctx.get(), n, a[0], a[1], a[2], a[3], a[4], a[5], a[0],
+                                                                      a[1], a[2], a[3], a[4], a[5], status),
+                     status, n, [&idx, status](size_t j) {
+                       const bool azimuth = status[j] == EARHIP_INVALID_ARGUMENT;
+                       return ear::detail::bad_block(
+                           idx[j], azimuth ? "azimuth is infinite or beyond +-2^40 degrees" : "could not find sector", status[j]);
+                     });
+        for (size_t j = 0; j < n; j++) {
+          ObjectsTypeMetadata &m = metadata[idx[j]];
+          if (to_polar)
+            m.position = PolarPosition(a[0][j], a[1][j], a[2][j]);
+          else
+            m.position = CartesianPosition(a[0][j], a[1][j], a[2][j]);
+          m.cartesian = !to_polar;
+          m.width = a[3][j], m.height = a[4][j], m.depth = a[5][j];
         }
-        earhip_host_release(ctx.get(), mem);
-        hip::check(st, msg);
       }
     }  // namespace detail
 

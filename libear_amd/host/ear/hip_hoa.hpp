@@ -8,8 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "hip.hpp"
-#include "metadata.hpp"
+#include "hip_batch.hpp"
 
 namespace ear {
   namespace hip {
@@ -47,30 +46,20 @@ namespace ear {
         for (size_t i = 0; i < n; i++) refuse(metadata[i]);
         gains.assign(n, std::vector<T>(nc));
         if (n == 0) return;
-        void *mem = nullptr;
-        check(earhip_host_alloc(ctx.get(), n * (3 * sizeof(double) + sizeof(int) + nc * sizeof(float)), &mem));
-        double *az = static_cast<double *>(mem), *el = az + n, *gain = el + n;
-        float *out = reinterpret_cast<float *>(gain + n);
-        int *status = reinterpret_cast<int *>(out + n * nc);
+        const ear::detail::DeviceBatch<Arrays> batch(ctx, n, nc);
+        const Arrays &a = batch.arrays;
         for (size_t i = 0; i < n; i++) {
-          az[i] = metadata[i].position.polar.azimuth, el[i] = metadata[i].position.polar.elevation;
-          gain[i] = metadata[i].gain;
+          a.az[i] = metadata[i].position.polar.azimuth, a.el[i] = metadata[i].position.polar.elevation;
+          a.gain[i] = metadata[i].gain;
         }
-        int st = earhip_hoa_encode_device(ctx.get(), (int)nc, orders_.data(), degrees_.data(), norm_.c_str(), n, az, el, gain,
-                                          out, status);
-        if (st == EARHIP_OK) st = earhip_ctx_synchronize(ctx.get());
-        std::string msg = st == EARHIP_OK ? std::string() : std::string(earhip_last_error());
-        for (size_t i = 0; i < n && st == EARHIP_OK; i++)
-          if (status[i] != 0) {
-            st = EARHIP_INVALID_ARGUMENT;
-            msg = "metadata block " + std::to_string(i) +
-                  ": azimuth, elevation and gain must be finite and the elevation within +-90 degrees";
-          }
-        if (st == EARHIP_OK)
-          for (size_t i = 0; i < n; i++)
-            for (size_t c = 0; c < nc; c++) gains[i][c] = (T)out[i * nc + c];
-        earhip_host_release(ctx.get(), mem);
-        check(st, msg);
+        batch.finish(earhip_hoa_encode_device(ctx.get(), (int)nc, orders_.data(), degrees_.data(), norm_.c_str(), n, a.az, a.el,
+                                              a.gain, a.out, a.status),
+                     a.status, n, [](size_t i) {
+                       return ear::detail::bad_block(
+                           i, "azimuth, elevation and gain must be finite and the elevation within +-90 degrees");
+                     });
+        for (size_t i = 0; i < n; i++)
+          for (size_t c = 0; c < nc; c++) gains[i][c] = (T)a.out[i * nc + c];
       }
 
       /// R [n_coef][n_coef] with encode(q u) = R encode(u): q is a proper rotation, row-major, acting on ADM Cartesian
@@ -86,6 +75,16 @@ namespace ear {
           for (size_t j = 0; j < nc; j++) out[i][j] = (T)r[i * nc + j];
         return out;
       }
+
+      /// the arrays of the batch form's block, in the order they are carved
+      struct Arrays {
+        Arrays(ear::detail::Carver &c, size_t n, size_t nc)
+            : az(c.take<double>(n)), el(c.take<double>(n)), gain(c.take<double>(n)), out(c.take<float>(n * nc)),
+              status(c.take<int>(n)) {}
+        double *az, *el, *gain;
+        float *out;
+        int *status;
+      };
 
      private:
       // The bus has no diffuse path and the encoder no extent, lock, divergence or zones: a field it would have to drop

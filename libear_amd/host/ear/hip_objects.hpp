@@ -7,7 +7,6 @@
 #pragma once
 #include <cstdint>
 #include <limits>
-#include <string>
 #include <vector>
 
 #include "gain_calculators.hpp"
@@ -17,11 +16,9 @@ namespace ear {
     class ObjectsGainCalculator {
      public:
       /// layout: an ITU-R BS.2051 layout (getLayout), with or without its LFE channels, or a layout of the caller's own
-      explicit ObjectsGainCalculator(const Layout &layout, Context &ctx = default_context()) {
-        std::vector<double> az, el;
-        keep_ = ear::detail::match_layout(layout, name_, az, el);
-        n_full_ = az.size();
-        check(earhip_panner_create_positions(ctx.get(), name_.c_str(), (int)n_full_, az.data(), el.data(), &h_));
+      explicit ObjectsGainCalculator(const Layout &layout, Context &ctx = default_context()) : layout_(layout) {
+        check(earhip_panner_create_positions(ctx.get(), layout_.name.c_str(), (int)layout_.n_full, layout_.az.data(),
+                                             layout_.el.data(), &h_));
       }
       ~ObjectsGainCalculator() { earhip_panner_destroy(h_); }
       ObjectsGainCalculator(const ObjectsGainCalculator &) = delete;
@@ -31,12 +28,7 @@ namespace ear {
       template <typename T>
       void calculate(const ObjectsTypeMetadata &metadata, std::vector<T> &directGains, std::vector<T> &diffuseGains,
                      const WarningCB & = default_warning_cb) {
-        if (directGains.size() != keep_.size() || diffuseGains.size() != keep_.size())
-          throw invalid_argument("incorrect size for output vector");
-        std::vector<std::vector<T>> d, f;
-        calculate(std::vector<ObjectsTypeMetadata>(1, metadata), d, f);
-        directGains = d[0];
-        diffuseGains = f[0];
+        ear::detail::calculate_one(*this, layout_, metadata, directGains, diffuseGains);
       }
       /// a batch of metadata blocks in one device call.  Still refused, with libear's messages: Cartesian positions and
       /// `cartesian`, a non-zero CartesianObjectDivergence, screenRef.
@@ -44,8 +36,8 @@ namespace ear {
       void calculate(const std::vector<ObjectsTypeMetadata> &metadata, std::vector<std::vector<T>> &directGains,
                      std::vector<std::vector<T>> &diffuseGains) {
         const size_t n = metadata.size();
-        std::vector<double> az(n), el(n), dist(n), gain(n), diffuse(n), width(n), height(n), depth(n), lock_max(n), div(n),
-            range(n);
+        ear::detail::PolarRows r(n);
+        std::vector<double> lock_max(n), div(n), range(n);
         std::vector<unsigned char> lock(n);
         std::vector<uint32_t> excluded(n, 0);
         for (size_t i = 0; i < n; i++) {
@@ -53,46 +45,28 @@ namespace ear {
           if (m.cartesian || m.position.isCartesian) throw not_implemented("cartesian");
           if (m.objectDivergence.isCartesian && m.objectDivergence.divergence != 0.0) throw not_implemented("divergence");
           if (m.screenRef) throw not_implemented("screenRef");
-          az[i] = m.position.polar.azimuth, el[i] = m.position.polar.elevation, dist[i] = m.position.polar.distance;
-          width[i] = m.width, height[i] = m.height, depth[i] = m.depth;
-          gain[i] = m.gain, diffuse[i] = m.diffuse;
+          r.set(i, m);
           lock[i] = m.channelLock.flag ? 1 : 0;
           lock_max[i] = m.channelLock.hasMaxDistance ? m.channelLock.maxDistance : std::numeric_limits<double>::infinity();
           div[i] = m.objectDivergence.divergence;
           range[i] = m.objectDivergence.isCartesian ? 45.0 : m.objectDivergence.range;
           if (!m.zoneExclusion.zones.empty()) {
             std::vector<earhip_exclusion_zone> zones;
-            for (const ExclusionZone &z : m.zoneExclusion.zones) {
-              earhip_exclusion_zone c = earhip_exclusion_zone();
-              c.cartesian = z.isCartesian;
-              c.min_azimuth = z.polar.minAzimuth, c.max_azimuth = z.polar.maxAzimuth;
-              c.min_elevation = z.polar.minElevation, c.max_elevation = z.polar.maxElevation;
-              c.min_x = z.cartesian.minX, c.max_x = z.cartesian.maxX;
-              c.min_y = z.cartesian.minY, c.max_y = z.cartesian.maxY;
-              c.min_z = z.cartesian.minZ, c.max_z = z.cartesian.maxZ;
-              zones.push_back(c);
-            }
-            check(earhip_objects_excluded_channels(name_.c_str(), (int)zones.size(), zones.data(), &excluded[i]));
+            for (const ExclusionZone &z : m.zoneExclusion.zones) zones.push_back(ear::detail::to_c(z));
+            check(earhip_objects_excluded_channels(layout_.name.c_str(), (int)zones.size(), zones.data(), &excluded[i]));
           }
         }
-        std::vector<float> d(n * n_full_), f(n * n_full_);
-        check(earhip_panner_calculate_objects(h_, n, az.data(), el.data(), dist.data(), width.data(), height.data(), depth.data(),
-                                              gain.data(), diffuse.data(), lock.data(), lock_max.data(), div.data(), range.data(),
-                                              excluded.data(), d.data(), f.data()));
-        directGains.assign(n, std::vector<T>(keep_.size()));
-        diffuseGains.assign(n, std::vector<T>(keep_.size()));
-        for (size_t i = 0; i < n; i++)
-          for (size_t c = 0; c < keep_.size(); c++) {
-            directGains[i][c] = (T)d[i * n_full_ + keep_[c]];
-            diffuseGains[i][c] = (T)f[i * n_full_ + keep_[c]];
-          }
+        std::vector<float> d(n * layout_.n_full), f(n * layout_.n_full);
+        check(earhip_panner_calculate_objects(h_, n, r.az.data(), r.el.data(), r.dist.data(), r.width.data(), r.height.data(),
+                                              r.depth.data(), r.gain.data(), r.diffuse.data(), lock.data(), lock_max.data(),
+                                              div.data(), range.data(), excluded.data(), d.data(), f.data()));
+        layout_.scatter(n, d.data(), directGains);
+        layout_.scatter(n, f.data(), diffuseGains);
       }
 
      private:
-      std::string name_;
+      const ear::detail::LayoutBinding layout_;
       earhip_panner *h_ = nullptr;
-      std::vector<int> keep_;
-      size_t n_full_ = 0;
     };
   }  // namespace hip
 }  // namespace ear

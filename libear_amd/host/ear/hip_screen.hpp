@@ -12,8 +12,7 @@
 #include <string>
 #include <vector>
 
-#include "hip.hpp"
-#include "metadata.hpp"
+#include "hip_batch.hpp"
 
 namespace ear {
   namespace hip {
@@ -76,11 +75,8 @@ namespace ear {
           if (g == screens.size()) screens.push_back(s);
           group[i] = g;
         }
-        void *mem = nullptr;
-        check(earhip_host_alloc(ctx.get(), n * (2 * sizeof(double) + sizeof(int) + 3), &mem));
-        double *az = static_cast<double *>(mem), *el = az + n;
-        int *status = reinterpret_cast<int *>(el + n);
-        unsigned char *ref = reinterpret_cast<unsigned char *>(status + n), *h = ref + n, *v = h + n;
+        const ear::detail::DeviceBatch<Arrays> batch(ctx, n);
+        const Arrays &a = batch.arrays;
         std::vector<size_t> idx(n);
         std::vector<size_t> first(screens.size() + 1, 0);
         size_t j = 0;
@@ -89,8 +85,8 @@ namespace ear {
           for (size_t i = 0; i < n; i++)
             if (group[i] == g) {
               const ObjectsTypeMetadata &m = metadata[i];
-              idx[j] = i, az[j] = m.position.polar.azimuth, el[j] = m.position.polar.elevation;
-              ref[j] = m.screenRef ? 1 : 0, h[j] = lh[i], v[j] = lv[i];
+              idx[j] = i, a.az[j] = m.position.polar.azimuth, a.el[j] = m.position.polar.elevation;
+              a.ref[j] = m.screenRef ? 1 : 0, a.h[j] = lh[i], a.v[j] = lv[i];
               j++;
             }
         }
@@ -99,25 +95,28 @@ namespace ear {
         for (size_t g = 0; g < screens.size() && st == EARHIP_OK; g++) {
           const size_t o = first[g];
           st = earhip_screen_apply_device(ctx.get(), &screens[g], has_screen_ ? &reproduction_ : nullptr, first[g + 1] - o,
-                                          az + o, el + o, ref + o, h + o, v + o, az + o, el + o, status + o);
+                                          a.az + o, a.el + o, a.ref + o, a.h + o, a.v + o, a.az + o, a.el + o, a.status + o);
         }
-        if (st == EARHIP_OK) st = earhip_ctx_synchronize(ctx.get());
-        std::string msg = st == EARHIP_OK ? std::string() : std::string(earhip_last_error());
-        for (size_t k = 0; k < n && st == EARHIP_OK; k++)
-          if (status[k] != 0) {
-            st = EARHIP_INVALID_ARGUMENT;
-            msg = "metadata block " + std::to_string(idx[k]) +
-                  ": azimuth and elevation must be finite, the azimuth within +-2^40 and the elevation within +-90 degrees";
-          }
-        if (st == EARHIP_OK)
-          for (size_t k = 0; k < n; k++) {
-            ObjectsTypeMetadata &m = metadata[idx[k]];
-            m.position.polar.azimuth = az[k], m.position.polar.elevation = el[k];
-            m.screenRef = false;
-          }
-        earhip_host_release(ctx.get(), mem);
-        check(st, msg);
+        batch.finish(st, a.status, n, [&idx](size_t k) {
+          return ear::detail::bad_block(idx[k], "azimuth and elevation must be finite, the azimuth within +-2^40 and the "
+                                                "elevation within +-90 degrees");
+        });
+        for (size_t k = 0; k < n; k++) {
+          ObjectsTypeMetadata &m = metadata[idx[k]];
+          m.position.polar.azimuth = a.az[k], m.position.polar.elevation = a.el[k];
+          m.screenRef = false;
+        }
       }
+
+      /// the arrays of the batch form's block, in the order they are carved
+      struct Arrays {
+        Arrays(ear::detail::Carver &c, size_t n)
+            : az(c.take<double>(n)), el(c.take<double>(n)), status(c.take<int>(n)), ref(c.take<unsigned char>(n)),
+              h(c.take<unsigned char>(n)), v(c.take<unsigned char>(n)) {}
+        double *az, *el;
+        int *status;
+        unsigned char *ref, *h, *v;
+      };
 
      private:
       static earhip_screen to_c(const Screen &s) {

@@ -28,6 +28,8 @@
 #include "ear/screen.hpp"
 #include "ear/warnings.hpp"
 
+#include "dropin_check.h"
+
 using namespace ear;
 using namespace ear::dsp;
 
@@ -63,15 +65,6 @@ void operator delete[](void *p) noexcept { std::free(p); }
 void operator delete(void *p, std::size_t) noexcept { std::free(p); }
 void operator delete[](void *p, std::size_t) noexcept { std::free(p); }
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                         \
-  do {                                                                      \
-    g_checks++;                                                             \
-    if (!(cond)) {                                                          \
-      g_failed++;                                                           \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);         \
-    }                                                                       \
-  } while (0)
 
 using Vec = std::vector<float>;
 
@@ -200,13 +193,7 @@ static void test_gain_interpolator() {
     Vec xx(10), oo(10);
     const float *ip = xx.data();
     float *op = oo.data();
-    bool threw = false;
-    try {
-      gi.process(0, 10, &ip, &op);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(gi.process(0, 10, &ip, &op), ear::invalid_argument);
   }
 }
 
@@ -331,14 +318,8 @@ static void test_block_convolver() {
     Context c512(512, get_fft_hip()), c256(256, get_fft_hip());
     BlockConvolver conv(c512, 1);
     const Vec ones(600, 1.0f);
+    CHECK_THROWS_AS(conv.set_filter(Filter(c256, 10, ones.data())), ear::invalid_argument);
     bool threw = false;
-    try {
-      conv.set_filter(Filter(c256, 10, ones.data()));
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
     try {
       conv.crossfade_filter(Filter(c512, 513, ones.data()));
     } catch (const ear::invalid_argument &e) {
@@ -634,13 +615,7 @@ static void test_gain_calculator_objects() {
       threw = std::string(e.what()).find("incorrect size for output vector") != std::string::npos;
     }
     CHECK(threw);
-    threw = false;
-    try {
-      calc.calculate(otm, direct, none);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(calc.calculate(otm, direct, none), ear::invalid_argument);
     // a channel without explicit ranges stands where it really stands (src/layout.cpp:24-33)
     Channel moved("X", PolarPosition(12.0, 3.0, 1.0), PolarPosition(10.0, 0.0, 1.0));
     CHECK(moved.azimuthRange() == std::make_pair(12.0, 12.0) && moved.elevationRange() == std::make_pair(3.0, 3.0));
@@ -979,13 +954,7 @@ static void test_pinned_channel_buffers() {
   hc.release_host(reg_out.data());
   hc.release_host(pin_out);
   hc.release_host(pin_in);
-  bool threw = false;
-  try {
-    hc.release_host(pin_in);
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(hc.release_host(pin_in), ear::invalid_argument);
 }
 
 // libear's one run-time plugin point (include/ear/fft.hpp:54-62, include/ear/dsp/block_convolver.hpp:34): the
@@ -995,13 +964,7 @@ static void test_fft_plugin_point() {
     std::shared_ptr<FFTPlan<float>> plan(size_t) const override { return nullptr; }
   } foreign;
   using ear::dsp::block_convolver::Context;
-  bool threw = false;
-  try {
-    Context ctx(512, foreign);
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(Context ctx(512, foreign), ear::invalid_argument);
   bool ok = true;
   try {
     Context a(512, get_fft_hip());
@@ -1058,13 +1021,7 @@ static void test_context_options() {
   CHECK(hc.get_option("EARHIP_H2_TILE", v) && v == 256);
   hc.reset_option("H2_TILE");
   CHECK(!hc.get_option("H2_TILE", v));
-  bool refused = false;
-  try {
-    hc.set_option("NO_SUCH_KNOB", 1);
-  } catch (const ear::invalid_argument &) {
-    refused = true;
-  }
-  CHECK(refused);
+  CHECK_THROWS_AS(hc.set_option("NO_SUCH_KNOB", 1), ear::invalid_argument);
   // the exact-f32 gain kernel by option: same scene, within 1e-6 of the default kernels' result
   const std::vector<std::string> names{"M+030", "M-030", "M+000", "LFE1", "M+110", "M-110"};
   const size_t M = 40, N = names.size(), B = 512, T = 2;

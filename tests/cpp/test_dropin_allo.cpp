@@ -12,18 +12,11 @@
 #include <ear/bs2051.hpp>
 #include <ear/hip_allo.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using ear::hip::AllocentricGainCalculator;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static ObjectsTypeMetadata at(double x, double y, double z, double gain = 1.0, double diffuse = 0.0) {
   ObjectsTypeMetadata m;
@@ -174,34 +167,10 @@ int main(int argc, char **argv) {
   // output vector sizes, and bad values as invalid_argument
   {
     std::vector<float> small(n - 1), right(n);
-    bool threw = false;
-    try {
-      calc.calculate(at(0.0, 0.0, 0.0), small, right);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      calc.calculate(at(0.0, 0.0, 0.0), right, small);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      calc.calculate(at(0.0, NAN, 0.0), direct, diffuse);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      calc.calculate(at(0.0, 0.0, 0.0, 1.0, 1.5), direct, diffuse);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(calc.calculate(at(0.0, 0.0, 0.0), small, right), ear::invalid_argument);
+    CHECK_THROWS_AS(calc.calculate(at(0.0, 0.0, 0.0), right, small), ear::invalid_argument);
+    CHECK_THROWS_AS(calc.calculate(at(0.0, NAN, 0.0), direct, diffuse), ear::invalid_argument);
+    CHECK_THROWS_AS(calc.calculate(at(0.0, 0.0, 0.0, 1.0, 1.5), direct, diffuse), ear::invalid_argument);
   }
   // a layout without its LFE channels: the same gains on the channels that remain
   {
@@ -232,23 +201,11 @@ int main(int argc, char **argv) {
     std::vector<float> d(6), f(6);
     cp.calculate(at(-0.25, 0.5, 0.0), d, f);
     CHECK(gains_are(l050, d, {{"M+030", r2}, {"M+000", r2}}));
-    bool threw = false;
-    try {
-      AllocentricGainCalculator bad(l050, std::vector<CartesianPosition>(5));
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(AllocentricGainCalculator bad(l050, std::vector<CartesianPosition>(5)), ear::invalid_argument);
     const Layout own("own", {Channel("L", PolarPosition(30.0, 0.0, 1.0)), Channel("R", PolarPosition(-30.0, 0.0, 1.0)),
                              Channel("C", PolarPosition(0.0, 0.0, 1.0)), Channel("Ls", PolarPosition(110.0, 0.0, 1.0)),
                              Channel("Rs", PolarPosition(-110.0, 0.0, 1.0))});
-    threw = false;
-    try {
-      AllocentricGainCalculator none(own);
-    } catch (const ear::not_implemented &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(AllocentricGainCalculator none(own), ear::not_implemented);
     const AllocentricGainCalculator co(own, {CartesianPosition(-1, 1, 0), CartesianPosition(1, 1, 0), CartesianPosition(0, 1, 0),
                                              CartesianPosition(-1, -1, 0), CartesianPosition(1, -1, 0)});
     std::vector<float> d5(5), f5(5);
@@ -256,8 +213,7 @@ int main(int argc, char **argv) {
     CHECK(d5[0] == 0.0f && d5[1] == 0.0f && d5[2] == r2 && d5[3] == 0.5f && d5[4] == 0.5f);
   }
   if (host_only) {
-    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
-    return g_failed ? 1 : 0;
+    return summary("host");
   }
 
   // the batch form on the device (one launch) against the host form: the two run one core and differ only in the math
@@ -289,6 +245,5 @@ int main(int argc, char **argv) {
     calc.calculate_device(std::vector<ObjectsTypeMetadata>(), dd, df);
     CHECK(dd.empty() && df.empty());
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

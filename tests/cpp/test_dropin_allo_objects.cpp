@@ -14,18 +14,11 @@
 #include <ear/hip_allo.hpp>
 #include <ear/hip_allo_objects.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using ear::hip::AllocentricObjectsGainCalculator;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static ObjectsTypeMetadata at(double x, double y, double z, double gain = 1.0, double diffuse = 0.0) {
   ObjectsTypeMetadata m;
@@ -223,13 +216,7 @@ int main(int argc, char **argv) {
     const Layout own("own", {Channel("L", PolarPosition(30.0, 0.0, 1.0)), Channel("R", PolarPosition(-30.0, 0.0, 1.0)),
                              Channel("C", PolarPosition(0.0, 0.0, 1.0)), Channel("Ls", PolarPosition(110.0, 0.0, 1.0)),
                              Channel("Rs", PolarPosition(-110.0, 0.0, 1.0))});
-    bool threw = false;
-    try {
-      AllocentricObjectsGainCalculator none(own);
-    } catch (const ear::not_implemented &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(AllocentricObjectsGainCalculator none(own), ear::not_implemented);
     const AllocentricObjectsGainCalculator co(own, {CartesianPosition(-1, 1, 0), CartesianPosition(1, 1, 0), CartesianPosition(0, 1, 0),
                                                     CartesianPosition(-1, -1, 0), CartesianPosition(1, -1, 0)});
     std::vector<float> d5(5), f5(5);
@@ -239,8 +226,7 @@ int main(int argc, char **argv) {
     CHECK(d5[0] == 0.0f && d5[1] == 0.0f && d5[2] == 0.0f && d5[3] == 0.0f && d5[4] == 1.0f);
   }
   if (host_only) {
-    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
-    return g_failed ? 1 : 0;
+    return summary("host");
   }
 
   // the batch form on the device (one launch) against the host form: the two run one core and differ only in the math
@@ -280,6 +266,5 @@ int main(int argc, char **argv) {
     calc.calculate_device(std::vector<ObjectsTypeMetadata>(), dd, df);
     CHECK(dd.empty() && df.empty());
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -12,28 +12,11 @@
 
 #include <ear/conversion.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using namespace ear::conversion;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
-#define CHECK_THROWS_AS(expr, type) \
-  do {                              \
-    bool thrown_ = false;           \
-    try {                           \
-      expr;                         \
-    } catch (const type &) {        \
-      thrown_ = true;               \
-    }                               \
-    CHECK(thrown_);                 \
-  } while (0)
 
 static bool near(double a, double b, double margin = 1e-6) { return std::fabs(a - b) <= margin; }
 static bool polar_eq(const PolarPosition &a, const PolarPosition &b, double m = 1e-6) {
@@ -174,13 +157,12 @@ int main() {
     g_failed++;
     std::printf("FAILED: exception %s\n", e.what());
   }
-  std::printf("single-element: %d passed, %d failed\n", g_checks - g_failed, g_failed);
+  summary("single-element");
   try {
     test_batch();
   } catch (const std::exception &e) {
     g_failed++;
     std::printf("FAILED: batch: exception %s\n", e.what());
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -15,17 +15,10 @@
 #include <ear/gain_calculators.hpp>
 #include <ear/hip_objects.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static Layout layout_2_7_0(const std::string &name) {
   std::vector<Channel> ch;
@@ -203,8 +196,7 @@ int main(int argc, char **argv) {
     CHECK(refused);
   }
   if (host_only) {
-    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
-    return g_failed ? 1 : 0;
+    return summary("host");
   }
 
   // ---- the calculators (device) ----
@@ -215,6 +207,5 @@ int main(int argc, char **argv) {
     GainCalculatorObjects calc(moved);  // the geometry follows the real positions
     check_objects(calc, moved);
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -21,18 +21,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_delaymix.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::DelayMatrix;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 6, n = B * T;
 
@@ -124,13 +117,7 @@ int main() {
 
   // a call longer than max_samples is refused and consumes nothing; reset() starts over
   {
-    bool threw = false;
-    try {
-      device.process_device(n + 1, bus, stride, sink, stride);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(device.process_device(n + 1, bus, stride, sink, stride), ear::invalid_argument);
   }
   host.reset();
   {
@@ -162,6 +149,5 @@ int main() {
     CHECK(threw);
   }
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -13,27 +13,10 @@
 
 #include <ear/ear.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
-#define CHECK_THROWS_AS(expr, type) \
-  do {                              \
-    bool thrown_ = false;           \
-    try {                           \
-      expr;                         \
-    } catch (const type &) {        \
-      thrown_ = true;               \
-    }                               \
-    CHECK(thrown_);                 \
-  } while (0)
 
 typedef std::vector<double> Gains;
 

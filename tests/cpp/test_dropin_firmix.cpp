@@ -18,18 +18,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_firmix.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::FirMatrix;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, K = 2, B = 512, T = 6, n = B * T, J = 700, LFE = 3;
 
@@ -139,22 +132,9 @@ int main() {
   // a matrix of the wrong width or block size is refused
   FirMatrix wide(N + 1, K, B, 4, std::vector<float>((N + 1) * K * 4, 1.0f)), small(N, K, B / 2, 4, std::vector<float>(N * K * 4, 1.0f));
   for (FirMatrix *w : {&wide, &small}) {
-    threw = false;
-    try {
-      r.attach_fir_matrix(*w, sink, stride, cap);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(r.attach_fir_matrix(*w, sink, stride, cap), ear::invalid_argument);
   }
-  threw = false;
-  try {
-    FirMatrix bad(N, K, 96, 4, std::vector<float>(N * K * 4, 1.0f));
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(FirMatrix bad(N, K, 96, 4, std::vector<float>(N * K * 4, 1.0f)), ear::invalid_argument);
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -14,17 +14,10 @@
 
 #include <ear/hip_firmix.hpp>
 
+#include "dropin_check.h"
+
 using ear::hip::FirMatrix;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t C = 3, K = 2, J = 129, B = 64, T = 7, n = B * T, S = 1, F = 1;
 
@@ -121,6 +114,5 @@ int main() {
   CHECK(refused([&] { FirMatrix none(C, K, B, J, h0, 4, 0); }));
   CHECK(refused([&] { FirMatrix many(C, K, B, J, h0, 4, 4097); }));
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

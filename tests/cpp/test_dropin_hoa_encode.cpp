@@ -10,18 +10,11 @@
 
 #include <ear/hip_hoa.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using ear::hip::HOAEncoder;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static void acn(int order, std::vector<int> &orders, std::vector<int> &degrees) {
   for (int n = 0; n <= order; n++)
@@ -118,36 +111,12 @@ int main(int argc, char **argv) {
   }
   // status codes as exceptions
   {
-    bool threw = false;
-    try {
-      HOAEncoder bad(o1, d1, "foo");
-    } catch (const ear::adm_error &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      HOAEncoder bad(std::vector<int>{4}, std::vector<int>{0}, "FuMa");
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      HOAEncoder bad(std::vector<int>{1, 1}, std::vector<int>{0});
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
+    CHECK_THROWS_AS(HOAEncoder bad(o1, d1, "foo"), ear::adm_error);
+    CHECK_THROWS_AS(HOAEncoder bad(std::vector<int>{4}, std::vector<int>{0}, "FuMa"), ear::invalid_argument);
+    CHECK_THROWS_AS(HOAEncoder bad(std::vector<int>{1, 1}, std::vector<int>{0}), ear::invalid_argument);
     const HOAEncoder enc(o1, d1);
     std::vector<float> g;
-    try {
-      enc.calculate(at(10.0, 91.0), g);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(enc.calculate(at(10.0, 91.0), g), ear::invalid_argument);
   }
   // rotation(): a yaw of 90 degrees against the closed form enc(az + 90), order 7 N3D; and a q that is no rotation
   {
@@ -176,17 +145,10 @@ int main(int argc, char **argv) {
         if (o7[i] != o7[j] && R[i][j] != 0.0) cross_zero = false;
     CHECK(cross_zero);
     const double mirror[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, -1.0};
-    bool threw = false;
-    try {
-      enc.rotation(mirror);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(enc.rotation(mirror), ear::invalid_argument);
   }
   if (host_only) {
-    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
-    return g_failed ? 1 : 0;
+    return summary("host");
   }
 
   // the batch path (one device launch) equals the single-element path bit for bit, at fixed positions: the two run one core
@@ -220,6 +182,5 @@ int main(int argc, char **argv) {
     enc.calculate(std::vector<ObjectsTypeMetadata>(), none);
     CHECK(none.empty());
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -19,18 +19,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_iir.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::IirBank;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 6, n = B * T, LFE = 3;
 
@@ -136,13 +129,7 @@ int main() {
   CHECK(w <= 1.0);
 
   // a call longer than max_samples is refused and consumes nothing; reset() starts over
-  bool threw = false;
-  try {
-    alone.process_device(n + 1, bus, stride, sink, stride);
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(alone.process_device(n + 1, bus, stride, sink, stride), ear::invalid_argument);
   bank.reset();
   {
     std::vector<float *> ip, mp;
@@ -155,7 +142,7 @@ int main() {
 
   // configurations outside the header's limits
   for (int which = 0; which < 4; which++) {
-    threw = false;
+    bool threw = false;
     try {
       if (which == 0) IirBank bad(N, N, {}, n);
       if (which == 1) IirBank bad(N, N, {{0, 0, 1.0, {IirBank::Section{{1.0, 0.0, 0.0, 0.0, 1.0}}}}}, n);
@@ -167,6 +154,5 @@ int main() {
     CHECK(threw);
   }
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

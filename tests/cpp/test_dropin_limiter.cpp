@@ -19,18 +19,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_limiter.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::Limiter;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 6, n = B * T;
 static const int L = 48, H = 200, TAPS = 12, D = TAPS / 2, K = L + 1, MW = L + 2 + H;
@@ -199,13 +192,7 @@ int main() {
 
   // a limiter of the wrong width is refused, and so is a configuration outside the header's limits
   Limiter wide(N + 1, c, L, H, n);
-  threw = false;
-  try {
-    r.attach_limiter(wide, sink, stride, cap);
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(r.attach_limiter(wide, sink, stride, cap), ear::invalid_argument);
   for (int which = 0; which < 4; which++) {
     threw = false;
     try {
@@ -221,6 +208,5 @@ int main() {
   Limiter own(2, c, 8, 0, 64, 96000, 2, 3, std::vector<double>{0.1, 0.8, 0.1, 0.3, 0.6, 0.1});
   CHECK(own.latency() == 8 + 1);
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

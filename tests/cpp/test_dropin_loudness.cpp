@@ -18,18 +18,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_loudness.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::LoudnessMeter;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 60, n = B * T, STEP = 4800;
 
@@ -93,13 +86,7 @@ int main() {
 
   const std::vector<double> w = ear::hip::loudness_layout_weights("0+5+0");
   CHECK((w == std::vector<double>{1.0, 1.0, 1.0, 0.0, 1.41, 1.41}));
-  bool threw = false;
-  try {
-    ear::hip::loudness_layout_weights("no such layout");
-  } catch (const ear::unknown_layout &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(ear::hip::loudness_layout_weights("no such layout"), ear::unknown_layout);
 
   // two calls of process() from host pointers with the meter attached
   std::mt19937 rng(7);
@@ -151,14 +138,7 @@ int main() {
 
   // a meter of the wrong width is refused
   LoudnessMeter wrong(N + 1, 48000, 8);
-  threw = false;
-  try {
-    r.attach_loudness(wrong);
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(r.attach_loudness(wrong), ear::invalid_argument);
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

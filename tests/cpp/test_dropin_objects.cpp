@@ -12,18 +12,11 @@
 #include <ear/gain_calculators.hpp>
 #include <ear/hip_objects.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using ear::hip::ObjectsGainCalculator;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 // the gains are `want` on the channels it names and 0 everywhere else, within tol
 static bool gains_are(const Layout &layout, const std::vector<float> &g, const std::map<std::string, double> &want, double tol) {
@@ -135,15 +128,9 @@ int main() {
   CHECK(!refuses(calc, base, n));
   // values outside their ranges are invalid arguments
   {
-    bool threw = false;
     m = base;
     m.objectDivergence = PolarObjectDivergence(1.5);
-    try {
-      calc.calculate(m, direct, diffuse);
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(calc.calculate(m, direct, diffuse), ear::invalid_argument);
   }
 
   // ear::GainCalculatorObjects refuses all three, as libear does
@@ -168,6 +155,5 @@ int main() {
   calc.calculate(m, d2, f2);
   CHECK(direct == d2 && diffuse == f2);
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

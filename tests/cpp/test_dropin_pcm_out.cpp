@@ -15,17 +15,10 @@
 #include <ear/decorrelate.hpp>
 #include <ear/dsp/objects_renderer.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 4, n = B * T;
 static const int C = 2 * (int)M + 1, FIRST = 5;
@@ -132,6 +125,5 @@ int main() {
     std::printf("FAILED: %s\n", e.what());
     return 1;
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

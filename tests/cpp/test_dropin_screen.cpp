@@ -14,18 +14,11 @@
 #include <ear/hip_objects.hpp>
 #include <ear/hip_screen.hpp>
 
+#include "dropin_check.h"
+
 using namespace ear;
 using ear::hip::ScreenHandler;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const Screen kScreen30 = PolarScreen{1.78, PolarPosition(0.0, 0.0, 1.0), 30.0};
 static const Screen kPolar15 = PolarScreen{1.5, PolarPosition(-20.0, 10.0, 2.0), 40.0};
@@ -130,28 +123,12 @@ int main(int argc, char **argv) {
     CHECK(threw);
     threw = false;
     m = at(10.0, 5.0), m.cartesian = true;
-    try {
-      to30.apply(m);
-    } catch (const ear::not_implemented &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(to30.apply(m), ear::not_implemented);
     for (int k = 0; k < 3; k++) {
-      threw = false;
-      try {
-        to30.apply(at(10.0, 5.0), k == 0 ? lock("top", nullptr) : (k == 1 ? lock(nullptr, "left") : lock("Left", nullptr)));
-      } catch (const ear::adm_error &) {
-        threw = true;
-      }
-      CHECK(threw);
+      const ScreenEdgeLock bad_lock = k == 0 ? lock("top", nullptr) : (k == 1 ? lock(nullptr, "left") : lock("Left", nullptr));
+      CHECK_THROWS_AS(to30.apply(at(10.0, 5.0), bad_lock), ear::adm_error);
     }
-    threw = false;
-    try {
-      to30.apply(at(10.0, 91.0));
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(to30.apply(at(10.0, 91.0)), ear::invalid_argument);
     // screens: across the rear seam, a zero aspect ratio, a width of 180 — as reproduction, as reference, in edges()
     const Screen bad[3] = {PolarScreen{1.78, PolarPosition(170.0, 0.0, 1.0), 58.0}, PolarScreen{0.0, PolarPosition(0.0, 0.0, 1.0), 58.0},
                            PolarScreen{1.78, PolarPosition(0.0, 0.0, 1.0), 180.0}};
@@ -176,8 +153,7 @@ int main(int argc, char **argv) {
     }
   }
   if (host_only) {
-    std::printf("host: %d passed, %d failed\n", g_checks - g_failed, g_failed);
-    return g_failed ? 1 : 0;
+    return summary("host");
   }
 
   // the batch form (one device launch per reference screen) equals the single form bit for bit
@@ -233,20 +209,8 @@ int main(int argc, char **argv) {
     CHECK(threw && batch[0].screenRef == blocks[0].screenRef && batch[1].position.polar.azimuth == blocks[1].position.polar.azimuth);
     batch = blocks;
     batch[5].position = CartesianPosition(0.0, 1.0, 0.0);
-    threw = false;
-    try {
-      to15.apply(batch, locks);
-    } catch (const ear::not_implemented &) {
-      threw = true;
-    }
-    CHECK(threw);
-    threw = false;
-    try {
-      to15.apply(batch, std::vector<ScreenEdgeLock>(3));
-    } catch (const ear::invalid_argument &) {
-      threw = true;
-    }
-    CHECK(threw);
+    CHECK_THROWS_AS(to15.apply(batch, locks), ear::not_implemented);
+    CHECK_THROWS_AS(to15.apply(batch, std::vector<ScreenEdgeLock>(3)), ear::invalid_argument);
   }
   // in front of the gain calculators: they refuse the raw block and accept the handler's result
   {
@@ -270,6 +234,5 @@ int main(int argc, char **argv) {
     }
     CHECK(ok);
   }
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -20,18 +20,11 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_src.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::SampleRateConverter;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 6, n = B * T;
 static const size_t UP = 147, DOWN = 160, TAPS = 48;
@@ -152,6 +145,5 @@ int main() {
     CHECK(threw);
   }
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

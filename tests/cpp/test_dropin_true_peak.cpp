@@ -18,19 +18,12 @@
 #include <ear/dsp/objects_renderer.hpp>
 #include <ear/hip_loudness.hpp>
 
+#include "dropin_check.h"
+
 using ear::dsp::ObjectsRenderer;
 using ear::hip::LoudnessMeter;
 using ear::hip::TruePeak;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond)                                                 \
-  do {                                                              \
-    g_checks++;                                                     \
-    if (!(cond)) {                                                  \
-      g_failed++;                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-    }                                                               \
-  } while (0)
 
 static const size_t M = 13, N = 6, B = 512, T = 300, n = B * T, STEP = 4800, CALLS = 4;
 
@@ -181,20 +174,10 @@ int main() {
   CHECK(e.lra == d.lra && e.low == d.low && e.high == d.high);
 
   // a meter made without true peak has no peaks to give; a table of the wrong shape is refused
-  bool threw = false;
-  try {
-    plain.peaks();
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
-  threw = false;
-  try {
-    LoudnessMeter bad(N, 48000, 8, std::vector<double>(), ear::hip::default_context(), TruePeak::table(9, 2, std::vector<double>(18, 0.5)));
-  } catch (const ear::invalid_argument &) {
-    threw = true;
-  }
-  CHECK(threw);
+  CHECK_THROWS_AS(plain.peaks(), ear::invalid_argument);
+  CHECK_THROWS_AS(LoudnessMeter bad(N, 48000, 8, std::vector<double>(), ear::hip::default_context(),
+                                    TruePeak::table(9, 2, std::vector<double>(18, 0.5))),
+                  ear::invalid_argument);
   // reset() of the renderer leaves the peaks alone, reset() of the meter clears them
   r.reset(0);
   CHECK(meter.peaks().true_peak == got.true_peak);
@@ -202,6 +185,5 @@ int main() {
   CHECK(meter.num_steps() == 0 && meter.peaks().true_peak == std::vector<float>(N, 0.0f));
   r.detach_loudness();
 
-  std::printf("%d passed, %d failed\n", g_checks - g_failed, g_failed);
-  return g_failed ? 1 : 0;
+  return summary();
 }

@@ -3,40 +3,24 @@ against the mirror headers alone (tests/cpp/test_dropin_allo.cpp).  CPU suite: i
 and everything that needs no device passes (ObjectsTypeMetadata against the rows of the C ABI, each not_implemented by field
 name, the output vector sizes, a layout without its LFE channels, caller positions).  GPU suite: the whole program, where
 calculate_device (one device launch) is held to the host form."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build(tmp_path):
-    from libear_amd import build as build_lib
-    build_lib()
-    exe = str(tmp_path / "test_dropin_allo")
-    libdir = os.path.join(ROOT, "libear_amd", "lib")
-    cmd = ["g++", "-std=c++14", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "libear_amd", "host"),
-           os.path.join(ROOT, "tests", "cpp", "test_dropin_allo.cpp"),
-           "-L" + libdir, "-learhip", "-Wl,-rpath," + libdir, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+import _dropin
 
 
 def test_allocentric_calculator_dropin_program_compiles_as_cpp14_and_its_host_part_passes(tmp_path):
-    exe = build(tmp_path)
-    res = subprocess.run([exe, "host"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    exe = _dropin.build(tmp_path, "test_dropin_allo")
+    res = _dropin.run(exe, "host", timeout=120)
     m = re.search(r"^host: (\d+) passed, 0 failed$", res.stdout, flags=re.M)
     assert res.returncode == 0 and m and int(m.group(1)) >= 40, res.stdout
 
 
 @pytest.mark.gpu
 def test_allocentric_calculator_dropin_program_passes_on_gpu(tmp_path):
-    exe = build(tmp_path)
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    exe = _dropin.build(tmp_path, "test_dropin_allo")
+    res = _dropin.run(exe, timeout=300)
     print(res.stdout)
     assert res.returncode == 0, res.stdout
     assert re.search(r"^\d+ passed, 0 failed$", res.stdout, flags=re.M), res.stdout

@@ -2,35 +2,19 @@
 the mirror headers alone, as a libear application would be (tests/cpp/test_dropin_conversion.cpp).  CPU suite: it
 compiles as C++14 with -Wall -Werror, every single-element check passes, and the batch overloads fail loudly without a
 GPU.  GPU suite: the whole program passes."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build(tmp_path):
-    from libear_amd import build as build_lib
-    build_lib()
-    exe = str(tmp_path / "test_dropin_conversion")
-    libdir = os.path.join(ROOT, "libear_amd", "lib")
-    cmd = ["g++", "-std=c++14", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "libear_amd", "host"),
-           os.path.join(ROOT, "tests", "cpp", "test_dropin_conversion.cpp"),
-           "-L" + libdir, "-learhip", "-Wl,-rpath," + libdir, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+import _dropin
 
 
 def test_conversion_mirror_single_element_passes_without_gpu_and_batch_fails_loudly(tmp_path):
-    exe = build(tmp_path)
+    exe = _dropin.build(tmp_path, "test_dropin_conversion", wextra=False)
     import torch
     if torch.cuda.is_available():
         pytest.skip("a GPU is present; the run is covered by the gpu test")
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    res = _dropin.run(exe, timeout=120)
     m = re.search(r"single-element: (\d+) passed, 0 failed", res.stdout)
     assert m and int(m.group(1)) >= 50, res.stdout
     assert res.returncode != 0
@@ -39,8 +23,8 @@ def test_conversion_mirror_single_element_passes_without_gpu_and_batch_fails_lou
 
 @pytest.mark.gpu
 def test_conversion_dropin_program_passes_on_gpu(tmp_path):
-    exe = build(tmp_path)
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    exe = _dropin.build(tmp_path, "test_dropin_conversion", wextra=False)
+    res = _dropin.run(exe, timeout=300)
     print(res.stdout)
     assert res.returncode == 0, res.stdout
     assert re.search(r"^\d+ passed, 0 failed$", res.stdout, flags=re.M), res.stdout

@@ -4,35 +4,20 @@
 the bytes and the levels of the C call."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build(tmp_path):
-    from libear_amd import build as build_lib
-    build_lib()
-    exe = str(tmp_path / "test_dropin_pcm_out")
-    libdir = os.path.join(ROOT, "libear_amd", "lib")
-    cmd = ["g++", "-std=c++14", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "libear_amd", "host"),
-           os.path.join(ROOT, "tests", "cpp", "test_dropin_pcm_out.cpp"),
-           "-L" + libdir, "-learhip", "-Wl,-rpath," + libdir, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+import _dropin
 
 
 def test_pcm_out_dropin_program_compiles_as_cpp14(tmp_path):
-    assert os.path.exists(build(tmp_path))
+    assert os.path.exists(_dropin.build(tmp_path, "test_dropin_pcm_out"))
 
 
 @pytest.mark.gpu
 def test_pcm_out_dropin_program_passes_on_gpu(tmp_path):
-    exe = build(tmp_path)
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    exe = _dropin.build(tmp_path, "test_dropin_pcm_out")
+    res = _dropin.run(exe, timeout=300)
     print(res.stdout)
     assert res.returncode == 0, res.stdout
     assert re.search(r"^\d+ passed, 0 failed$", res.stdout, flags=re.M), res.stdout

@@ -5,35 +5,20 @@ written out on the host and ceil(N L / M) outputs, its host and device forms giv
 limits are refused.  (The stage is not attached to the renderer: there is no ObjectsRenderer::attach_src to test.)"""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build(tmp_path):
-    from libear_amd import build as build_lib
-    build_lib()
-    exe = str(tmp_path / "test_dropin_src")
-    libdir = os.path.join(ROOT, "libear_amd", "lib")
-    cmd = ["g++", "-std=c++14", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "libear_amd", "host"),
-           os.path.join(ROOT, "tests", "cpp", "test_dropin_src.cpp"),
-           "-L" + libdir, "-learhip", "-Wl,-rpath," + libdir, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+import _dropin
 
 
 def test_src_dropin_program_compiles_as_cpp14(tmp_path):
-    assert os.path.exists(build(tmp_path))
+    assert os.path.exists(_dropin.build(tmp_path, "test_dropin_src"))
 
 
 @pytest.mark.gpu
 def test_src_dropin_program_passes_on_gpu(tmp_path):
-    exe = build(tmp_path)
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    exe = _dropin.build(tmp_path, "test_dropin_src")
+    res = _dropin.run(exe, timeout=300)
     print(res.stdout)
     assert res.returncode == 0, res.stdout
     assert re.search(r"^\d+ passed, 0 failed$", res.stdout, flags=re.M), res.stdout

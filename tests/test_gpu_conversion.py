@@ -174,8 +174,8 @@ def test_cartesian_scene_through_to_polar_and_extent_panner(layout):
 def test_batch_overloads_equal_single_calls(tmp_path):
     """toPolar / toCartesian on std::vector<ObjectsTypeMetadata> (one device launch) against single calls, in the
     drop-in program (tests/cpp/test_dropin_conversion.cpp, test_batch)"""
-    import test_dropin_conversion
-    exe = test_dropin_conversion.build(tmp_path)
+    import _dropin
+    exe = _dropin.build(tmp_path, "test_dropin_conversion", wextra=False)
     res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     print(res.stdout)
     assert res.returncode == 0 and "FAILED" not in res.stdout, res.stdout
