@@ -1728,8 +1728,7 @@ int earhip_delaymix_align(int n, const double *distance_m, double sample_rate, d
  * the wave's 64 rows leave through one LDS tile as full-width contiguous stores, first direct, then diffuse_out.  No atomics:
  * the same input gives the same bits.
  *
- * Out of scope: the screen stages on Cartesian positions (a block with screenRef still takes group K and the polar producer),
- * attaching anything to a renderer, tables for layouts outside BS.2051.  The Cartesian extent panner (width, height, depth),
+ * Out of scope: attaching anything to a renderer, tables for layouts outside BS.2051.  The Cartesian extent panner (width, height, depth),
  * channelLock for Cartesian blocks and Cartesian objectDivergence are group U, on this handle; the entry points of this group
  * stay point-source.
  * ---------------------------------------------------------------------- */
@@ -1748,8 +1747,8 @@ int earhip_allo_calculate_device(earhip_ctx *ctx, const earhip_allo *a, size_t n
                                  const uint32_t *excluded_dev, float *direct_dev, float *diffuse_out_dev, int *status_dev);
 
 /* ------------------------------------------------------------------------
- * (U) Extent, channelLock and objectDivergence for the allocentric panner, on the handle of group T: with these every Cartesian
- * Objects block without screenRef is rendered allocentrically, on the host or as one device launch over a resident batch.
+ * (U) Extent, channelLock and objectDivergence for the allocentric panner, on the handle of group T: with these (and the
+ * screen stage of group V in front of them) every Cartesian Objects block is rendered allocentrically, on the host or as one device launch over a resident batch.
  * libear carries only a stub here too.  THIS COMMENT IS THE SPECIFICATION.  It was written after BS.2127-0 7.3.6, 7.3.7 and
  * 7.3.11 WITHOUT A REFERENCE IMPLEMENTATION TO COMPARE AGAINST and without the Recommendation's text at hand; three sets of
  * constants are THIS PROJECT'S READING: the lock weights 1/16, 4, 32; the 20-point grid; the fall-off 10^(-5.0625 (u^4 - 1)).
@@ -1816,6 +1815,55 @@ int earhip_allo_calculate_objects_device(earhip_ctx *ctx, const earhip_allo *a, 
                                          const double *lock_max_distance_dev, const double *divergence_dev,
                                          const double *position_range_dev, const uint32_t *excluded_dev, float *direct_dev,
                                          float *diffuse_out_dev, int *status_dev);
+
+/* ------------------------------------------------------------------------
+ * (V) The screen of a CARTESIAN Objects block: screenRef scaling and screenEdgeLock on (x, y, z), the stage in front of groups T
+ * and U that group R is in front of group I.  With it every Cartesian Objects block is rendered allocentrically: a block with
+ * screenRef or a screenEdgeLock no longer has to take group K and the polar producer.  libear has no counterpart (it refuses
+ * both everywhere).  THIS COMMENT IS THE SPECIFICATION, after BS.2127-0 7.3.3 and 7.3.4, which define both steps for a Cartesian
+ * position as: to polar with section 10's point conversion, the polar step, back with the inverse point conversion.
+ *
+ * Screens, edges, the NULL rules of the three flag arrays (a NULL screen_ref means all 1, a NULL lock array all 0), the lock
+ * codes, n < 2^31 and n == 0 are group R's.  Per element i:
+ *   1. A NULL reproduction makes every element a bit-for-bit copy, and none is checked.
+ *   2. An element with screen_ref[i] == 0 and both lock codes 0 is copied bit for bit, whatever it holds (NaN, infinity, -0.0;
+ *      status 0).  Chaining groups K, R and K cannot give this: there every position takes two lossy conversions, and one that
+ *      sits exactly on a loudspeaker plane of the cube (what groups T and U snap on) no longer does.
+ *   3. Any other element is checked first: a non-finite coordinate or a lock code above 2 is refused.  The host form returns
+ *      EARHIP_INVALID_ARGUMENT, the message naming the index; the elements before it are written, it and those after it are
+ *      not.  The device form writes NaN to all three outputs and status[i] = EARHIP_INVALID_ARGUMENT (1, as group R).
+ *   4. TO POLAR.  (az, el, d) = group K's point conversion of (x, y, z) (csrc/conversion.h).  A code it returns is the element's
+ *      code on the host and its status, with NaN outputs, on the device, as in group K.
+ *   5. SCALE AND LOCK.  Group R's steps 3 and 4 on (az, el) (csrc/screen.h); the conversion delivers az in [-180, 180] and el in
+ *      [-90, 90].  d is not changed.
+ *   6. BACK.  (x', y', z') = group K's point conversion of (az', el', d) to Cartesian, a code handled as in step 4.
+ * Extent is not touched.  Each output may alias its own input (an element's three inputs are read before its outputs are
+ * written), so the stage can run in place on the arrays groups T and U then read.  The origin stays the origin, and a position
+ * on the z axis with |z| >= 1e-10 (below that the conversion calls it the origin) keeps its z and stays on the axis, unless a
+ * vertical lock takes it off the pole.
+ *
+ * earhip_screen_apply_cartesian is a deliberate CPU computation on the calling thread, no context and no device.
+ * earhip_screen_apply_cartesian_device takes the two screens in host memory and the arrays as device pointers
+ * (device-reachable host memory included); it runs ONE kernel on the context's stream (one thread per element, 256 per block,
+ * the six segments a by-value argument: 27 bytes read and 24 written per position, against 131 for the three launches),
+ * allocates nothing, does not synchronise and never computes on the CPU.  Both forms call one core (csrc/screen_cart.h), which
+ * calls the cores of groups K and R as they stand, and the library is built without contraction.  So on every element with a
+ * flag set and no refusal THE HOST FORM HAS THE BITS OF earhip_conversion_to_polar, earhip_screen_apply,
+ * earhip_conversion_to_cartesian CHAINED, AND THE DEVICE FORM THE BITS OF THEIR THREE DEVICE FORMS CHAINED.  Device against host
+ * differs by what group K's libm calls differ on the two sides, nothing more.
+ *
+ * Out of scope: screen stages for HOA and DirectSpeakers, scaling of extent, fusing the stage into the kernels of groups T and
+ * U, a polar-out form.
+ * ---------------------------------------------------------------------- */
+int earhip_screen_apply_cartesian(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *x,
+                                  const double *y, const double *z, const unsigned char *screen_ref,
+                                  const unsigned char *lock_horizontal, const unsigned char *lock_vertical, double *x_out,
+                                  double *y_out, double *z_out);
+int earhip_screen_apply_cartesian_device(earhip_ctx *ctx, const earhip_screen *reference, const earhip_screen *reproduction,
+                                         size_t n, const double *x, const double *y, const double *z,
+                                         const unsigned char *screen_ref, const unsigned char *lock_horizontal,
+                                         const unsigned char *lock_vertical, double *x_out, double *y_out, double *z_out,
+                                         int *status);
 
 #ifdef __cplusplus
 }

@@ -1027,6 +1027,38 @@ def screen_apply_device(ctx, n, az, el, az_out, el_out, reproduction, reference=
                                             _dev_ptr(el_out, n, "float64"), _dev_ptr(status, n, "int32")))
 
 
+# (V) the same stage on Cartesian positions, in front of the allocentric panner
+
+def screen_apply_cartesian(x, y, z, reproduction, reference=None, screen_ref=None, lock_horizontal=None, lock_vertical=None):
+    """screenRef scaling from `reference` (None: the default screen) to `reproduction` (None: no screen, everything passes
+    through), then screenEdgeLock, of Cartesian positions, on the calling thread (no device needed): to polar, the polar
+    steps of screen_apply, back to Cartesian.  Arrays [n] -> (x, y, z).  screen_ref: flags, None = all set; lock_horizontal: 0
+    none, 1 left, 2 right; lock_vertical: 0 none, 1 bottom, 2 top; None = none.  An element with no flag set keeps its bits.
+    Raises on the first element it refuses, the message naming its index."""
+    f64, u8 = C.POINTER(C.c_double), C.POINTER(C.c_ubyte)
+    x = np.ascontiguousarray(np.atleast_1d(x), np.float64)
+    n = x.size
+    y, z = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,))) for v in (y, z))
+    flags = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.uint8), (n,)))
+             for v in (screen_ref, lock_horizontal, lock_vertical)]
+    out = [np.empty(n, np.float64) for _ in range(3)]
+    check(load().earhip_screen_apply_cartesian(_screen_ref(reference), _screen_ref(reproduction), C.c_size_t(n), _ptr(x, f64),
+                                               _ptr(y, f64), _ptr(z, f64), *[None if v is None else _ptr(v, u8) for v in flags],
+                                               *[_ptr(v, f64) for v in out]))
+    return tuple(out)
+
+
+def screen_apply_cartesian_device(ctx, n, x, y, z, x_out, y_out, z_out, reproduction, reference=None, screen_ref=None,
+                                  lock_horizontal=None, lock_vertical=None, status=None):
+    """the same on the device: float64 tensors (or device addresses) of n elements, the flags uint8 tensors, status an int32
+    tensor [n] (may be None): a non-zero code and NaN outputs for an element screen_apply_cartesian refuses.  An output may be
+    its own input (in place).  Enqueues one kernel on the context's stream and does not synchronise."""
+    check(load().earhip_screen_apply_cartesian_device(
+        ctx.h, _screen_ref(reference), _screen_ref(reproduction), C.c_size_t(n), *[_dev_ptr(v, n, "float64") for v in (x, y, z)],
+        _dev_ptr(screen_ref, n, "uint8"), _dev_ptr(lock_horizontal, n, "uint8"), _dev_ptr(lock_vertical, n, "uint8"),
+        *[_dev_ptr(v, n, "float64") for v in (x_out, y_out, z_out)], _dev_ptr(status, n, "int32")))
+
+
 # (T) the allocentric (Cartesian) point-source panner for Objects
 
 class Allo:

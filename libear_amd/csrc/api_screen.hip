@@ -1,13 +1,15 @@
 // api_screen.hip — screenRef scaling and screenEdgeLock of Objects positions (earhip group R; ITU-R BS.2127-0 sections 7.3.3
 // and 7.3.4, which libear refuses).  The per-element arithmetic is screen.h, shared by the host form (computed on the calling
 // thread, like the host forms of group K) and the device form (one thread per element, enqueued on the context's stream).
-// A screen's edges, and from them the six segments of a call, are host arithmetic.
+// A screen's edges, and from them the six segments of a call, are host arithmetic.  Group V is the same stage for Cartesian
+// positions: screen_cart.h wraps the per-element arithmetic in group K's point conversions, one kernel and one host loop here.
 #include <cmath>
 #include <cstdio>
 #include <string>
 
 #include "common.h"
 #include "screen.h"
+#include "screen_cart.h"
 
 using namespace earhip;
 using namespace earhip::screen;
@@ -102,6 +104,15 @@ __global__ void __launch_bounds__(256) k_screen_apply(Map m, ScreenArgs a, int *
 
 const size_t kMaxElements = (size_t)1 << 31;
 
+// the host arithmetic both groups share, after a call's own checks of n and its arrays: the call's map
+Map make_map_of(const earhip_screen *reference, const earhip_screen *reproduction) {
+  double e_ref[4], e_rep[4];
+  screen_edges(reference ? *reference : kDefaultScreen, "reference", e_ref);
+  if (!reproduction) return identity_map();
+  screen_edges(*reproduction, "reproduction", e_rep);
+  return make_map(e_ref, e_rep);
+}
+
 // the checks and the host arithmetic both forms share: the call's map and arrays
 Map make_call(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *az, const double *el,
               const unsigned char *ref, const unsigned char *lock_h, const unsigned char *lock_v, double *az_out,
@@ -109,11 +120,39 @@ Map make_call(const earhip_screen *reference, const earhip_screen *reproduction,
   require(n < kMaxElements, "too many elements (at most 2^31 - 1 per call)");
   require(n == 0 || (az && el && az_out && el_out), "azimuth, elevation, azimuth_out and elevation_out must not be NULL");
   a = ScreenArgs{n, az, el, ref, lock_h, lock_v, az_out, el_out};
-  double e_ref[4], e_rep[4];
-  screen_edges(reference ? *reference : kDefaultScreen, "reference", e_ref);
-  if (!reproduction) return identity_map();
-  screen_edges(*reproduction, "reproduction", e_rep);
-  return make_map(e_ref, e_rep);
+  return make_map_of(reference, reproduction);
+}
+
+// Group V.  SoA arrays of one call; an output may alias its own input, as in ScreenArgs.
+struct ScreenCartArgs {
+  size_t n;
+  const double *in[3];                         // x, y, z
+  const unsigned char *ref, *lock_h, *lock_v;  // NULL: all 1, all 0, all 0
+  double *out[3];
+};
+
+__host__ __device__ inline int apply_cart_element(const Map &m, const ScreenCartArgs &a, size_t i, double out[3]) {
+  return apply_cart_one(m, a.in[0][i], a.in[1][i], a.in[2][i], a.ref ? a.ref[i] : 1u, a.lock_h ? a.lock_h[i] : 0u,
+                        a.lock_v ? a.lock_v[i] : 0u, out);
+}
+
+__global__ void __launch_bounds__(256) k_screen_apply_cartesian(Map m, ScreenCartArgs a, int *status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  double out[3];
+  const int st = apply_cart_element(m, a, i, out);
+  if (st != EARHIP_OK) out[0] = out[1] = out[2] = __longlong_as_double(0x7ff8000000000000LL);  // the host form refuses it
+  for (int k = 0; k < 3; k++) a.out[k][i] = out[k];
+  if (status) status[i] = st;
+}
+
+Map make_cart_call(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *x, const double *y,
+                   const double *z, const unsigned char *ref, const unsigned char *lock_h, const unsigned char *lock_v,
+                   double *x_out, double *y_out, double *z_out, ScreenCartArgs &a) {
+  require(n < kMaxElements, "too many elements (at most 2^31 - 1 per call)");
+  require(n == 0 || (x && y && z && x_out && y_out && z_out), "x, y, z, x_out, y_out and z_out must not be NULL");
+  a = ScreenCartArgs{n, {x, y, z}, ref, lock_h, lock_v, {x_out, y_out, z_out}};
+  return make_map_of(reference, reproduction);
 }
 
 }  // namespace
@@ -168,6 +207,50 @@ int earhip_screen_apply_device(earhip_ctx *ctx, const earhip_screen *reference, 
     if (n == 0) return;
     ctx->use();
     hipLaunchKernelGGL(k_screen_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m, a, status);
+    EARHIP_HIP(hipGetLastError());
+  });
+}
+
+int earhip_screen_apply_cartesian(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *x,
+                                  const double *y, const double *z, const unsigned char *screen_ref,
+                                  const unsigned char *lock_horizontal, const unsigned char *lock_vertical, double *x_out,
+                                  double *y_out, double *z_out) {
+  return guarded([&] {
+    ScreenCartArgs a;
+    const Map m = make_cart_call(reference, reproduction, n, x, y, z, screen_ref, lock_horizontal, lock_vertical, x_out, y_out,
+                                 z_out, a);
+    for (size_t i = 0; i < n; i++) {
+      double out[3];
+      const int st = apply_cart_element(m, a, i, out);
+      if (st != EARHIP_OK) {
+        char msg[256];
+        if (st == EARHIP_INVALID_ARGUMENT)
+          std::snprintf(msg, sizeof msg, "element %zu: position %g, %g, %g, lock codes %u, %u: the coordinates must be finite, "
+                        "a lock code at most 2", i, x[i], y[i], z[i],
+                        a.lock_h ? a.lock_h[i] : 0u, a.lock_v ? a.lock_v[i] : 0u);
+        else
+          std::snprintf(msg, sizeof msg, "internal error: element %zu: could not find sector or p out of range (position %g, "
+                        "%g, %g)", i, x[i], y[i], z[i]);
+        throw Error{st, msg};
+      }
+      for (int k = 0; k < 3; k++) a.out[k][i] = out[k];
+    }
+  });
+}
+
+int earhip_screen_apply_cartesian_device(earhip_ctx *ctx, const earhip_screen *reference, const earhip_screen *reproduction,
+                                         size_t n, const double *x, const double *y, const double *z,
+                                         const unsigned char *screen_ref, const unsigned char *lock_horizontal,
+                                         const unsigned char *lock_vertical, double *x_out, double *y_out, double *z_out,
+                                         int *status) {
+  return guarded([&] {
+    require(ctx != nullptr, "context must not be NULL");
+    ScreenCartArgs a;
+    const Map m = make_cart_call(reference, reproduction, n, x, y, z, screen_ref, lock_horizontal, lock_vertical, x_out, y_out,
+                                 z_out, a);
+    if (n == 0) return;
+    ctx->use();
+    hipLaunchKernelGGL(k_screen_apply_cartesian, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m, a, status);
     EARHIP_HIP(hipGetLastError());
   });
 }

@@ -44,7 +44,7 @@ struct Sector {
    {30.0, 0.0, 45.0, -0.0, {-1.0, 1.0}, {0.0, 1.0}, {{-1.0, 1.0}, {0.0, 1.0}}}}
 
 constexpr int kNumSectors = 5;
-__constant__ Sector d_sectors[kNumSectors] = EARHIP_CONV_SECTORS;
+static __constant__ Sector d_sectors[kNumSectors] = EARHIP_CONV_SECTORS;  // (static: one per unit that includes this)
 static const Sector h_sectors[kNumSectors] = EARHIP_CONV_SECTORS;
 
 __host__ __device__ inline const Sector &sector(int i) {

@@ -1,5 +1,5 @@
-// ear/hip_allo_objects.hpp — the gain calculator for every Objects block with Cartesian positions (cartesian == 1) but
-// screenRef: the C++ face of group U of the C ABI (include/earhip.h, where the gains are specified, after ITU-R BS.2127-0
+// ear/hip_allo_objects.hpp — the gain calculator for every Objects block with Cartesian positions (cartesian == 1), behind
+// ear::hip::ScreenHandler::apply_cartesian where it has screenRef: the C++ face of group U of the C ABI (include/earhip.h, where the gains are specified, after ITU-R BS.2127-0
 // 7.3.6, 7.3.7, 7.3.10 and 7.3.11).  Beyond AllocentricGainCalculator (hip_allo.hpp), whose constructors and calculate /
 // calculate_device overloads it has, it takes width, height and depth, channelLock (flag and maxDistance) and
 // CartesianObjectDivergence.  libear carries only a stub of this panner, so there is no libear class this one mirrors.  It is
@@ -29,8 +29,8 @@ namespace ear {
         ear::detail::calculate_one(*this, allo_.layout, metadata, directGains, diffuseGains);
       }
       /// a batch of metadata blocks, on the calling thread.  Refused with not_implemented, the message naming the field: a
-      /// polar position or `cartesian == false`, a non-zero PolarObjectDivergence, screenRef (such a block still takes
-      /// ear::conversion and the polar calculators), a polar exclusion zone.
+      /// polar position or `cartesian == false`, a non-zero PolarObjectDivergence, screenRef (ear::hip::ScreenHandler::apply_cartesian comes first
+      /// and clears it), a polar exclusion zone.
       template <typename T>
       void calculate(const std::vector<ObjectsTypeMetadata> &metadata, std::vector<std::vector<T>> &directGains,
                      std::vector<std::vector<T>> &diffuseGains) const {
