@@ -1865,6 +1865,102 @@ int earhip_screen_apply_cartesian_device(earhip_ctx *ctx, const earhip_screen *r
                                          const unsigned char *lock_vertical, double *x_out, double *y_out, double *z_out,
                                          int *status);
 
+/* ------------------------------------------------------------------------
+ * (W) The block timeline: from the timing of a track's audioBlockFormats (rtime, duration, jumpPosition, interpolationLength)
+ * to the interpolation points of the renderer's curves (group F), the step between the gain producers (groups I, T, U, the
+ * DirectSpeakers and HOA calculators) and earhip_render_set_object_points.  libear has no counterpart: its ObjectsTypeMetadata
+ * carries no timing.  THIS COMMENT IS THE SPECIFICATION.  It follows the EBU ADM Renderer's reading of the block timing of
+ * ITU-R BS.2127-0's Objects renderer; NO REFERENCE IMPLEMENTATION OF IT WAS AVAILABLE TO CHECK AGAINST, so what the tests hold
+ * the code to is this comment, stated twice in exact arithmetic (tests/timeline_model.py: as a point list, and sample by sample).
+ *
+ * TIME.  Every time is a count of samples of the renderer's clock (earhip_render_reset).  Turning ADM time codes into samples
+ * is the caller's job; take ceil(t * fs) for EVERY block boundary (a start, an end, the end of a ramp), so that a block covers
+ * exactly the samples n with start <= n / fs < end, and two blocks that touch in time touch in samples.  `start` is the
+ * track's offset (the audioObject's start), of any sign; s_b = start + rtime_b and e_b = s_b + duration_b are block b's first
+ * sample and the first sample after it.  duration -1 is an open end (e_b is infinite), on the last block only.
+ *
+ * MODE.  EARHIP_TIMELINE_INTERPOLATED is the Objects rule: gains ramp from the previous block's.  EARHIP_TIMELINE_STEPPED is
+ * for DirectSpeakers, HOA and any bed: no ramps, and jump_position and interpolation_length are not read at all.
+ *
+ * THE RULE.  A point is (time, src), src a block index — its row of gains — or -1, the all-zero row.  emit(t, src) appends a
+ * point unless the last point has the same t and the same src.
+ *
+ *   prev = none
+ *   for b in blocks, in order:
+ *       if prev is none:   emit(s_b, -1); emit(s_b, b)               silence before; the first block is fixed from s_b on
+ *       else:
+ *           if s_b > e_prev:   emit(e_prev, -1); emit(s_b, -1)        a gap is silent
+ *           if INTERPOLATED:   L = jump_position ? max(interpolation_length, 0) : duration_b
+ *                              emit(s_b, prev); emit(s_b + L, b)      a ramp from the previous block's gains; L == 0 is a step
+ *           else:              emit(s_b, b)                           STEPPED
+ *       if duration_b != -1:   emit(e_b, b)
+ *       prev = b; e_prev = e_b
+ *   if the last duration != -1:   emit(e_prev, -1)                    silence after; an open end holds for ever
+ *
+ * The points have the semantics of GainInterpolator::interp_points (gain_interpolator.hpp:27-43): segment k covers the samples
+ * [t_k-1, t_k) and runs linearly from point k-1 to point k, two points at one time are a step, the first value holds before
+ * the first point and the last value after the last.  So:
+ *   - block b owns the samples [s_b, e_b), and every sample no block owns is exactly +0.0 (no ramp into the first block, none
+ *     out of the last, none across a gap: after a gap the ramp starts from the gains of the block before the gap);
+ *   - sample n of a ramp is G_prev + (n - s_b) / L * (G_b - G_prev) in the renderer's own arithmetic, G_b is reached at s_b + L
+ *     and held to e_b; without a jump the ramp takes the whole block and G_b itself is reached only at e_b, where the next
+ *     block starts from it;
+ *   - a list of n blocks makes at most 5 n + 1 points.
+ *
+ * REFUSALS, each EARHIP_INVALID_ARGUMENT with a message that names the block (the bulk setter: the track, then the block), and
+ * always made on the WHOLE list, whatever the window: rtime < 0; duration == 0 or < -1; duration == -1 on a block that is not
+ * the last; s_b < e_prev (blocks overlap or are out of order); an unknown mode; n_blocks < 1; a NULL blocks; and in
+ * INTERPOLATED mode jump_position other than 0 or 1, with a jump an interpolation_length < -1 or an L > duration_b, and an
+ * open-ended block that is not the first and has no jump (there is no duration to ramp over).  Also refused: start beyond
+ * +-2^61, an rtime, duration or interpolation_length above 2^61 (no sum here leaves int64_t), and t0 >= t1.
+ *
+ * WINDOWS.  A curve holds at most 2^18 - 1 points, so a long programme with dense metadata is bound by time window.  For the
+ * window [t0, t1) the selected blocks are [b0, b1]: b1 is the first block with e_b >= t1, or the last block if there is none;
+ * b0 is the last block with s_b <= t0, or block 0 if there is none, and then one block earlier if that exists (its row is where
+ * the ramp into the next block starts).  The rule runs on that sub-list as if it were the whole list; src keeps the indices
+ * of the whole list.  ON EVERY SAMPLE OF [t0, t1) THE WINDOWED CURVE EQUALS THE WHOLE-LIST CURVE; outside it does not (the
+ * sub-list's first block is not ramped into, and there is silence after its last).  t0 = INT64_MIN, t1 = INT64_MAX selects
+ * everything.  The loop for a long programme: bind [t, t + W), commit, render the calls that fall into it, advance t by W.
+ *
+ * earhip_timeline_window and earhip_timeline_points are pure host functions, no context and no device.  earhip_timeline_points
+ * writes at most `capacity` points and *n_points always; capacity == 0 only counts (times and source may then be NULL), any
+ * other capacity below the count is EARHIP_INVALID_ARGUMENT.
+ *
+ * THE SETTERS bind the curves of a renderer (group F) from blocks and one row of gains per block: direct and diffuse are
+ * [n_blocks][n_out] in BLOCK order, what the host form of a batch producer returns for the blocks in that order (the bulk form:
+ * for the concatenated blocks of all tracks, track k's being block_offsets[k] .. block_offsets[k + 1], block_offsets[0] == 0).
+ * Only rows of selected blocks are read: a caller may compute rows [first_block, last_block] of each track alone and leave
+ * the rest unwritten.  diffuse is ignored (may be NULL) when n_buses == 1.  Each object's point rows — a block's row where src
+ * is a block, +0.0 where it is -1 — are built in one buffer and go to the curve exactly as earhip_render_set_object_points
+ * puts them there; rendering from these curves is bit for bit rendering from the same points set by hand.  The bulk form
+ * checks every track before it changes any curve: a refused call leaves all curves as they were.  An object named twice gets
+ * its last track.  earhip_render_commit stays the caller's call.  More than 2^18 - 1 points for one object is refused as in
+ * earhip_render_set_object_points: bind a window instead.  As there, no segment may be longer than 2^31 - 1 samples: a block, a
+ * ramp or a gap that long is refused.
+ *
+ * Out of scope: time codes and fractions of samples, clipping to the audioObject's duration, object gain, mute and
+ * positionOffset (the caller scales rows), interpolating positions instead of gains, curves resident on the device.
+ * ---------------------------------------------------------------------- */
+typedef struct earhip_block_timing {
+  int64_t rtime;                /* samples from the track's start, >= 0 */
+  int64_t duration;             /* samples, >= 1; -1 = open end, allowed on the last block only */
+  int64_t interpolation_length; /* samples; read only when jump_position != 0; -1 = not given (means 0) */
+  int32_t jump_position;        /* 0 | 1 */
+} earhip_block_timing;
+
+enum { EARHIP_TIMELINE_INTERPOLATED = 0 /* Objects */, EARHIP_TIMELINE_STEPPED = 1 /* DirectSpeakers, HOA, any bed */ };
+
+int earhip_timeline_window(int mode, int64_t start, int n_blocks, const earhip_block_timing *blocks,
+                           int64_t t0, int64_t t1, int *first_block, int *last_block);
+int earhip_timeline_points(int mode, int64_t start, int n_blocks, const earhip_block_timing *blocks, int64_t t0, int64_t t1,
+                           int capacity, int64_t *times, int32_t *source, int *n_points);
+int earhip_render_set_object_blocks(earhip_render *r, int object, int mode, int64_t start, int n_blocks,
+                                    const earhip_block_timing *blocks, int64_t t0, int64_t t1,
+                                    const float *direct, const float *diffuse);
+int earhip_render_set_objects_blocks(earhip_render *r, int n_tracks, const int *objects, const int *modes, const int64_t *starts,
+                                     const int64_t *block_offsets, const earhip_block_timing *blocks,
+                                     int64_t t0, int64_t t1, const float *direct, const float *diffuse);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1203,6 +1203,52 @@ def pcm_format(fmt):
     return _PCM[name]
 
 
+# (W) the block timeline: audioBlockFormat timing -> the points of a renderer's curves (pure host functions)
+
+TIMELINE_INTERPOLATED, TIMELINE_STEPPED = 0, 1
+INT64_MIN, INT64_MAX = -2 ** 63, 2 ** 63 - 1
+# earhip_block_timing
+BLOCK_TIMING = np.dtype([("rtime", "<i8"), ("duration", "<i8"), ("interpolation_length", "<i8"), ("jump_position", "<i4")],
+                        align=True)
+
+
+def block_timings(blocks):
+    """an earhip_block_timing array: from one (an array of dtype BLOCK_TIMING, used as it is), or from a sequence of
+    (rtime, duration[, jump_position[, interpolation_length]]) in samples; duration -1 is an open end"""
+    if isinstance(blocks, np.ndarray) and blocks.dtype == BLOCK_TIMING:
+        return np.ascontiguousarray(blocks)
+    out = np.zeros(len(blocks), BLOCK_TIMING)
+    out["interpolation_length"] = -1
+    for i, b in enumerate(blocks):
+        out["rtime"][i], out["duration"][i] = b[0], b[1]
+        if len(b) > 2:
+            out["jump_position"][i] = b[2]
+        if len(b) > 3:
+            out["interpolation_length"][i] = b[3]
+    return out
+
+
+def timeline_window(mode, start, blocks, t0=INT64_MIN, t1=INT64_MAX):
+    """(first, last) block whose rows the curve of the window [t0, t1) uses (include/earhip.h: earhip_timeline_window)"""
+    b = block_timings(blocks)
+    first, last = C.c_int(0), C.c_int(0)
+    check(load().earhip_timeline_window(C.c_int(mode), C.c_int64(start), C.c_int(len(b)), C.c_void_p(b.ctypes.data),
+                                        C.c_int64(t0), C.c_int64(t1), C.byref(first), C.byref(last)))
+    return first.value, last.value
+
+
+def timeline_points(mode, start, blocks, t0=INT64_MIN, t1=INT64_MAX):
+    """(times int64 [n], source int32 [n]) of the window [t0, t1): source[k] is the block whose row of gains point k takes, -1
+    the zero row (include/earhip.h: earhip_timeline_points, called once to count and once to fill)"""
+    b = block_timings(blocks)
+    args = (C.c_int(mode), C.c_int64(start), C.c_int(len(b)), C.c_void_p(b.ctypes.data), C.c_int64(t0), C.c_int64(t1))
+    n = C.c_int(0)
+    check(load().earhip_timeline_points(*args, C.c_int(0), None, None, C.byref(n)))
+    times, source = np.empty(n.value, np.int64), np.empty(n.value, np.int32)
+    check(load().earhip_timeline_points(*args, n, C.c_void_p(times.ctypes.data), C.c_void_p(source.ctypes.data), C.byref(n)))
+    return times, source
+
+
 class Renderer:
     """(F) composed Objects render block."""
 
@@ -1230,6 +1276,33 @@ class Renderer:
         f = _f32(diffuse).reshape(len(t), self.N) if diffuse is not None else None
         check(load().earhip_render_set_object_points(self.h, obj, len(t), _ptr(t, i64p), _ptr(d),
                                                      _ptr(f) if f is not None else None))
+
+    def set_object_blocks(self, obj, mode, start, blocks, direct, diffuse=None, t0=INT64_MIN, t1=INT64_MAX):
+        """one object's curve from its blocks' timing and one row of gains per block, direct / diffuse [n_blocks][n_out] in
+        block order, for the window [t0, t1) (include/earhip.h group W: earhip_render_set_object_blocks)"""
+        b = block_timings(blocks)
+        d = _f32(direct).reshape(len(b), self.N)
+        f = _f32(diffuse).reshape(len(b), self.N) if diffuse is not None else None
+        check(load().earhip_render_set_object_blocks(self.h, C.c_int(obj), C.c_int(mode), C.c_int64(start), C.c_int(len(b)),
+                                                     C.c_void_p(b.ctypes.data), C.c_int64(t0), C.c_int64(t1), _ptr(d),
+                                                     _ptr(f) if f is not None else None))
+
+    def set_objects_blocks(self, objects, modes, starts, block_offsets, blocks, direct, diffuse=None, t0=INT64_MIN, t1=INT64_MAX):
+        """the curves of many objects in one call: track k is object objects[k] with blocks block_offsets[k] ..
+        block_offsets[k + 1] of `blocks`; direct / diffuse [total blocks][n_out], the rows of a batch producer for the
+        concatenated blocks.  Every track is checked before any curve changes (earhip_render_set_objects_blocks)."""
+        o = np.ascontiguousarray(objects, dtype=np.int32)
+        m = np.ascontiguousarray(modes, dtype=np.int32)
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        ofs = np.ascontiguousarray(block_offsets, dtype=np.int64)
+        assert len(m) == len(o) and len(s) == len(o) and len(ofs) == len(o) + 1
+        b = block_timings(blocks)
+        assert len(o) == 0 or ofs[-1] <= len(b), "block_offsets reach beyond the blocks"
+        d = _f32(direct).reshape(len(b), self.N)
+        f = _f32(diffuse).reshape(len(b), self.N) if diffuse is not None else None
+        check(load().earhip_render_set_objects_blocks(self.h, C.c_int(len(o)), C.c_void_p(o.ctypes.data), C.c_void_p(m.ctypes.data),
+                                                      _ptr(s, i64p), _ptr(ofs, i64p), C.c_void_p(b.ctypes.data), C.c_int64(t0),
+                                                      C.c_int64(t1), _ptr(d), _ptr(f) if f is not None else None))
 
     def commit(self):
         check(load().earhip_render_commit(self.h))

@@ -8,7 +8,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
+#include <functional>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "bus_stage.h"
@@ -16,6 +18,7 @@
 #include "decor_stage.h"
 #include "host_pipeline.h"
 #include "pcm_frames.h"
+#include "timeline.h"
 
 using namespace earhip;
 
@@ -483,6 +486,67 @@ int earhip_render_set_object_points(earhip_render *r, int object, int npoints,
     }
     r->curves->set_object(object, npoints, times, rows.data());
   });
+}
+
+// ---- the block timeline (include/earhip.h, group W; the rule, the windows and the row copies: timeline.h) -------------------
+static void timeline_guard(const std::function<void()> &f) {
+  try {
+    f();
+  } catch (const TimelineFailure &e) {
+    fail_invalid(e.msg);
+  }
+}
+
+int earhip_timeline_window(int mode, int64_t start, int n_blocks, const earhip_block_timing *blocks, int64_t t0, int64_t t1,
+                           int *first_block, int *last_block) {
+  return guarded([&] {
+    require(first_block != nullptr && last_block != nullptr, "first_block / last_block must not be NULL");
+    timeline_guard([&] {
+      timeline_check(mode, start, n_blocks, blocks);
+      timeline_window(start, n_blocks, blocks, t0, t1, first_block, last_block);
+    });
+  });
+}
+
+int earhip_timeline_points(int mode, int64_t start, int n_blocks, const earhip_block_timing *blocks, int64_t t0, int64_t t1,
+                           int capacity, int64_t *times, int32_t *source, int *n_points) {
+  return guarded([&] {
+    require(n_points != nullptr, "n_points must not be NULL");
+    require(capacity >= 0, "capacity must be >= 0");
+    require(capacity == 0 || (times != nullptr && source != nullptr), "times / source must not be NULL when capacity > 0");
+    timeline_guard([&] {
+      timeline_check(mode, start, n_blocks, blocks);
+      int b0, b1;
+      timeline_window(start, n_blocks, blocks, t0, t1, &b0, &b1);
+      const int64_t n = timeline_emit(mode, start, blocks, b0, b1, 0, nullptr, nullptr);
+      if (n > (int64_t)0x7fffffff) timeline_fail("more than 2^31 - 1 points: take a window");
+      *n_points = (int)n;
+      if (capacity == 0) return;
+      if (capacity < n) timeline_fail("capacity " + std::to_string(capacity) + " is too small for " + std::to_string(n) + " points");
+      timeline_emit(mode, start, blocks, b0, b1, n, times, source);
+    });
+  });
+}
+
+int earhip_render_set_objects_blocks(earhip_render *r, int n_tracks, const int *objects, const int *modes, const int64_t *starts,
+                                     const int64_t *block_offsets, const earhip_block_timing *blocks, int64_t t0, int64_t t1,
+                                     const float *direct, const float *diffuse) {
+  return guarded([&] {
+    require(r != nullptr, "render must not be NULL");
+    timeline_guard([&] {
+      timeline_bind(r->M, r->N, r->K, kMaxPointsPerObject, n_tracks, objects, modes, starts, block_offsets, blocks, t0, t1, direct,
+                    diffuse, [&](int object, int npoints, const int64_t *times, const float *rows) {
+                      r->curves->set_object(object, npoints, times, rows);
+                    });
+    });
+  });
+}
+
+int earhip_render_set_object_blocks(earhip_render *r, int object, int mode, int64_t start, int n_blocks,
+                                    const earhip_block_timing *blocks, int64_t t0, int64_t t1, const float *direct,
+                                    const float *diffuse) {
+  const int64_t offsets[2] = {0, n_blocks};
+  return earhip_render_set_objects_blocks(r, 1, &object, &mode, &start, offsets, blocks, t0, t1, direct, diffuse);
 }
 
 int earhip_render_commit(earhip_render *r) {

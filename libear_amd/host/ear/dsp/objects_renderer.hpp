@@ -10,6 +10,7 @@
 #include "../hip_firmix.hpp"
 #include "../hip_limiter.hpp"
 #include "../hip_loudness.hpp"
+#include "../hip_timeline.hpp"
 
 namespace ear {
   namespace dsp {
@@ -65,6 +66,53 @@ namespace ear {
         hip::check(earhip_render_set_object_points(h_, (int)object, (int)times.size(), times.data(),
                                                    d.data(), f.empty() ? nullptr : f.data()));
       }
+      /// Gain curve of one object from its blocks' timing and one gain vector per block (include/earhip.h group W, where the
+      /// rule is specified; ear/hip_timeline.hpp), for the time window [t0, t1): silence outside the blocks, no ramp into the
+      /// first, a ramp from the previous block's gains over the whole block or over interpolationLength after a jump.
+      void set_object_blocks(size_t object, hip::TimelineMode mode, int64_t start, const std::vector<hip::BlockTiming> &blocks,
+                             const std::vector<std::vector<float>> &direct, const std::vector<std::vector<float>> &diffuse,
+                             int64_t t0 = hip::kTimelineBegin, int64_t t1 = hip::kTimelineEnd) {
+        if (direct.size() != blocks.size()) throw invalid_argument("one direct gain vector per block");
+        if (two_buses_ ? diffuse.size() != blocks.size() : !diffuse.empty())
+          throw invalid_argument(two_buses_ ? "one diffuse gain vector per block"
+                                            : "diffuse gains given to a renderer without a diffuse bus");
+        std::vector<float> d, f;
+        for (auto &p : direct) {
+          if (p.size() != n_out_) throw invalid_argument("gain vector length != number of outputs");
+          d.insert(d.end(), p.begin(), p.end());
+        }
+        for (auto &p : diffuse) {
+          if (p.size() != n_out_) throw invalid_argument("gain vector length != number of outputs");
+          f.insert(f.end(), p.begin(), p.end());
+        }
+        const std::vector<earhip_block_timing> c = hip::detail::to_c(blocks);
+        hip::check(earhip_render_set_object_blocks(h_, (int)object, (int)mode, start, (int)c.size(), c.data(), t0, t1, d.data(),
+                                                   f.empty() ? nullptr : f.data()));
+      }
+      /// The curves of many objects in one call.  direct and diffuse: [blocks of all tracks, in order][n_out], the rows a gain
+      /// calculator's batch form returns for the concatenated blocks; only rows of blocks the window selects
+      /// (hip::timelineWindow) are read.  Every track is checked before any curve changes.  diffuse: ignored without a
+      /// diffuse bus.
+      void set_objects_blocks(const std::vector<hip::TimelineTrack> &tracks, const std::vector<float> &direct,
+                              const std::vector<float> &diffuse, int64_t t0 = hip::kTimelineBegin,
+                              int64_t t1 = hip::kTimelineEnd) {
+        std::vector<int> objects, modes;
+        std::vector<int64_t> starts, offsets(1, 0);
+        std::vector<earhip_block_timing> blocks;
+        for (auto &t : tracks) {
+          const std::vector<earhip_block_timing> c = hip::detail::to_c(t.blocks);
+          blocks.insert(blocks.end(), c.begin(), c.end());
+          objects.push_back((int)t.object), modes.push_back((int)t.mode), starts.push_back(t.start);
+          offsets.push_back((int64_t)blocks.size());
+        }
+        if (direct.size() != blocks.size() * n_out_) throw invalid_argument("one direct gain vector per block");
+        if (two_buses_ && diffuse.size() != direct.size()) throw invalid_argument("one diffuse gain vector per block");
+        hip::check(earhip_render_set_objects_blocks(h_, (int)tracks.size(), objects.data(), modes.data(), starts.data(),
+                                                    offsets.data(), blocks.data(), t0, t1, direct.data(),
+                                                    two_buses_ ? diffuse.data() : nullptr));
+      }
+      /// upload pending curve changes now (otherwise done by the next process call)
+      void commit() { hip::check(earhip_render_commit(h_)); }
       /// one block: in[n_objects][block_size] -> out[n_out][block_size] (ProcessFunc shape)
       void process(const float *const *in, float *const *out) {
         hip::check(earhip_render_process(h_, 1, in, out));
@@ -204,6 +252,7 @@ namespace ear {
       }
       void reset(int64_t sample_time = 0) { hip::check(earhip_render_reset(h_, sample_time)); }
       size_t block_size() const { return block_size_; }
+      size_t n_out() const { return n_out_; }
 
      private:
       static earhip_pcm_format pcm_format_of(const int16_t *) { return EARHIP_PCM_S16; }
