@@ -18,6 +18,7 @@
 #include "decor_stage.h"
 #include "host_pipeline.h"
 #include "pcm_frames.h"
+#include "stream_pipe.h"
 #include "timeline.h"
 
 using namespace earhip;
@@ -645,14 +646,14 @@ int earhip_render_process(earhip_render *r, size_t nblocks, const float *const *
       // device-reachable rows (earhip_host_alloc / _register) go by strided DMA both ways, without either copy.
       // (the plan, the same for earhip_render_process_frames: host_gather.h, plan_host_chunks)
       const HostChunkPlan plan = r->host_plan(nblocks, in_st != 0);
-      r->pipe.make();
+      r->pipe.begin(ctx->stream);
       GatherPool *gp = nullptr;
       if (!in_st) {
         gp = &r->staging_threads();
         gp->submit(in, r->p_in.p, n, plan.cstart, plan.nch, r->M, ctx->get(OPT_HOST_BIND, 0) != 0, ctx->get(OPT_HOST_NT, 1) != 0);
       }
       const HostChunkTimes tm = run_host_chunks(
-          r->pipe, gp, plan, ctx->stream, !out_st, &r->last_host_chunks,
+          r->pipe, gp, plan, !out_st, &r->last_host_chunks,
           [&](size_t at, size_t len) {
             float *din = r->d_in.p + (size_t)r->M * at;
             if (in_st)
@@ -784,7 +785,7 @@ static void process_frames_host(earhip_render *r, size_t nblocks, const void *fr
   // Long calls: the pipeline of earhip_render_process, on the packed bytes.  A chunk is one contiguous byte range of the caller's
   // buffer, staged into the pinned buffer at the same offset by the staging threads (pageable frames) or not at all; its kernels
   // are the conversion into the chunk's rows of d_in, then the chunk's render as an ordinary process call.
-  r->pipe.make();
+  r->pipe.begin(ctx->stream);
   GatherPool *gp = nullptr;
   if (!direct) {
     gp = &r->staging_threads();
@@ -792,7 +793,7 @@ static void process_frames_host(earhip_render *r, size_t nblocks, const void *fr
     src = r->p_bytes.p;
   }
   run_host_chunks(
-      r->pipe, gp, plan, ctx->stream, !out_direct, &r->last_host_chunks,
+      r->pipe, gp, plan, !out_direct, &r->last_host_chunks,
       [&](size_t at, size_t len) {
         return hipMemcpyAsync(r->d_bytes.p + at * fb, src + at * fb, len * fb, hipMemcpyHostToDevice, r->pipe.in);
       },

@@ -1,5 +1,6 @@
-// common.h — shared host-side plumbing of libearhip: status codes, the
-// thread-local error string, the context object and HIP error checks.
+// common.h — shared host-side plumbing of libearhip: the context object, HIP error
+// checks and the owning device / pinned buffers.  Status codes, the thread-local error
+// string and the exception behind them: errors.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,43 +11,9 @@
 #include <vector>
 
 #include "../../include/earhip.h"
+#include "errors.h"
 
 namespace earhip {
-
-struct Error {
-  int code;
-  std::string msg;
-};
-
-void set_last_error(const std::string &msg);
-
-// Runs f, translating earhip::Error / std::exception into a status code.
-template <typename F>
-int guarded(F &&f) {
-  try {
-    f();
-    return EARHIP_OK;
-  } catch (const Error &e) {
-    set_last_error(e.msg);
-    return e.code;
-  } catch (const std::bad_alloc &) {
-    set_last_error("out of host memory");
-    return EARHIP_INTERNAL_ERROR;
-  } catch (const std::exception &e) {
-    set_last_error(e.what());
-    return EARHIP_INTERNAL_ERROR;
-  }
-}
-
-[[noreturn]] inline void fail_invalid(const std::string &m) {
-  throw Error{EARHIP_INVALID_ARGUMENT, m};
-}
-[[noreturn]] inline void fail_internal(const std::string &m) {
-  throw Error{EARHIP_INTERNAL_ERROR, "internal error: " + m};
-}
-inline void require(bool ok, const char *m) {
-  if (!ok) fail_invalid(m);
-}
 
 #define EARHIP_HIP(expr)                                                        \
   do {                                                                          \

@@ -1,16 +1,20 @@
 // host_pipeline.h — the chunked pipeline of long calls from host memory (earhip_render_process, _process_frames and _frames_pcm:
-// api_render.hip): the staging threads, the copy streams and events, and the ONE loop that runs a call's time chunks through
-// them; a chunk's transfers and kernels are the caller's callables.  The plan and the copies the threads make: host_gather.h.
+// api_render.hip): the staging threads and the ONE loop that runs a call's time chunks through three lanes of the device; a
+// chunk's transfers and kernels are the caller's callables, the lanes a type of the caller's (the copy streams and events:
+// stream_pipe.h).  The plan and the copies the threads make: host_gather.h.  Plain C++17 and threads, no device interface: a
+// stand-alone program drives this pool and this loop against lanes made of threads, under the thread and address sanitizers
+// (tests/cpp/test_host_pipeline.cpp).
 #pragma once
 
 #include <atomic>
 #include <condition_variable>
+#include <exception>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "common.h"
+#include "errors.h"
 #include "host_gather.h"
 
 namespace earhip {
@@ -135,94 +139,76 @@ struct GatherPool {
   }
 };
 
-// Copy streams and events of long host-pointer calls (made at the first such call and kept): the chunks of a call go
-// H2D on `in`, through the kernels on the context's stream, and D2H on `out`, each stage ordered behind the one
-// before it by the chunk's events — chunk c's kernels and the transfer of its outputs run beside the transfer of c + 1.
-struct StreamPipe {
-  hipStream_t in = nullptr, out = nullptr;
-  hipEvent_t ev_in[GatherPool::kMaxGroups], ev_k[GatherPool::kMaxGroups], ev_out[GatherPool::kMaxGroups];
-  bool made = false;
-  void make() {
-    if (made) return;
-    EARHIP_HIP(hipStreamCreateWithFlags(&in, hipStreamNonBlocking));
-    EARHIP_HIP(hipStreamCreateWithFlags(&out, hipStreamNonBlocking));
-    for (int i = 0; i < GatherPool::kMaxGroups; i++) {
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_in[i], hipEventDisableTiming));
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_k[i], hipEventDisableTiming));
-      EARHIP_HIP(hipEventCreateWithFlags(&ev_out[i], hipEventDisableTiming));
-    }
-    made = true;
-  }
-  ~StreamPipe() {
-    if (!made) return;
-    for (int i = 0; i < GatherPool::kMaxGroups; i++) {
-      (void)hipEventDestroy(ev_in[i]);
-      (void)hipEventDestroy(ev_k[i]);
-      (void)hipEventDestroy(ev_out[i]);
-    }
-    (void)hipStreamDestroy(in);
-    (void)hipStreamDestroy(out);
-  }
-};
-
 struct HostChunkTimes { double enqueued = 0.0, drained = 0.0; };  // the last chunk enqueued, the gather through / all of it drained
 
-// The chunks of `plan` — chunk c = samples [at, at + len) of every channel — through three stages on three streams: H2D of chunk
-// c + 1 (pipe.in) beside the kernels of chunk c (`stream`, the context's) beside the D2H of chunk c - 1 (pipe.out), one event
-// per stage and chunk.  gather: the staging threads, their job submitted (a chunk is enqueued once they have gathered it), or
-// nullptr.  h2d / d2h (at, len) enqueue a chunk's transfer and return HIP's status; kernels(at, len) may throw Error.
-// staged_out: outputs return through pinned staging and scatter(at, len) hands a landed chunk to the caller, while the call waits
-// for the gather and at the end — only chunks whose output transfer THIS call recorded (an event of an earlier call says nothing
-// about this one), and none once anything has failed.  After a failure nothing more is enqueued, the staging threads still
-// finish their job and everything queued is waited for; then the first HIP error or the caught Error's message is raised.
+// The chunks of `plan` — chunk c = samples [at, at + len) of every channel — through three stages on three lanes of the device,
+// each a queue that runs what it is given in order: the transfer in of chunk c + 1 (the in lane) beside the kernels of chunk c (the
+// compute lane) beside the transfer out of chunk c - 1 (the out lane), one mark per stage and chunk.  `lanes` orders them, and is
+// all this loop knows of the device (StreamPipe, stream_pipe.h: streams and events; the CPU test: threads):
+//   Status in_done(c)       chunk c's input transfer is queued: mark it on the in lane, and the compute lane waits for the mark
+//   Status kernels_done(c)  mark on the compute lane, and the out lane waits for it
+//   Status out_done(c)      mark on the out lane
+//   bool out_landed(c)      has the mark of out_done(c) been reached (never blocks; a mark keeps its state from call to call)
+//   void drain()            waits for the in, compute and out lanes, in that order; never throws
+//   void raise(Status)      throws Error for a status that is not success
+// Status is the lanes' own type, a default-constructed one means success.  gather: the staging threads, their job submitted (a
+// chunk is enqueued once they have gathered it), or nullptr.  h2d / d2h (at, len) enqueue a chunk's transfer on the in / out lane
+// and return a Status; kernels(at, len) enqueues on the compute lane and may throw.  staged_out: outputs return through pinned
+// staging and scatter(at, len) hands a landed chunk to the caller, while the call waits for the gather and at the end — only chunks
+// whose output transfer THIS call marked (a mark of an earlier call says nothing about this one), and none once anything has failed.
+// NO EXCEPTION LEAVES A CALL MID-FLIGHT: whatever kernels throws is caught here, and after that, or after a Status that is not
+// success, nothing more is enqueued, the staging threads still finish their job and the lanes are drained; only then is the first
+// bad Status raised, or Error{EARHIP_INTERNAL_ERROR, the message thrown} (an Error's msg, a std::exception's what(); out of memory
+// reads as it does at the C boundary).  When the call returns or throws, nothing reads or writes the caller's or the staging buffers.
 // now(): the caller's clock for the two times returned; *chunks_run = the number of chunks, on success.
-template <typename H2D, typename Kernels, typename D2H, typename Scatter, typename Clock>
-HostChunkTimes run_host_chunks(StreamPipe &pipe, GatherPool *gather, const HostChunkPlan &plan, hipStream_t stream, bool staged_out,
-                               int *chunks_run, H2D h2d, Kernels kernels, D2H d2h, Scatter scatter, Clock now) {
+template <typename Lanes, typename H2D, typename Kernels, typename D2H, typename Scatter, typename Clock>
+HostChunkTimes run_host_chunks(Lanes &lanes, GatherPool *gather, const HostChunkPlan &plan, bool staged_out, int *chunks_run, H2D h2d,
+                               Kernels kernels, D2H d2h, Scatter scatter, Clock now) {
+  using Status = decltype(lanes.in_done(0));
   const int nch = plan.nch;
   const size_t *at = plan.cstart;
   const auto len = [at](int c) { return at[c + 1] - at[c]; };
-  hipError_t err = hipSuccess;
+  Status err = Status();
+  bool thrown = false;
   std::string fail;
-  int recorded = 0;   // chunks whose output transfer this call has queued (ev_out[c] recorded)
+  const auto ok = [&] { return err == Status() && !thrown; };
+  int recorded = 0;   // chunks whose output transfer this call has queued and marked
   int scattered = 0;  // ... whose outputs have been handed to the caller
   for (int c = 0; c < nch; c++) {
     if (gather) {
       while (gather->done[c].load(std::memory_order_acquire) < gather->nthreads()) {
-        if (staged_out && scattered < recorded && err == hipSuccess && fail.empty() &&
-            hipEventQuery(pipe.ev_out[scattered]) == hipSuccess)
+        if (staged_out && scattered < recorded && ok() && lanes.out_landed(scattered))
           scatter(at[scattered], len(scattered)), scattered++;
         else
           std::this_thread::yield();
       }
     }
-    if (err != hipSuccess || !fail.empty()) continue;  // (the staging threads still finish their job)
+    if (!ok()) continue;  // (the staging threads still finish their job)
     err = h2d(at[c], len(c));
-    if (err == hipSuccess) err = hipEventRecord(pipe.ev_in[c], pipe.in);
-    if (err == hipSuccess) err = hipStreamWaitEvent(stream, pipe.ev_in[c], 0);
-    if (err != hipSuccess) continue;
+    if (ok()) err = lanes.in_done(c);
+    if (!ok()) continue;
     try {
       kernels(at[c], len(c));
     } catch (const Error &e) {
-      fail = e.msg;
-      continue;
+      thrown = true, fail = e.msg;
+    } catch (const std::bad_alloc &) {
+      thrown = true, fail = "out of host memory";
+    } catch (const std::exception &e) {
+      thrown = true, fail = e.what();
+    } catch (...) {
+      thrown = true, fail = "unknown exception";
     }
-    err = hipEventRecord(pipe.ev_k[c], stream);
-    if (err == hipSuccess) err = hipStreamWaitEvent(pipe.out, pipe.ev_k[c], 0);
-    if (err != hipSuccess) continue;
-    err = d2h(at[c], len(c));
-    if (err == hipSuccess) err = hipEventRecord(pipe.ev_out[c], pipe.out);
-    if (err == hipSuccess) recorded = c + 1;
+    if (ok()) err = lanes.kernels_done(c);
+    if (ok()) err = d2h(at[c], len(c));
+    if (ok()) err = lanes.out_done(c);
+    if (ok()) recorded = c + 1;
   }
   if (gather) gather->wait_all();
   HostChunkTimes times;
   times.enqueued = now();
-  // (everything queued is waited for whatever happened above: nothing of this call is in flight when it returns)
-  (void)hipStreamSynchronize(pipe.in);
-  (void)hipStreamSynchronize(stream);
-  (void)hipStreamSynchronize(pipe.out);
-  EARHIP_HIP(err);
-  if (!fail.empty()) throw Error{EARHIP_INTERNAL_ERROR, fail};
+  lanes.drain();  // (whatever happened above: nothing of this call is in flight when it returns)
+  lanes.raise(err);
+  if (thrown) throw Error{EARHIP_INTERNAL_ERROR, fail};
   times.drained = now();
   if (staged_out)
     for (; scattered < nch; scattered++) scatter(at[scattered], len(scattered));
