@@ -521,7 +521,7 @@ int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int 
  * ear::GainCalculatorDirectSpeakers (include/ear/gain_calculators.hpp:18-35,
  * src/direct_speakers/gain_calculator_direct_speakers.cpp:58-320).  Per channel, in libear's order:
  *   1. audioPackFormatID without speakerLabels: EARHIP_ADM_ERROR (:247-250); a Cartesian position:
- *      EARHIP_NOT_IMPLEMENTED (:253);
+ *      EARHIP_NOT_IMPLEMENTED (:253; group X serves it);
  *   2. LFE or not: lowPass <= 200 Hz without highPass, or a nominal label LFE1 / LFE2; the warnings
  *      FREQ_NOT_LFE and FREQ_SPEAKERLABEL_LFE_MISMATCH (:111-137);
  *   3. nominal label: the capture of ^urn:itu:bs:2051:[0-9]+:speaker:(.*)$ or the label itself, replaced
@@ -529,7 +529,7 @@ int earhip_hoa_decode_matrix_positions(earhip_ctx *ctx, const char *layout, int 
  *      the caller's, which do not override these (:80-83, :139-150);
  *   4. the first label naming a layout channel of the same LFE type gets gain 1 (:280-291);
  *   5. a screenEdgeLock is EARHIP_NOT_IMPLEMENTED from here on, as in libear (:293,
- *      src/common/screen_edge_lock.hpp:15-17); else the one channel of the same LFE type whose NOMINAL
+ *      src/common/screen_edge_lock.hpp:15-17; group X serves it); else the one channel of the same LFE type whose NOMINAL
  *      position lies within the position's bounds (tolerance 1e-5), or the nearest of several when it is
  *      more than 1e-5 nearer than the next (distances to the REAL positions) gets gain 1 (:152-242);
  *   6. else an LFE channel goes to LFE1 (silence without one), anything else through the layout's point
@@ -1557,7 +1557,7 @@ int earhip_hoa_rotation_matrix(int n_coef, const int *orders, const int *degrees
  * but the exact fmod and its only contraction is explicit (one shared core, csrc/screen.h), so THE DEVICE FORM RETURNS THE HOST
  * FORM'S BITS.
  *
- * Out of scope: screenRef for HOA, screenEdgeLock for DirectSpeakers (still refused), a reproduction screen on a layout,
+ * Out of scope: screenRef for HOA, a reproduction screen on a layout,
  * fusing the stage into the producer's kernels.
  * ---------------------------------------------------------------------- */
 typedef struct earhip_screen {
@@ -1852,7 +1852,7 @@ int earhip_allo_calculate_objects_device(earhip_ctx *ctx, const earhip_allo *a, 
  * earhip_conversion_to_cartesian CHAINED, AND THE DEVICE FORM THE BITS OF THEIR THREE DEVICE FORMS CHAINED.  Device against host
  * differs by what group K's libm calls differ on the two sides, nothing more.
  *
- * Out of scope: screen stages for HOA and DirectSpeakers, scaling of extent, fusing the stage into the kernels of groups T and
+ * Out of scope: a screen stage for HOA, scaling of extent, fusing the stage into the kernels of groups T and
  * U, a polar-out form.
  * ---------------------------------------------------------------------- */
 int earhip_screen_apply_cartesian(const earhip_screen *reference, const earhip_screen *reproduction, size_t n, const double *x,
@@ -1960,6 +1960,94 @@ int earhip_render_set_object_blocks(earhip_render *r, int object, int mode, int6
 int earhip_render_set_objects_blocks(earhip_render *r, int n_tracks, const int *objects, const int *modes, const int64_t *starts,
                                      const int64_t *block_offsets, const earhip_block_timing *blocks,
                                      int64_t t0, int64_t t1, const float *direct, const float *diffuse);
+
+/* ------------------------------------------------------------------------
+ * (X) DirectSpeakers with a CARTESIAN position or a screenEdgeLock: the two cases of ITU-R BS.2127-0 section 8 that the
+ * calculator of group I (DirectSpeakers) refuses, as libear does, on that calculator's handle.  A file whose Objects are
+ * Cartesian carries its bed the same way — channels with a CartesianSpeakerPosition, RC_L at (-1, 1, 0), RC_Lss at (-1, 0, 0),
+ * RC_LFE with a lowPass, labels that are no BS.2051 labels — and with this group such a bed is placed by the library beside
+ * the objects of groups T, U and V.  libear has no counterpart (it refuses both).  THIS COMMENT IS THE SPECIFICATION.  The lock
+ * is BS.2127-0 7.3.4 as groups R and V state it.  THE CARTESIAN BOUNDS TEST AND THE FALL-THROUGH BY SECTION 10'S POINT
+ * CONVERSION ARE THIS PROJECT'S READING of section 8, which words both for polar positions; no reference implementation of
+ * either was available to check against, so what the tests hold the code to is this comment (tests/ds_cart_model.py).
+ *
+ * earhip_direct_speakers_calculate itself is unchanged: it still refuses both cases.
+ *
+ * INPUT.  md[i] is group I's earhip_ds_metadata.  Where md[i].cartesian is nonzero the position and its bounds are cart[i]
+ * (x, y, z; a bound whose has_* flag is 0 is absent) and the polar fields of md[i] are not read; elsewhere cart[i] is not
+ * read.  cart may be NULL when no md[i].cartesian is set.  In this entry point screen_edge_lock_horizontal / _vertical are
+ * group R's lock CODES: horizontal 0 none, 1 left, 2 right; vertical 0 none, 1 bottom, 2 top.  reproduction is the
+ * reproduction screen (group R's earhip_screen, checked as earhip_screen_edges checks it, whatever n is); NULL: no screen.
+ * The reference screen of a lock is the default screen; a lock reads only the reproduction screen's edges.
+ *
+ * PER CHANNEL, in the order of group I.  A Cartesian element with cart == NULL is refused before anything else.
+ *   1-4. Group I's steps 1 to 4 as they stand — the ADM check, the LFE decision and its two warnings, the refusal of
+ *        AP_0001xxxx packs, nominal labels, the first label naming a layout channel of the same LFE type gets gain 1 — except
+ *        that a Cartesian position is not refused.  A channel placed by a label never has its position, bounds or lock codes
+ *        looked at.
+ *   5a.  LOCK, in place of group I's refusal.  First the checks: a lock code above 2 is refused whatever the screen; a
+ *        Cartesian element whose x, y or z is not finite, or which has a present bound that is not finite, is refused.  Then:
+ *        - no reproduction screen: the position is unchanged;
+ *        - polar: (azimuth, elevation) become what earhip_screen_apply gives for this element with screen_ref 0 and the two
+ *          codes (csrc/screen.h on the map of the default screen's edges to the reproduction screen's, so the bits are group
+ *          R's).  With no code set the position keeps its bits and is not checked.  With one set group R's checks apply: a
+ *          non-finite azimuth or elevation, |azimuth| > 2^40 or |elevation| > 90 is refused.  The distance is untouched;
+ *        - Cartesian: (x, y, z) become what earhip_screen_apply_cartesian gives for this element with screen_ref 0 and the
+ *          two codes (csrc/screen_cart.h: to polar by group K's point conversion, the lock, back).  With no code set the
+ *          position keeps its bits.  A code a conversion returns refuses the element.
+ *        Bounds that are present stay as given; an absent bound is the position's value AFTER the lock.
+ *   5b.  BOUNDS, polar: group I's step 5 on the locked position (nominal positions within the bounds, tolerance 1e-5, the pole
+ *        clause; the nearest of several by the real positions).
+ *        BOUNDS, Cartesian.  Loudspeaker c of the full layout stands at q_c = P(nominal azimuth, nominal elevation, 1) and
+ *        its real position at r_c = P(real azimuth, real elevation, 1), P being group K's point conversion from polar to
+ *        Cartesian (csrc/conversion.h; BS.2127-0 section 10).  Both tables are computed once at create, for BS.2051 layouts and
+ *        defined layouts (group H) alike; no allocentric table (group T) enters, so a layout of the caller's own works.  In
+ *        0+5+0 M+030 stands at (-1, 1, 0), M-030 at (1, 1, 0), M+110 at (-1, -1, 0), M-110 at (1, -1, 0), M+000 at (0, 1, 0).
+ *        earhip_direct_speakers_cartesian_positions returns both tables, [n_channels][3] each.  c is a CANDIDATE when it has
+ *        the channel's LFE type and
+ *            q_c.x > x_min - 1e-5 && q_c.x < x_max + 1e-5,   and the same for y and z
+ *        (double arithmetic as written; there is no pole clause).  One candidate gets gain 1.  Of several, with d_c the
+ *        Euclidean distance sqrt((r_c.x - x)^2 + (r_c.y - y)^2 + (r_c.z - z)^2) from the locked position to r_c, the candidate
+ *        of the smallest d_c gets gain 1 when |d_best - d_second| > 1e-5, d_second being the next smallest (equal to d_best
+ *        when two candidates tie).  Otherwise, and with no candidate, the channel goes to step 6.
+ *   6.   FALL-THROUGH.  An LFE channel goes to LFE1, or to silence in a layout without one.  Any other polar channel goes to
+ *        the layout's point source panner at its locked (azimuth, elevation); any other Cartesian channel at the (azimuth,
+ *        elevation) of group K's point conversion of the locked (x, y, z) to polar, which takes the origin (|x|, |y|, |z| all
+ *        below 1e-10) to (0, 0, 0): panned straight ahead.  Every channel of the batch that reaches the panner, polar or
+ *        Cartesian, goes to the device in the SAME single launch (real positions; LFE columns zero).
+ *
+ * REFUSALS.  EARHIP_INVALID_ARGUMENT, the message starting "metadata[i]: " when n > 1: cart == NULL with a Cartesian element;
+ * a non-finite x, y, z or present bound; a lock code above 2; a polar position group R refuses under a lock; a conversion
+ * that does not return EARHIP_OK (the message gives its code), which includes a calculator created with a loudspeaker
+ * position group K's conversion refuses (|azimuth| > 2^40: every Cartesian element that reaches step 5a is then refused, and
+ * so is earhip_direct_speakers_cartesian_positions; labelled and polar channels are served as ever); a Cartesian channel
+ * whose conversion to polar gives an azimuth or elevation that is not finite (a guard in front of the launch: every finite
+ * position tried, up to the largest double, converts to a finite direction and is panned); a handle created with ctx == NULL and a non-LFE channel that
+ * reaches the panner.  EARHIP_ADM_ERROR and EARHIP_NOT_IMPLEMENTED (AP_0001xxxx) are group I's.  warnings_out is group I's:
+ * [n][2], and on an error the rows up to and including the failing channel hold what was raised before it.
+ *
+ * PROMISES.  A batch with no Cartesian element and no lock code returns the bits of earhip_direct_speakers_calculate, gains
+ * and warnings, its status and message on an error too, with or without a screen.  A batch equals its channels computed one
+ * at a time.  Without a reproduction screen a lock code (0, 1 or 2) changes nothing.
+ *
+ * The work is host logic over a few dozen loudspeakers plus group I's panner launch: there is no new kernel, and no rate was
+ * measured.  Out of scope: the common-definitions mapping rules (as in group I), a reference screen other than the default.
+ * ---------------------------------------------------------------------- */
+/* the Cartesian position of one channel; read only where md[i].cartesian != 0 */
+typedef struct earhip_ds_cartesian {
+  double x, y, z;
+  int has_x_min, has_x_max, has_y_min, has_y_max, has_z_min, has_z_max;
+  double x_min, x_max, y_min, y_max, z_min, z_max;
+} earhip_ds_cartesian;
+
+int earhip_direct_speakers_calculate_screen(earhip_direct_speakers *ds,
+                                            const earhip_screen *reproduction, /* NULL: no screen, locks are the identity */
+                                            size_t n, const earhip_ds_metadata *md,
+                                            const earhip_ds_cartesian *cart,   /* [n], or NULL when no md[i].cartesian is set */
+                                            float *gains, int *warnings_out);
+
+/* the loudspeakers as the Cartesian bounds test and the nearest-candidate rule see them: [n_channels][3] each */
+int earhip_direct_speakers_cartesian_positions(const earhip_direct_speakers *ds, double *nominal_xyz, double *real_xyz);
 
 #ifdef __cplusplus
 }

@@ -665,6 +665,13 @@ class DSMetadata(C.Structure):
                  ("high_pass", C.c_double), ("audio_pack_format_id", C.c_char_p)]
 
 
+class DSCartesian(C.Structure):
+    """earhip_ds_cartesian: the Cartesian position of one DirectSpeakers channel (group X)"""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
+    _fields_ += [("has_" + k, C.c_int) for k in ("x_min", "x_max", "y_min", "y_max", "z_min", "z_max")]
+    _fields_ += [(k, C.c_double) for k in ("x_min", "x_max", "y_min", "y_max", "z_min", "z_max")]
+
+
 BOUNDS = ("azimuth_min", "azimuth_max", "elevation_min", "elevation_max", "distance_min", "distance_max")
 
 # Warning::Code values (libear_amd/host/ear/warnings.hpp)
@@ -739,6 +746,53 @@ class DirectSpeakers:
         check(load().earhip_direct_speakers_calculate(self.h, C.c_size_t(n), md, _ptr(gains),
                                                       _ptr(warnings, C.POINTER(C.c_int))))
         return gains, warnings
+
+    _CART_KEYS = {"XMin": "x_min", "XMax": "x_max", "YMin": "y_min", "YMax": "y_max", "ZMin": "z_min", "ZMax": "z_max"}
+    _LOCK_CODES = ({None: 0, "left": 1, "right": 2}, {None: 0, "bottom": 1, "top": 2})
+
+    def calculate_screen(self, metadata, reproduction=None):
+        """(X) calculate for beds with Cartesian positions and screenEdgeLock.  The same dicts, plus X, Y, Z (the presence of
+        X makes the position Cartesian; Y defaults to 1, Z to 0) with XMin ... ZMax; screenEdgeLock {"horizontal": "left" |
+        "right", "vertical": "bottom" | "top"} (or group R's codes 0, 1, 2) locks the position to an edge of `reproduction`
+        (a Screen; None: no screen, a lock changes nothing).  -> (gains, warnings) as calculate"""
+        n = len(metadata)
+        keep = []
+        md = (DSMetadata * max(n, 1))()
+        cart = (DSCartesian * max(n, 1))()
+        for i, m in enumerate(metadata):
+            md[i] = self._struct(m, keep)
+            sel = m.get("screenEdgeLock") or {}
+            for field, key, codes in zip(("screen_edge_lock_horizontal", "screen_edge_lock_vertical"),
+                                         ("horizontal", "vertical"), self._LOCK_CODES):
+                v = sel.get(key)
+                if isinstance(v, (int, np.integer)):
+                    code = int(v)
+                elif v in codes:
+                    code = codes[v]
+                else:
+                    raise InvalidArgument(1, f"metadata[{i}]: invalid {key} screenEdgeLock: {v!r}")
+                setattr(md[i], field, code)
+            if m.get("X") is not None or m.get("cartesian"):
+                md[i].cartesian = 1
+                cart[i].x, cart[i].y, cart[i].z = m.get("X", 0.0), m.get("Y", 1.0), m.get("Z", 0.0)
+                for k, f in self._CART_KEYS.items():
+                    if m.get(k) is not None:
+                        setattr(cart[i], "has_" + f, 1)
+                        setattr(cart[i], f, m[k])
+        gains = np.zeros((n, self.n_out), np.float32)
+        warnings = np.zeros((n, 2), np.int32)
+        self.last_warnings = warnings
+        check(load().earhip_direct_speakers_calculate_screen(self.h, _screen_ref(reproduction), C.c_size_t(n), md, cart,
+                                                             _ptr(gains), _ptr(warnings, C.POINTER(C.c_int))))
+        return gains, warnings
+
+    def cartesian_positions(self):
+        """(X) -> (nominal, real) float64 [n_out][3]: the loudspeakers as the Cartesian bounds test and the nearest-candidate
+        rule see them, group K's point conversion of the nominal and of the real positions at distance 1"""
+        f64 = C.POINTER(C.c_double)
+        nominal, real = np.empty((self.n_out, 3), np.float64), np.empty((self.n_out, 3), np.float64)
+        check(load().earhip_direct_speakers_cartesian_positions(self.h, _ptr(nominal, f64), _ptr(real, f64)))
+        return nominal, real
 
     def missed(self):
         """channels of the last calculate that no region of the point source panner took"""

@@ -6,3 +6,4 @@
 #include "warnings.hpp"
 #include "decorrelate.hpp"
 #include "gain_calculators.hpp"
+#include "hip_direct_speakers.hpp"  // (ear::hip::DirectSpeakersGainCalculator: the positions and locks libear refuses)

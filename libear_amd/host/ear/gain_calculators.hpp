@@ -103,43 +103,11 @@ namespace ear {
     void calculate(const std::vector<DirectSpeakersTypeMetadata> &metadata, std::vector<std::vector<T>> &gains,
                    const WarningCB &warning_cb = default_warning_cb) {
       const size_t n = metadata.size();
-      std::vector<earhip_ds_metadata> md(n);
-      std::vector<std::vector<const char *>> labels(n);
-      for (size_t i = 0; i < n; i++) {
-        const DirectSpeakersTypeMetadata &m = metadata[i];
-        earhip_ds_metadata &c = md[i];
-        c = earhip_ds_metadata();
-        for (auto &l : m.speakerLabels) labels[i].push_back(l.c_str());
-        c.n_labels = (int)labels[i].size();
-        c.labels = labels[i].data();
-        c.cartesian = m.position.isCartesian;
-        const PolarSpeakerPosition &p = m.position.polar;
-        c.azimuth = p.azimuth, c.elevation = p.elevation, c.distance = p.distance;
-        c.has_azimuth_min = (bool)p.azimuthMin, c.azimuth_min = p.azimuthMin.value_or(0.0);
-        c.has_azimuth_max = (bool)p.azimuthMax, c.azimuth_max = p.azimuthMax.value_or(0.0);
-        c.has_elevation_min = (bool)p.elevationMin, c.elevation_min = p.elevationMin.value_or(0.0);
-        c.has_elevation_max = (bool)p.elevationMax, c.elevation_max = p.elevationMax.value_or(0.0);
-        c.has_distance_min = (bool)p.distanceMin, c.distance_min = p.distanceMin.value_or(0.0);
-        c.has_distance_max = (bool)p.distanceMax, c.distance_max = p.distanceMax.value_or(0.0);
-        c.screen_edge_lock_horizontal = (bool)p.screenEdgeLock.horizontal;
-        c.screen_edge_lock_vertical = (bool)p.screenEdgeLock.vertical;
-        c.has_low_pass = (bool)m.channelFrequency.lowPass, c.low_pass = m.channelFrequency.lowPass.value_or(0.0);
-        c.has_high_pass = (bool)m.channelFrequency.highPass, c.high_pass = m.channelFrequency.highPass.value_or(0.0);
-        c.audio_pack_format_id = m.audioPackFormatID ? m.audioPackFormatID.get().c_str() : nullptr;
-      }
+      const detail::DirectSpeakersRows rows(metadata);
       std::vector<float> g(n * layout_.n_full);
       std::vector<int> warnings(2 * n, 0);
-      const int status = earhip_direct_speakers_calculate(h_, n, md.data(), g.data(), warnings.data());
-      const std::string error = status == EARHIP_OK ? std::string() : std::string(earhip_last_error());
-      for (int w : warnings) {
-        // (libear's messages: src/direct_speakers/gain_calculator_direct_speakers.cpp:118-120, :132-134)
-        if (w == (int)Warning::Code::FREQ_NOT_LFE)
-          warning_cb({Warning::Code::FREQ_NOT_LFE, "frequency indication present but does not indicate an LFE channel"});
-        else if (w == (int)Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH)
-          warning_cb({Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH,
-                      "LFE indication from frequency element does not match speakerLabel"});
-      }
-      hip::check(status, error);
+      const int status = earhip_direct_speakers_calculate(h_, n, rows.md.data(), g.data(), warnings.data());
+      detail::DirectSpeakersRows::finish(status, warnings, warning_cb);
       layout_.scatter(n, g.data(), gains);
     }
 

@@ -1,6 +1,6 @@
 // ear/hip_batch.hpp — what the mirror's gain calculators and device batches share, each piece once: the native layout behind
 // a caller's Layout and the scatter of its rows (LayoutBinding), the single-block calculate, the polar and the Cartesian
-// Objects rows, the allocentric handle, the zone conversion, and the device batch: a block of host memory the device
+// Objects rows, the DirectSpeakers rows, the allocentric handle, the zone conversion, and the device batch: a block of host memory the device
 // reaches, carved into typed arrays (Carver, DeviceBatch), and the step after the device call (finish).
 #pragma once
 #include <cstdint>
@@ -12,6 +12,7 @@
 
 #include "hip.hpp"
 #include "metadata.hpp"
+#include "warnings.hpp"
 
 namespace ear {
   namespace detail {
@@ -129,6 +130,54 @@ namespace ear {
         gain[i] = m.gain, diffuse[i] = m.diffuse;
       }
       std::vector<double> az, el, dist, width, height, depth, gain, diffuse;
+    };
+
+    /// The rows of a DirectSpeakers batch as group I takes them, with the label pointers they refer to (`metadata` must
+    /// outlive them).  The polar position and its bounds are filled in whatever the position is; the two screenEdgeLock
+    /// fields say whether a lock is set.
+    struct DirectSpeakersRows {
+      explicit DirectSpeakersRows(const std::vector<DirectSpeakersTypeMetadata> &metadata)
+          : md(metadata.size()), labels(metadata.size()) {
+        for (size_t i = 0; i < metadata.size(); i++) {
+          const DirectSpeakersTypeMetadata &m = metadata[i];
+          earhip_ds_metadata &c = md[i];
+          c = earhip_ds_metadata();
+          for (auto &l : m.speakerLabels) labels[i].push_back(l.c_str());
+          c.n_labels = (int)labels[i].size();
+          c.labels = labels[i].data();
+          c.cartesian = m.position.isCartesian;
+          const PolarSpeakerPosition &p = m.position.polar;
+          c.azimuth = p.azimuth, c.elevation = p.elevation, c.distance = p.distance;
+          c.has_azimuth_min = (bool)p.azimuthMin, c.azimuth_min = p.azimuthMin.value_or(0.0);
+          c.has_azimuth_max = (bool)p.azimuthMax, c.azimuth_max = p.azimuthMax.value_or(0.0);
+          c.has_elevation_min = (bool)p.elevationMin, c.elevation_min = p.elevationMin.value_or(0.0);
+          c.has_elevation_max = (bool)p.elevationMax, c.elevation_max = p.elevationMax.value_or(0.0);
+          c.has_distance_min = (bool)p.distanceMin, c.distance_min = p.distanceMin.value_or(0.0);
+          c.has_distance_max = (bool)p.distanceMax, c.distance_max = p.distanceMax.value_or(0.0);
+          c.screen_edge_lock_horizontal = (bool)p.screenEdgeLock.horizontal;
+          c.screen_edge_lock_vertical = (bool)p.screenEdgeLock.vertical;
+          c.has_low_pass = (bool)m.channelFrequency.lowPass, c.low_pass = m.channelFrequency.lowPass.value_or(0.0);
+          c.has_high_pass = (bool)m.channelFrequency.highPass, c.high_pass = m.channelFrequency.highPass.value_or(0.0);
+          c.audio_pack_format_id = m.audioPackFormatID ? m.audioPackFormatID.get().c_str() : nullptr;
+        }
+      }
+      /// After the call (status: what it returned; warnings: its warnings_out): every warning to warning_cb in order, then
+      /// the throw for a failed call
+      static void finish(int status, const std::vector<int> &warnings, const WarningCB &warning_cb) {
+        const std::string error = status == EARHIP_OK ? std::string() : std::string(earhip_last_error());
+        for (int w : warnings) {
+          // (libear's messages: src/direct_speakers/gain_calculator_direct_speakers.cpp:118-120, :132-134)
+          if (w == (int)Warning::Code::FREQ_NOT_LFE)
+            warning_cb({Warning::Code::FREQ_NOT_LFE, "frequency indication present but does not indicate an LFE channel"});
+          else if (w == (int)Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH)
+            warning_cb({Warning::Code::FREQ_SPEAKERLABEL_LFE_MISMATCH,
+                        "LFE indication from frequency element does not match speakerLabel"});
+        }
+        hip::check(status, error);
+      }
+
+      std::vector<earhip_ds_metadata> md;
+      std::vector<std::vector<const char *>> labels;
     };
 
     /// Owner of an earhip_allo with the layout it was made for: what the two allocentric calculators are made of.

@@ -29,12 +29,43 @@ namespace ear {
         check(earhip_screen_edges(&reproduction_, e));
       }
 
+      /// the reproduction screen as the C ABI takes it, nullptr without one
+      const earhip_screen *reproduction() const { return has_screen_ ? &reproduction_ : nullptr; }
+
       /// left azimuth, right azimuth, bottom elevation, top elevation of a screen, degrees
       static std::array<double, 4> edges(const Screen &screen) {
         const earhip_screen s = to_c(screen);
         std::array<double, 4> e;
         check(earhip_screen_edges(&s, e.data()));
         return e;
+      }
+
+      /// a Screen as the C ABI takes it (the fields of the other kind are zero)
+      static earhip_screen to_c(const Screen &s) {
+        earhip_screen c = earhip_screen();
+        c.cartesian = s.isCartesian ? 1 : 0;
+        if (s.isCartesian) {
+          c.aspect_ratio = s.cartesian.aspectRatio, c.width_x = s.cartesian.widthX;
+          c.x = s.cartesian.centrePosition.X, c.y = s.cartesian.centrePosition.Y, c.z = s.cartesian.centrePosition.Z;
+        } else {
+          c.aspect_ratio = s.polar.aspectRatio, c.width_azimuth = s.polar.widthAzimuth;
+          c.azimuth = s.polar.centrePosition.azimuth, c.elevation = s.polar.centrePosition.elevation;
+          c.distance = s.polar.centrePosition.distance;
+        }
+        return c;
+      }
+      /// group R's lock codes of a screenEdgeLock's strings; a string that names no edge throws adm_error
+      static unsigned char horizontal_code(const ScreenEdgeLock &lock) {
+        if (!lock.horizontal) return 0;
+        if (*lock.horizontal == "left") return 1;
+        if (*lock.horizontal == "right") return 2;
+        throw adm_error("invalid horizontal screenEdgeLock: '" + *lock.horizontal + "' (left or right)");
+      }
+      static unsigned char vertical_code(const ScreenEdgeLock &lock) {
+        if (!lock.vertical) return 0;
+        if (*lock.vertical == "bottom") return 1;
+        if (*lock.vertical == "top") return 2;
+        throw adm_error("invalid vertical screenEdgeLock: '" + *lock.vertical + "' (bottom or top)");
       }
 
       /// one metadata block, on the calling thread (no device): scaled from m.referenceScreen to the reproduction screen when
@@ -206,19 +237,6 @@ namespace ear {
         g.first.push_back(n);
         return g;
       }
-      static earhip_screen to_c(const Screen &s) {
-        earhip_screen c = earhip_screen();
-        c.cartesian = s.isCartesian ? 1 : 0;
-        if (s.isCartesian) {
-          c.aspect_ratio = s.cartesian.aspectRatio, c.width_x = s.cartesian.widthX;
-          c.x = s.cartesian.centrePosition.X, c.y = s.cartesian.centrePosition.Y, c.z = s.cartesian.centrePosition.Z;
-        } else {
-          c.aspect_ratio = s.polar.aspectRatio, c.width_azimuth = s.polar.widthAzimuth;
-          c.azimuth = s.polar.centrePosition.azimuth, c.elevation = s.polar.centrePosition.elevation;
-          c.distance = s.polar.centrePosition.distance;
-        }
-        return c;
-      }
       // (to_c zeroes the fields of the other kind, so equal screens have equal fields)
       static bool same(const earhip_screen &a, const earhip_screen &b) {
         return a.cartesian == b.cartesian && a.aspect_ratio == b.aspect_ratio && a.azimuth == b.azimuth &&
@@ -233,19 +251,6 @@ namespace ear {
         if (!m.position.isCartesian) throw not_implemented("position: polar");
         if (!m.cartesian) throw not_implemented("cartesian == false");
       }
-      static unsigned char horizontal_code(const ScreenEdgeLock &lock) {
-        if (!lock.horizontal) return 0;
-        if (*lock.horizontal == "left") return 1;
-        if (*lock.horizontal == "right") return 2;
-        throw adm_error("invalid horizontal screenEdgeLock: '" + *lock.horizontal + "' (left or right)");
-      }
-      static unsigned char vertical_code(const ScreenEdgeLock &lock) {
-        if (!lock.vertical) return 0;
-        if (*lock.vertical == "bottom") return 1;
-        if (*lock.vertical == "top") return 2;
-        throw adm_error("invalid vertical screenEdgeLock: '" + *lock.vertical + "' (bottom or top)");
-      }
-
       bool has_screen_;
       earhip_screen reproduction_;
     };

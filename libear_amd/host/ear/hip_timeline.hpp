@@ -7,7 +7,8 @@
 //   BlockTiming, TimelineMode        one block's timing; Objects ramp (Interpolated), beds and HOA do not (Stepped)
 //   timelinePoints, timelineWindow   the rule itself and the blocks a time window needs: pure host functions
 //   ObjectsProgramme                 tracks of (timing, metadata) blocks -> gains -> curves: bind(renderer, t0, t1) sends every
-//                                    selected block of every track through ONE call of each gain calculator and makes ONE
+//                                    selected block of every track through ONE call of each gain calculator (Objects polar
+//                                    and Cartesian, DirectSpeakers) and makes ONE
 //                                    ObjectsRenderer::set_objects_blocks call
 //
 // A long programme is bound window by window: for (t = 0; t < end; t += W) { programme.bind(renderer, t, t + W); render the
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "hip_allo_objects.hpp"
+#include "hip_direct_speakers.hpp"
 #include "hip_objects.hpp"
 #include "hip_screen.hpp"
 
@@ -89,7 +91,9 @@ namespace ear {
 
     /// The tracks of a programme with what each block renders: Objects tracks with one ObjectsTypeMetadata per block, polar or
     /// Cartesian block by block, and stepped tracks (beds, HOA channels) whose constant rows came from the DirectSpeakers or
-    /// the HOA calculator.  bind() turns a time window of it into the curves of a renderer.
+    /// the HOA calculator, or whose DirectSpeakersTypeMetadata bind() sends through ear::hip::DirectSpeakersGainCalculator
+    /// itself (a bed with Cartesian positions or screenEdgeLocks included).  bind() turns a time window of it into the curves of
+    /// a renderer.
     class ObjectsProgramme {
      public:
       /// layout: what the renderer renders to (its channel count is the renderer's n_out); a layout of the caller's own has
@@ -119,12 +123,26 @@ namespace ear {
         t.rows = rows;
         tracks_.push_back(t);
       }
+      /// a DirectSpeakers channel: a stepped track whose rows bind() computes, one DirectSpeakersTypeMetadata per block, polar
+      /// or Cartesian, with or without a screenEdgeLock (locked to the programme's reproduction screen when it has one)
+      void add_direct_speakers(size_t object, int64_t start, const std::vector<BlockTiming> &timings,
+                               const std::vector<DirectSpeakersTypeMetadata> &metadata) {
+        if (metadata.size() != timings.size()) throw invalid_argument("one DirectSpeakersTypeMetadata per block");
+        Track t;
+        t.timing.object = object, t.timing.mode = TimelineMode::Stepped, t.timing.start = start;
+        t.timing.blocks = timings;
+        t.bed = metadata;
+        tracks_.push_back(t);
+      }
       size_t size() const { return tracks_.size(); }
 
       /// Bind the window [t0, t1) of every track to `renderer` (ear::dsp::ObjectsRenderer), whose commit stays the caller's.
       /// Whatever throws — a block list group W refuses, a block a calculator refuses — throws before any curve has changed.
+      /// warning_cb receives the warnings of the DirectSpeakers tracks' selected blocks (e.g. a lowPass on a label that is no
+      /// LFE label), in track order, at every bind.
       template <typename Renderer>
-      void bind(Renderer &renderer, int64_t t0 = kTimelineBegin, int64_t t1 = kTimelineEnd) {
+      void bind(Renderer &renderer, int64_t t0 = kTimelineBegin, int64_t t1 = kTimelineEnd,
+                const WarningCB &warning_cb = default_warning_cb) {
         const size_t n_out = layout_.channels().size();
         if (renderer.n_out() != n_out) throw invalid_argument("the renderer's outputs are not the programme's layout");
         // 1. the blocks each track needs
@@ -135,6 +153,8 @@ namespace ear {
         std::vector<ScreenEdgeLock> polar_locks, cartesian_locks;
         std::vector<size_t> polar_row, cartesian_row;
         bool polar_screen = false, cartesian_screen = false;
+        std::vector<DirectSpeakersTypeMetadata> bed;
+        std::vector<size_t> bed_row;
         for (const Track &t : tracks_) {
           const std::pair<int, int> w = timelineWindow(t.timing.mode, t.timing.start, t.timing.blocks, t0, t1);
           tracks.push_back(t.timing);
@@ -151,6 +171,7 @@ namespace ear {
               polar_screen = polar_screen || on_screen;
             }
           }
+          for (int b = w.first; b <= w.second && !t.bed.empty(); b++) bed.push_back(t.bed[b]), bed_row.push_back(total + b);
           total += t.timing.blocks.size();
         }
         // 2. every selected block through one call of its calculator, behind the screen stage where a block asks for it
@@ -168,6 +189,13 @@ namespace ear {
           cartesian_calc_->calculate(cartesian, d, f);
           put(d, cartesian_row, n_out, direct), put(f, cartesian_row, n_out, diffuse);
         }
+        if (!bed.empty()) {
+          if (!bed_calc_)
+            bed_calc_.reset(screen_ ? new DirectSpeakersGainCalculator(layout_, *screen_, {}, ctx_)
+                                          : new DirectSpeakersGainCalculator(layout_, {}, ctx_));
+          bed_calc_->calculate(bed, d, warning_cb);
+          put(d, bed_row, n_out, direct);
+        }
         for (size_t k = 0; k < tracks_.size(); k++)
           for (size_t b = 0; b < tracks_[k].rows.size(); b++) {
             if (tracks_[k].rows[b].size() != n_out) throw invalid_argument("gain vector length != number of outputs");
@@ -183,6 +211,7 @@ namespace ear {
         std::vector<ObjectsTypeMetadata> metadata;  // Objects tracks
         std::vector<ScreenEdgeLock> locks;
         std::vector<std::vector<float>> rows;  // stepped tracks
+        std::vector<DirectSpeakersTypeMetadata> bed;  // DirectSpeakers tracks
       };
       static void put(const std::vector<std::vector<float>> &rows, const std::vector<size_t> &at, size_t n_out,
                       std::vector<float> &flat) {
@@ -195,6 +224,7 @@ namespace ear {
       std::unique_ptr<ScreenHandler> screen_;
       std::unique_ptr<ObjectsGainCalculator> polar_calc_;
       std::unique_ptr<AllocentricObjectsGainCalculator> cartesian_calc_;
+      std::unique_ptr<DirectSpeakersGainCalculator> bed_calc_;
       std::vector<Track> tracks_;
     };
   }  // namespace hip

@@ -57,7 +57,7 @@ namespace ear {
     Optional<double> distanceMax;
     ScreenEdgeLock screenEdgeLock;
   };
-  /// (refused by the calculator, as in libear)
+  /// (refused by ear::GainCalculatorDirectSpeakers, as in libear; ear::hip::DirectSpeakersGainCalculator takes it)
   struct CartesianSpeakerPosition {
     CartesianSpeakerPosition(double X = 0.0, double Y = 1.0, double Z = 0.0) : X(X), Y(Y), Z(Z) {}
     double X;
